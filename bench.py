@@ -50,6 +50,9 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-flat-rows", action="store_true", help="skip the second, shorter measurement with the reference's flat fp32 rows")
     ap.add_argument("--no-state-check", action="store_true", help="skip the oracle replay of sampled envs over the last timed rollout")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rollout buffer, trained policy state, per-minibatch "
+                         "training statistics) as DIR/<name>.npy, to compare two builds output for output")
     return ap.parse_args()
 
 
@@ -159,6 +162,38 @@ def instrument_voxel(env):
             return orig(*a, **k)
     upd.update = timed
     return ph
+
+
+DUMP_SAMPLE = 1 << 20  # elements kept of an output larger than this: a fixed, seeded sample (keeps a dump far below 64 MB)
+
+
+def dump_outputs(algo, out_dir: str) -> dict:
+    """What one PPO iteration hands its caller, after the last timed one: the rollout buffer it filled (GAE included), the policy's
+    state after train(), and train()'s per-minibatch statistics.  float64 stays float64, everything else is written as float32;
+    arrays keep their shapes, except that those above DUMP_SAMPLE elements become a sample at flat indices drawn from RandomState(0),
+    the same for every run of a shape."""
+    import numpy as np
+    import torch
+    buf = algo.rollout_buffer
+    arrays = {f"rollout_{k}": getattr(buf, k) for k in ("observations", "grid_i8", "actions", "rewards", "episode_starts", "values",
+                                                       "log_probs", "advantages", "returns") if getattr(buf, k, None) is not None}
+    arrays.update({"policy." + k: v for k, v in algo.policy.state_dict().items()})
+    if getattr(algo, "last_train_stats", None) is not None:
+        arrays["train_stats"] = torch.from_numpy(np.asarray(algo.last_train_stats))
+    os.makedirs(out_dir, exist_ok=True)
+    total, files = 0, 0
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.RandomState(0).randint(0, t.numel(), size=DUMP_SAMPLE, dtype=np.int64))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+            name += "_sample"
+        a = t.cpu().numpy().astype(np.float64 if t.dtype in (torch.float64, torch.int64) else np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        total += a.nbytes
+        files += 1
+    assert total <= 64 << 20, f"--dump-outputs wrote {total} bytes"
+    return {"dir": os.path.abspath(out_dir), "files": files, "bytes": total}
 
 
 def one_iteration(algo, phases):
@@ -596,6 +631,7 @@ def main():
         tt = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    dumped = dump_outputs(algo, args.dump_outputs) if args.dump_outputs and rank == 0 else None
 
     env_steps = world * args.envs * args.n_steps * args.steps
     value = env_steps / elapsed
@@ -689,6 +725,8 @@ def main():
                                                    "speedup_over_floor": (args.envs * b_ref / 8e12 * 1e3) / vox_ms},
                      "traffic": traffic, "traffic_source": traffic_src},
     }
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     if dist.is_initialized():
         try:  # (every rank: collectives) what the step's exchanges cost by themselves on this node -- ring or direct, answered by the numbers
             from gennbv_amd import parallel as _par

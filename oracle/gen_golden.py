@@ -11,6 +11,7 @@ only; no reference source is stored.
   F1_postproc   A1  env_train_base.py:513-534 (depth / seg branch; rgb branch unpinned)
   F2_backproj   A2  env_train_gennbv.py:494-533 (+A3 per-point indices, A4 pose idx)
   F4_bresenham  A5  utils.py:43-197 kernel text compiled by oracle/build_ref.py
+  F4_bresenham_random  A5  the same kernel on random sources / targets (RandomState(0), as the test draws them)
   F5_envstep_*  A1-A9 whole Env_Train_GenNBV.step() on a fake simulator fed by the
                 synthetic feed: obs dict, flat obs, rewards, dones, grids per step
   F8_gae        C2 / C-alt  buffers.py:706-724, rsl_rl/storage/rollout_storage.py:130-144
@@ -357,6 +358,23 @@ def gen_bresenham(ref):
     print("F4_bresenham saved", len(cases) // 4, "cases")
 
 
+def gen_bresenham_random(ref):
+    """The inputs tests/test_oracle_golden.py draws with RandomState(0), and the compiled reference kernel's outputs for them."""
+    rs = np.random.RandomState(0)
+    cases = {}
+    for g in (8, 16, 20, 33, 64):
+        for i in range(6):
+            src = rs.randint(-2 * g, 3 * g, size=3).astype(np.int32)
+            tgt = rs.randint(0, g, size=(200, 3)).astype(np.int32)
+            traj, lens = orc.ref_bresenham3d(src, tgt, g)
+            cases[f"g{g}_r{i}_src"] = src
+            cases[f"g{g}_r{i}_tgt"] = tgt
+            cases[f"g{g}_r{i}_traj"] = traj.astype(np.int16)
+            cases[f"g{g}_r{i}_len"] = lens
+    np.savez_compressed(os.path.join(GOLDEN, "F4_bresenham_random.npz"), **cases)
+    print("F4_bresenham_random saved", len(cases) // 4, "cases")
+
+
 def gen_gae(ref):
     torch.manual_seed(3)
     T, N = 128, 8
@@ -403,6 +421,7 @@ def main(names):
     todo = {
         "F2_backproj": lambda: gen_backproj(ref),
         "F4_bresenham": lambda: gen_bresenham(ref),
+        "F4_bresenham_random": lambda: gen_bresenham_random(ref),
         "F8_gae": lambda: gen_gae(ref),
         # BASELINE config 0 shape: 4 envs, 240x320, 16^3 ; 30 steps, resets every <=10 steps
         "F5_envstep_c0": lambda: gen_envstep(ref, "F5_envstep_c0", 4, 240, 320, 16, 3, 30, 10, 1, [0, 1, 2, 9, 10, 29]),

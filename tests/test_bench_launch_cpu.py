@@ -35,3 +35,30 @@ def test_gpus1_needs_no_launcher():
 def test_without_gpus_the_real_bench_fails_loudly():
     r = _run({}, "--gpus", "1", "--steps", "1", "--warmup", "0")
     assert r.returncode != 0 and "GPU" in (r.stderr + r.stdout)
+
+
+def test_dump_outputs_writes_float_arrays_and_a_fixed_sample_of_large_ones(tmp_path):
+    import types
+
+    import numpy as np
+    import torch
+
+    import bench
+    n_big = bench.DUMP_SAMPLE + 12345
+    buf = types.SimpleNamespace(observations=torch.randn(3, 4, 5), grid_i8=torch.randint(-1, 2, (n_big,), dtype=torch.int8),
+                                actions=torch.randn(2, 4, 6), rewards=torch.randn(2, 4, 1),
+                                episode_starts=torch.ones(2, 4, 1, dtype=torch.uint8), values=torch.randn(2, 4, 1),
+                                log_probs=torch.randn(2, 4, 1), advantages=torch.randn(2, 4, 1), returns=torch.randn(2, 4, 1))
+    policy = torch.nn.Sequential(torch.nn.Linear(3, 2), torch.nn.BatchNorm1d(2))
+    algo = types.SimpleNamespace(rollout_buffer=buf, policy=policy, last_train_stats=np.arange(12.0).reshape(4, 3))
+    info = [bench.dump_outputs(algo, str(tmp_path / d)) for d in ("a", "b")]
+    names = sorted(f[:-4] for f in os.listdir(tmp_path / "a"))
+    assert info[0]["files"] == len(names) == 9 + 7 + 1 and info[0]["bytes"] <= 64 << 20
+    assert "rollout_grid_i8_sample" in names and "policy.1.num_batches_tracked" in names and "train_stats" in names
+    for name in names:
+        a, b = (np.load(tmp_path / d / (name + ".npy")) for d in ("a", "b"))
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), name
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "rollout_observations.npy"), buf.observations.numpy())
+    assert np.load(tmp_path / "a" / "train_stats.npy").dtype == np.float64
+    grid = np.load(tmp_path / "a" / "rollout_grid_i8_sample.npy")
+    assert grid.shape == (bench.DUMP_SAMPLE,) and set(np.unique(grid)) <= {-1.0, 0.0, 1.0}

@@ -18,6 +18,7 @@ import os
 import re
 import subprocess
 import sys
+import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -101,8 +102,9 @@ def main():
     ap.add_argument("--kernel", default="k_conv12_fwd_splitILb1E")
     ap.add_argument("--max-keep", type=int, default=7)
     a = ap.parse_args()
-    asm = a.asm or compile_asm("/tmp/isa/encoder_check.s")
-    loads, n_paths, problems = check(asm, a.kernel, a.max_keep)
+    with tempfile.TemporaryDirectory(prefix="gennbv_isa_") as tmp:  # (private: a fixed path under /tmp may belong to another user)
+        asm = a.asm or compile_asm(os.path.join(tmp, "encoder_check.s"))
+        loads, n_paths, problems = check(asm, a.kernel, a.max_keep)
     print(f"{a.kernel}: {len(loads)} opaque requests, {n_paths} first-use sites reached, {len(problems)} problem(s)")
     for p in problems:
         print("  " + p)
