@@ -51,6 +51,7 @@ SIGNATURES = {
     "gnbv_env_obs_rgb": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _i64, _p]),
     "gnbv_env_observe": (_i, [_p, _p, _p, _i, _p, _p, _p, _p, _i, _p, _i64, _p, _p, _i, _i, _i, _i, _p, _p]),
     "gnbv_env_post_step": (_i, [_p, _p]),
+    "gnbv_render_depth": (_i, [_p, _p, _i64, _p, _i, _i, _p, _p, _p, _p, _p]),
     "gnbv_rollout_add": (_i, [_i, _i, _p, _p, _p, _p, _i, _f, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "gnbv_input_autocorr_row_ints": (_i, []),
     "gnbv_input_autocorr": (_i, [_p, _i64, _i, _i, _p, _i64, _p]),
@@ -107,6 +108,12 @@ class GnbvEnvPost(C.Structure):
                 ("coverage_ratio", _p), ("episode_sums", _p), ("cur_reward_sum", _p), ("cur_episode_length", _p),
                 ("ring_reward", _p), ("ring_length", _p), ("ring_state", _p), ("ring_len", _i), ("episode_info", _p), ("episode_state", _p),
                 ("max_episode_length_s", _f)]
+
+
+class GnbvMeshScene(C.Structure):
+    """include/gennbv_hip.h: GnbvMeshScene"""
+    _fields_ = [("n", _i), ("tris", _p), ("tri_obj", _p), ("cell_lo", _p), ("cell_size", _p), ("cell_res", _p),
+                ("cell_base", _p), ("cell_start", _p), ("cell_tris", _p)]
 
 
 class GnbvEncoderParams(C.Structure):

@@ -1,0 +1,220 @@
+"""MeshScene: per-env triangle geometry for the closed-loop renderer (csrc/render.hip).
+
+Each env holds a triangle soup in env-local coordinates (the frame of the poses and of `range_gt`); every triangle
+carries an int object id > 0.  Over each env's triangle bounds lies a uniform grid of cells whose triangle lists are
+stored as CSR (cell -> triangle indices).  A triangle is listed in every cell its axis-aligned bounding box, padded
+by `eps`, overlaps: the lists are a conservative superset, so a ray that crosses a triangle always visits a cell that
+lists it, also where the renderer's fp32 cell walk rounds a boundary crossing by a few ulps.
+
+The lists are built once with torch on the scene's device: set-up work, not hot path.
+
+Cell resolution: with T triangles over a padded box of volume V, the grid aims at CELLS_PER_TRIANGLE * T cells of
+equal edge (edge = (V / (CELLS_PER_TRIANGLE * T)) ** (1/3)), so each axis gets ceil(extent / edge) cells, at least 1
+and at most MAX_CELLS_PER_AXIS.  A box scene (<= 96 triangles) gets a few hundred cells; a 50 k-triangle mesh about
+100 k.
+
+Ground truth grids stay the caller's: `synthetic.Scene` carries them for box scenes, a mesh user loads them like the
+reference does.
+"""
+from __future__ import annotations
+
+import math
+from typing import List, Optional, Sequence
+
+import torch
+
+from .. import _lib
+from . import synthetic as S
+
+CELLS_PER_TRIANGLE = 2.0
+MAX_CELLS_PER_AXIS = 64
+EPS_REL = 1e-4  # AABB padding, relative to the env's largest extent
+EPS_ABS = 1e-5  # metres, for tiny or flat scenes
+
+# the 12 triangles of a box as corner indices (corner bit 0 = x max, bit 1 = y max, bit 2 = z max), wound
+# counter-clockwise seen from outside (normal = (v1 - v0) x (v2 - v0) points out)
+_BOX_TRIS = torch.tensor([
+    [0, 4, 6], [0, 6, 2],  # x min
+    [1, 3, 7], [1, 7, 5],  # x max
+    [0, 1, 5], [0, 5, 4],  # y min
+    [2, 6, 7], [2, 7, 3],  # y max
+    [0, 2, 3], [0, 3, 1],  # z min
+    [4, 5, 7], [4, 7, 6],  # z max
+])
+
+
+def box_triangles(lo: torch.Tensor, hi: torch.Tensor) -> torch.Tensor:
+    """[B,3] corners -> [B*12,3,3] outward-wound triangles."""
+    bits = torch.tensor([[(c >> a) & 1 for a in range(3)] for c in range(8)], dtype=torch.bool, device=lo.device)
+    corners = torch.where(bits[None], hi[:, None, :], lo[:, None, :])  # [B,8,3]
+    return corners[:, _BOX_TRIS.to(lo.device)].reshape(-1, 3, 3)
+
+
+class MeshScene:
+    """Triangles + cell lists of N envs, resident on one device (see the module docstring)."""
+
+    def __init__(self, tris: torch.Tensor, tri_obj: torch.Tensor, tri_env: torch.Tensor, tri_count: torch.Tensor,
+                 cell_lo: torch.Tensor, cell_size: torch.Tensor, cell_res: torch.Tensor, cell_base: torch.Tensor,
+                 cell_start: torch.Tensor, cell_tris: torch.Tensor):
+        self.tris, self.tri_obj, self.tri_env, self.tri_count = tris, tri_obj, tri_env, tri_count
+        self.cell_lo, self.cell_size, self.cell_res, self.cell_base = cell_lo, cell_size, cell_res, cell_base
+        self.cell_start, self.cell_tris = cell_start, cell_tris
+        self.num_envs = int(cell_res.shape[0])
+        self.device = tris.device
+
+    @property
+    def num_triangles(self) -> int:
+        return int(self.tris.shape[0])
+
+    def env_triangles(self, e: int):
+        """(triangles [T_e,3,3], object ids [T_e]) of env e."""
+        s = int(self.tri_count[:e].sum())
+        k = int(self.tri_count[e])
+        return self.tris[s:s + k], self.tri_obj[s:s + k]
+
+    def c_struct(self) -> "_lib.GnbvMeshScene":
+        """include/gennbv_hip.h GnbvMeshScene over this scene's tensors (they must outlive the call)."""
+        s = _lib.GnbvMeshScene()
+        s.n = self.num_envs
+        s.tris = self.tris.data_ptr() if self.tris.numel() else None
+        s.tri_obj = self.tri_obj.data_ptr() if self.tri_obj.numel() else None
+        s.cell_lo, s.cell_size = self.cell_lo.data_ptr(), self.cell_size.data_ptr()
+        s.cell_res, s.cell_base = self.cell_res.data_ptr(), self.cell_base.data_ptr()
+        s.cell_start = self.cell_start.data_ptr()
+        s.cell_tris = self.cell_tris.data_ptr() if self.cell_tris.numel() else None
+        return s
+
+    # ------------------------------------------------------------------
+    @staticmethod
+    def from_boxes(scene: S.Scene, device=None) -> "MeshScene":
+        """12 triangles per valid box of a synthetic scene, object id = box index + 1 (synthetic.render_depth's `which`).
+        Unused boxes (min > max on some axis) give no triangles."""
+        dev = scene.boxes_min.device if device is None else torch.device(device)
+        bmin, bmax = scene.boxes_min.to(dev, torch.float32), scene.boxes_max.to(dev, torch.float32)
+        tris, ids = [], []
+        for e in range(bmin.shape[0]):
+            valid = (bmin[e] <= bmax[e]).all(-1)
+            k = torch.nonzero(valid).flatten()
+            tris.append(box_triangles(bmin[e, k], bmax[e, k]))
+            ids.append((k.to(torch.int32) + 1).repeat_interleave(12))
+        return MeshScene.from_triangles(tris, ids, device=dev)
+
+    @staticmethod
+    def from_triangles(tris: Sequence[torch.Tensor], ids: Sequence[torch.Tensor], device=None,
+                       cells_per_triangle: float = CELLS_PER_TRIANGLE, max_cells_per_axis: int = MAX_CELLS_PER_AXIS) -> "MeshScene":
+        """tris: one [T_e,3,3] float tensor per env (env-local metres), ids: one [T_e] int tensor per env (object ids > 0).
+        An env may have zero triangles."""
+        if len(tris) == 0 or len(tris) != len(ids):
+            raise ValueError("MeshScene.from_triangles: one triangle tensor and one id tensor per env are required")
+        if not 1 <= int(max_cells_per_axis) <= 1024 or not cells_per_triangle > 0:
+            raise ValueError("MeshScene.from_triangles: bad cell resolution parameters")
+        dev = torch.device(device) if device is not None else torch.as_tensor(tris[0]).device
+        n = len(tris)
+        tl, il = [], []
+        for e, (t, i) in enumerate(zip(tris, ids)):
+            t = torch.as_tensor(t)
+            i = torch.as_tensor(i)
+            if t.dim() != 3 or t.shape[1:] != (3, 3) or not t.is_floating_point():
+                raise ValueError(f"env {e}: triangles must be a float [T,3,3] tensor, got {tuple(t.shape)} {t.dtype}")
+            if i.shape != (t.shape[0],) or i.is_floating_point() or i.dtype == torch.bool:
+                raise ValueError(f"env {e}: object ids must be an int [T] tensor matching the triangles")
+            t = t.to(dev, torch.float32)
+            if not torch.isfinite(t).all():
+                raise ValueError(f"env {e}: triangle vertices must be finite")
+            if t.shape[0] and not (int(i.min()) > 0 and int(i.max()) < 2 ** 31):
+                raise ValueError(f"env {e}: object ids must be in [1, 2^31)")
+            tl.append(t)
+            il.append(i.to(dev, torch.int32))
+        count = torch.tensor([t.shape[0] for t in tl], dtype=torch.int64)
+        all_tris = torch.cat(tl, 0).contiguous() if count.sum() else torch.zeros(0, 3, 3, device=dev)
+        all_ids = torch.cat(il, 0).contiguous() if count.sum() else torch.zeros(0, dtype=torch.int32, device=dev)
+        tri_env = torch.repeat_interleave(torch.arange(n, device=dev), count.to(dev))
+        return MeshScene._bin(all_tris, all_ids, tri_env, count, n, dev, float(cells_per_triangle), int(max_cells_per_axis))
+
+    @staticmethod
+    def _bin(tris, ids, tri_env, count, n, dev, cells_per_triangle, max_res) -> "MeshScene":
+        t_total = tris.shape[0]
+        tmin, tmax = tris.amin(1), tris.amax(1)  # [T,3] triangle AABBs
+        big = torch.full((n, 3), float("inf"), device=dev)
+        lo = big.scatter_reduce(0, tri_env[:, None].expand(-1, 3), tmin, "amin")
+        hi = (-big).scatter_reduce(0, tri_env[:, None].expand(-1, 3), tmax, "amax")
+        has = count.to(dev) > 0
+        lo = torch.where(has[:, None], lo, torch.zeros_like(lo))
+        hi = torch.where(has[:, None], hi, torch.zeros_like(hi))
+        eps = (hi - lo).amax(-1) * EPS_REL + EPS_ABS  # [N]
+        lo = lo - 2 * eps[:, None]
+        hi = hi + 2 * eps[:, None]
+        ext = hi - lo
+        # cell edge from the triangle count (module docstring), res = ceil(extent / edge) clamped to [1, max_res]
+        vol = ext.double().prod(-1)
+        edge = (vol / (cells_per_triangle * count.to(dev).double().clamp(min=1))).pow(1.0 / 3.0)
+        res = torch.ceil(ext.double() / edge[:, None]).clamp(1, max_res).to(torch.int64)
+        res = torch.where(has[:, None], res, torch.zeros_like(res))
+        size = torch.where(has[:, None], ext / res.clamp(min=1).to(torch.float32), torch.ones_like(ext))
+        ncell = res.prod(-1)
+        total_cells = int(ncell.sum())
+        if total_cells >= 2 ** 31:
+            raise ValueError("MeshScene: too many cells")
+        base = torch.cumsum(ncell, 0) - ncell
+        # the cell range of each triangle's padded AABB
+        if t_total:
+            e_lo, e_sz, e_res, e_eps = lo[tri_env], size[tri_env], res[tri_env], eps[tri_env, None]
+            i0 = torch.floor((tmin - e_eps - e_lo) / e_sz).to(torch.int64).clamp(min=0)
+            i1 = torch.floor((tmax + e_eps - e_lo) / e_sz).to(torch.int64)
+            i1 = torch.minimum(i1, e_res - 1)
+            i0 = torch.minimum(i0, i1)
+            span = i1 - i0 + 1  # [T,3]
+            per_tri = span.prod(-1)
+            entries = int(per_tri.sum())
+            if entries >= 2 ** 31:
+                raise ValueError("MeshScene: too many cell entries")
+            tri_of = torch.repeat_interleave(torch.arange(t_total, device=dev), per_tri)
+            k = torch.arange(entries, device=dev) - (torch.cumsum(per_tri, 0) - per_tri)[tri_of]
+            sp = span[tri_of]
+            cx = i0[tri_of, 0] + k % sp[:, 0]
+            cy = i0[tri_of, 1] + (k // sp[:, 0]) % sp[:, 1]
+            cz = i0[tri_of, 2] + k // (sp[:, 0] * sp[:, 1])
+            r = res[tri_env[tri_of]]
+            cell = base[tri_env[tri_of]] + cx + r[:, 0] * (cy + r[:, 1] * cz)
+            order = torch.argsort(cell * max(t_total, 1) + tri_of)  # by cell, triangles ascending inside a cell
+            cell_tris = tri_of[order].to(torch.int32).contiguous()
+            counts = torch.bincount(cell, minlength=total_cells)
+        else:
+            cell_tris = torch.zeros(0, dtype=torch.int32, device=dev)
+            counts = torch.zeros(total_cells, dtype=torch.int64, device=dev)
+        cell_start = torch.zeros(total_cells + 1, dtype=torch.int64, device=dev)
+        cell_start[1:] = torch.cumsum(counts, 0)
+        return MeshScene(tris.reshape(-1, 3, 3).contiguous(), ids.contiguous(), tri_env, count,
+                         lo.to(torch.float32).contiguous(), size.to(torch.float32).contiguous(), res.to(torch.int32).contiguous(),
+                         base.to(torch.int32).contiguous(), cell_start.to(torch.int32).contiguous(), cell_tris)
+
+    def cell_box(self, e: int, c: int):
+        """(lo, hi) [3] of local cell index c (x fastest) of env e."""
+        r = self.cell_res[e].tolist()
+        ijk = torch.tensor([c % r[0], (c // r[0]) % r[1], c // (r[0] * r[1])], dtype=torch.float32, device=self.device)
+        lo = self.cell_lo[e] + ijk * self.cell_size[e]
+        return lo, lo + self.cell_size[e]
+
+
+def sphere_triangles(centre: Sequence[float], radius: float, n_lat: int = 12, n_lon: int = 24) -> torch.Tensor:
+    """A closed UV sphere as [T,3,3] outward-wound triangles, T = 2 * n_lon * (n_lat - 1) (test scenes, dense benchmark)."""
+    th = torch.linspace(0, math.pi, n_lat + 1, dtype=torch.float64)
+    ph = torch.linspace(0, 2 * math.pi, n_lon + 1, dtype=torch.float64)[:-1]
+    pts = torch.stack([torch.sin(th)[:, None] * torch.cos(ph)[None], torch.sin(th)[:, None] * torch.sin(ph)[None],
+                       torch.cos(th)[:, None].expand(-1, n_lon)], -1) * radius + torch.tensor(centre, dtype=torch.float64)
+    i = torch.arange(n_lat)[:, None].expand(-1, n_lon)
+    j = torch.arange(n_lon)[None, :].expand(n_lat, -1)
+    j1 = (j + 1) % n_lon
+    a, b, c, d = pts[i, j], pts[i, j1], pts[i + 1, j], pts[i + 1, j1]  # [n_lat, n_lon, 3]
+    upper = torch.stack([a, c, b], -2)[1:]  # the pole rows have one triangle per quad
+    lower = torch.stack([b, c, d], -2)[:-1]
+    return torch.cat([upper.reshape(-1, 3, 3), lower.reshape(-1, 3, 3)]).float()
+
+
+def random_rotation(generator: Optional[torch.Generator] = None) -> torch.Tensor:
+    """A uniformly random 3x3 rotation (QR of a Gaussian matrix)."""
+    q, r = torch.linalg.qr(torch.randn(3, 3, generator=generator, dtype=torch.float64))
+    q = q * torch.sign(torch.diagonal(r))[None]
+    if torch.det(q) < 0:
+        q[:, 0] = -q[:, 0]
+    return q

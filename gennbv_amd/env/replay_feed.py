@@ -93,7 +93,7 @@ class ReplayFeedEnv:
         return cls(cfg, feed_file.load_scene(ff, "cpu"), feed_file.load_feed(ff, device), device, max_episode_length,
                    inv_intrinsics=kinv)
 
-    def __init__(self, cfg: TaskConfig, scene: S.Scene, feed: ReplayFeed, device="cuda:0",
+    def __init__(self, cfg: TaskConfig, scene: S.Scene, feed, device="cuda:0",
                  max_episode_length: Optional[int] = None, inv_intrinsics: Optional[torch.Tensor] = None):
         self.lib = _lib.load()
         self.cfg = cfg
@@ -101,6 +101,9 @@ class ReplayFeedEnv:
         if self.device.type != "cuda":
             raise _lib.GennbvHipError("ReplayFeedEnv runs on the GPU only (no CPU fallback)")
         self.feed = feed
+        # a RenderFeed (env/render_feed.py) renders each frame from the poses of the step: actions -> poses -> render ->
+        # observation -> voxel update, in place of the recorded frame pool
+        self.closed_loop = bool(getattr(feed, "closed_loop", False))
         n = scene.grid_gt.shape[0]
         self.num_envs = n
         self.grid_size = cfg.grid_size
@@ -216,23 +219,27 @@ class ReplayFeedEnv:
             raise _lib.GennbvHipError("compact observation rows need grid_i8_out and the coded grid update")
         assert (compact or obs.shape == (n, cfg.obs_dim)) and obs.dtype == torch.float32 and obs.stride(1) == 1
         stride = obs.stride(0)
-        depth_raw, seg_raw, rgba, c2w = self.feed.next()
+        closed_loop = self.closed_loop
+        if not closed_loop:
+            depth_raw, seg_raw, rgba, c2w = self.feed.next()
         # step(): clip, forced init action, poses; episode_length_buf += 1
         self._post.episode_length_buf = self.episode_length_buf.data_ptr()  # the algorithm may have replaced the tensor
         rgb_off = cfg.state_dim + (0 if compact else cfg.grid_dim)
-        if rgba is None:
-            if self._zero_rgba is None:
-                self._zero_rgba = torch.zeros(n, cfg.camera_height, cfg.camera_width, 4, dtype=torch.uint8, device=self.device)
-            rgba = self._zero_rgba
-        fused_observe = self.fused_observe and getattr(lib, "gnbv_env_observe", None) is not None
-        if fused_observe:
+        if closed_loop:
+            # closed loop (RenderFeed): the frame is rendered from the poses this step computes, so the fused
+            # gnbv_env_observe (poses and the rgba read in one launch) cannot be used
+            self._pre_step(actions_in, st)
+            depth_raw, seg_raw, rgba, c2w = self.feed.render(self.poses)
+            self._observe_slices(obs, stride, self._rgba_or_zero(rgba), rgb_off, st)
+        elif self.fused_observe and getattr(lib, "gnbv_env_observe", None) is not None:
+            rgba = self._rgba_or_zero(rgba)
             # round 5: the three launches below as one (same arithmetic, bit-identical: tests/test_envstep_gpu.py)
             _lib.check(lib.gnbv_env_observe(actions_in.data_ptr(), C.byref(self._lat), self.episode_length_buf.data_ptr(), n, self.actions.data_ptr(),
                                             self.poses.data_ptr(), self.pose_hist.data_ptr(), self.reset_mask.data_ptr(), cfg.stack, obs.data_ptr(), stride,
                                             rgba.data_ptr(), self.gray_prev.data_ptr(), cfg.camera_height, cfg.camera_width, cfg.rgb_h, cfg.rgb_w,
                                             obs.data_ptr() + 4 * rgb_off, st), "gnbv_env_observe")
         else:
-            self._observe_three_launches(actions_in, obs, stride, rgba, rgb_off, st)
+            self._observe_three_launches(actions_in, obs, stride, self._rgba_or_zero(rgba), rgb_off, st)
         # obs["grid"]: tri-class grid straight into the observation rows
         if compact:
             self.updater.update(depth_raw, seg_raw, c2w, self.poses, reset_mask=self.reset_mask, tri_i8_out=grid_i8_out, fp32_out=False)
@@ -246,11 +253,27 @@ class ReplayFeedEnv:
         _lib.check(lib.gnbv_env_post_step(C.byref(self._post), st), "gnbv_env_post_step")
         return obs
 
+    def _rgba_or_zero(self, rgba):
+        if rgba is None:
+            if self._zero_rgba is None:
+                cfg = self.cfg
+                self._zero_rgba = torch.zeros(self.num_envs, cfg.camera_height, cfg.camera_width, 4, dtype=torch.uint8, device=self.device)
+            rgba = self._zero_rgba
+        return rgba
+
     def _observe_three_launches(self, actions_in, obs, stride, rgba, rgb_off, st):
         """step()'s head and the two small observation slices as the three separate launches (`fused_observe = False`)."""
+        self._pre_step(actions_in, st)
+        self._observe_slices(obs, stride, rgba, rgb_off, st)
+
+    def _pre_step(self, actions_in, st):
+        """step()'s head: clip, forced init action, poses; episode_length_buf += 1."""
+        _lib.check(self.lib.gnbv_env_pre_step(actions_in.data_ptr(), C.byref(self._lat), self.episode_length_buf.data_ptr(), self.num_envs,
+                                              self.actions.data_ptr(), self.poses.data_ptr(), st), "gnbv_env_pre_step")
+
+    def _observe_slices(self, obs, stride, rgba, rgb_off, st):
+        """obs["state"] and obs["state_rgb"]: the two small observation slices."""
         cfg, n, lib = self.cfg, self.num_envs, self.lib
-        _lib.check(lib.gnbv_env_pre_step(actions_in.data_ptr(), C.byref(self._lat), self.episode_length_buf.data_ptr(), n,
-                                         self.actions.data_ptr(), self.poses.data_ptr(), st), "gnbv_env_pre_step")
         # (Round 5 ran the two small observation kernels below on a second stream beside the voxel update, joined in front of the
         # post-step kernel: the env step +1.9 ... +5.4 us, the voxel update +4.9 us -- they take slots from k_hit_list's single round of
         # workgroups.  profiles/r05_ab_rollout_obs_overlap.json)

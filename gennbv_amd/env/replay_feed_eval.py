@@ -25,13 +25,17 @@ from .replay_feed import ReplayFeed, ReplayFeedEnv
 
 
 class _RecordingFeed:
-    """Feed proxy that remembers the frame it handed out last."""
+    """Feed proxy that remembers the frame it handed out last (recorded, or rendered by a closed-loop RenderFeed)."""
 
-    def __init__(self, feed: ReplayFeed):
+    def __init__(self, feed):
         self._feed, self.last = feed, None
 
     def next(self):
         self.last = self._feed.next()
+        return self.last
+
+    def render(self, poses):
+        self.last = self._feed.render(poses)
         return self.last
 
     def __getattr__(self, k):
@@ -50,7 +54,7 @@ def gt_cloud_from_grid(grid_gt: torch.Tensor, range_gt: torch.Tensor, voxel_size
 
 
 class ReplayFeedEvalEnv(ReplayFeedEnv):
-    def __init__(self, cfg: TaskConfig, scene: S.Scene, feed: ReplayFeed, device="cuda:0", max_episode_length: Optional[int] = None,
+    def __init__(self, cfg: TaskConfig, scene: S.Scene, feed, device="cuda:0", max_episode_length: Optional[int] = None,
                  pc_gt: Optional[List[torch.Tensor]] = None):
         super().__init__(cfg, scene, _RecordingFeed(feed), device, max_episode_length)
         self.pc_gt = [p.to(self.device, torch.float32).contiguous() for p in

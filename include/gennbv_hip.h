@@ -184,6 +184,30 @@ int gnbv_env_observe(const int64_t *actions_in, const GnbvLattice *lattice /*[ho
                      float *poses_out, float *pose_hist, const uint8_t *reset_mask, int stack, float *obs, int64_t obs_row_stride,
                      const uint8_t *rgba, float *gray_prev, int h, int w, int oh, int ow, float *obs_rgb, void *stream);
 
+/* Closed-loop camera (a new entry point of ABI 5): renders every env from the pose step() computed, in place of the
+ * Isaac Gym camera sensors (env_train_gennbv.py:346-354).  The scene is a triangle soup per env (env-local frame, the
+ * frame of the poses and range_gt) with a uniform cell grid of conservative triangle lists (CSR), built once by
+ * gennbv_amd/env/mesh_scene.py.  [host struct]; every pointer in it is device. */
+typedef struct GnbvMeshScene {
+    int n;                          /* envs */
+    const float *tris;              /* [T,3,3] triangle vertices, all envs concatenated (NULL if T == 0) */
+    const int32_t *tri_obj;         /* [T] object id of each triangle, > 0 */
+    const float *cell_lo;           /* [N,3] lower corner of the env's cell grid */
+    const float *cell_size;         /* [N,3] cell edge per axis */
+    const int32_t *cell_res;        /* [N,3] cells per axis (x fastest); 0,0,0 = an env without triangles */
+    const int32_t *cell_base;       /* [N] global index of the env's first cell */
+    const int32_t *cell_start;      /* [cells + 1] CSR offsets into cell_tris */
+    const int32_t *cell_tris;       /* triangle indices into tris (NULL if empty) */
+} GnbvMeshScene;
+
+/* c2w [N,4,4] from poses (x, y, z, roll, pitch, yaw) in synthetic.camera_to_world's convention (fp64 trig rounded to
+ * fp32, roll ignored), then one ray per pixel d = R * inv_intri * (u, v, 1) cast against the env's triangles and the
+ * ground plane z = 0: depth_raw [N,H,W] = -t (-inf on a miss), seg_raw [N,H,W] = 255 on an object / 0 on ground or
+ * miss, rgba [N,H,W,4] u8 (NULL: none) = synthetic.render_depth's shading of the hit's object id.  Deterministic. */
+int gnbv_render_depth(const GnbvMeshScene *scene /*[host]*/, const float *poses, int64_t poses_row_stride /*floats*/,
+                      const float *inv_intri /*[host] [3,3]*/, int h, int w, float *c2w_out, float *depth_raw, float *seg_raw,
+                      uint8_t *rgba, void *stream);
+
 /* compute_reward (env_train_base.py:377-398), _reward_* / check_termination /
  * reset_idx (env_train_gennbv.py:377-457,535-556), update_extra_episode_info
  * (env_train_base.py:629-639). All pointers device, arrays [N] unless noted. [host struct] */
