@@ -52,6 +52,7 @@ SIGNATURES = {
     "gnbv_env_observe": (_i, [_p, _p, _p, _i, _p, _p, _p, _p, _i, _p, _i64, _p, _p, _i, _i, _i, _i, _p, _p]),
     "gnbv_env_post_step": (_i, [_p, _p]),
     "gnbv_render_depth": (_i, [_p, _p, _i64, _p, _i, _i, _p, _p, _p, _p, _p]),
+    "gnbv_voxelize_surface": (_i, [_p, _p, _p, _i, _p, _p]),
     "gnbv_rollout_add": (_i, [_i, _i, _p, _p, _p, _p, _i, _f, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "gnbv_input_autocorr_row_ints": (_i, []),
     "gnbv_input_autocorr": (_i, [_p, _i64, _i, _i, _p, _i64, _p]),

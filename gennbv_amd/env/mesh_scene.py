@@ -13,11 +13,13 @@ equal edge (edge = (V / (CELLS_PER_TRIANGLE * T)) ** (1/3)), so each axis gets c
 and at most MAX_CELLS_PER_AXIS.  A box scene (<= 96 triangles) gets a few hundred cells; a 50 k-triangle mesh about
 100 k.
 
-Ground truth grids stay the caller's: `synthetic.Scene` carries them for box scenes, a mesh user loads them like the
-reference does.
+Ground truth comes from the same triangles: `ground_truth` voxelizes the surface with gnbv_voxelize_surface
+(csrc/voxelize.hip) under the updater's own voxel bounds, so the coverage reward can reach 1; `surface_points` samples
+the GT point cloud of the evaluation env.  env/mesh_io.py reads Wavefront OBJ files.
 """
 from __future__ import annotations
 
+import ctypes as C
 import math
 from typing import List, Optional, Sequence
 
@@ -187,6 +189,95 @@ class MeshScene:
         return MeshScene(tris.reshape(-1, 3, 3).contiguous(), ids.contiguous(), tri_env, count,
                          lo.to(torch.float32).contiguous(), size.to(torch.float32).contiguous(), res.to(torch.int32).contiguous(),
                          base.to(torch.int32).contiguous(), cell_start.to(torch.int32).contiguous(), cell_tris)
+
+    # ------------------------------------------------------------------
+    def grid_spec(self, grid_size: int, range_gt: Optional[torch.Tensor] = None):
+        """(range_gt [N,6], voxel_size [N,3]) f32 on the CPU for a G^3 ground-truth grid.  range_gt = (xmax, xmin, ymax,
+        ymin, zmax, zmin) of the voxel centres; voxel_size = range / (G - 1) per axis (env_train_gennbv.py:67-80).
+        Without range_gt each env's follows the reference's frame: xmax = -xmin = max |x|, the same for y, zmax = max z,
+        zmin = 0; an env without triangles or with zero extent on an axis then needs an explicit range_gt."""
+        g = int(grid_size)
+        if not 2 <= g <= 1024:
+            raise ValueError(f"grid_size must be in [2, 1024], got {grid_size}")
+        n = self.num_envs
+        if range_gt is None:
+            rows = []
+            for e in range(n):
+                t = self.env_triangles(e)[0].detach().to("cpu", torch.float32).reshape(-1, 3)
+                if t.shape[0] == 0:
+                    raise ValueError(f"env {e} has no triangles: pass range_gt explicitly")
+                mx, my, mz = float(t[:, 0].abs().max()), float(t[:, 1].abs().max()), float(t[:, 2].max())
+                if not (mx > 0 and my > 0 and mz > 0):
+                    raise ValueError(f"env {e} has zero extent on an axis (max|x| {mx}, max|y| {my}, max z {mz}): "
+                                     "pass range_gt explicitly")
+                rows.append([mx, -mx, my, -my, mz, 0.0])
+            rng = torch.tensor(rows, dtype=torch.float32)
+        else:
+            rng = torch.as_tensor(range_gt).detach().to("cpu", torch.float32)
+            if rng.shape != (n, 6):
+                raise ValueError(f"range_gt must be [{n}, 6], got {tuple(rng.shape)}")
+        vox = torch.stack([rng[:, 0] - rng[:, 1], rng[:, 2] - rng[:, 3], rng[:, 4] - rng[:, 5]], -1) / (g - 1)
+        if not (torch.isfinite(rng).all() and torch.isfinite(vox).all() and (vox > 0).all()):
+            raise ValueError("range_gt must be finite with max > min on every axis")
+        return rng.contiguous(), vox.contiguous()
+
+    def ground_truth(self, grid_size: int, range_gt: Optional[torch.Tensor] = None,
+                     env_origins: Optional[torch.Tensor] = None) -> S.Scene:
+        """The env's ground truth as a synthetic.Scene: grid_gt [N,G,G,G] f32 = the surface voxels of the triangles
+        (gnbv_voxelize_surface), range_gt / voxel_size from grid_spec, num_valid_voxel_gt = the voxel count (at least 1),
+        no boxes ([N,0,3], like feed_file.load_scene), env_origins the caller's or make_scenes' layout.  On the GPU only."""
+        rng, vox = self.grid_spec(grid_size, range_gt)
+        g, n, dev = int(grid_size), self.num_envs, self.device
+        if dev.type != "cuda":
+            raise _lib.GennbvHipError("MeshScene.ground_truth voxelizes on the GPU only (no CPU fallback): "
+                                      "build the MeshScene on a cuda device")
+        if env_origins is None:
+            env_origins = S.default_env_origins(n)
+        env_origins = torch.as_tensor(env_origins).to(dev, torch.float32)
+        if env_origins.shape != (n, 3):
+            raise ValueError(f"env_origins must be [{n}, 3], got {tuple(env_origins.shape)}")
+        rng_d, vox_d = rng.to(dev), vox.to(dev)
+        grid = torch.empty(n, g, g, g, dtype=torch.float32, device=dev)
+        self.voxelize_into(grid, rng_d, vox_d)
+        empty = torch.zeros(n, 0, 3, dtype=torch.float32, device=dev)
+        return S.Scene(empty, empty.clone(), grid, rng_d, vox_d, grid.sum(dim=(1, 2, 3)).clamp(min=1.0), env_origins.contiguous())
+
+    def voxelize_into(self, grid_out: torch.Tensor, range_gt: torch.Tensor, voxel_size: torch.Tensor) -> torch.Tensor:
+        """gnbv_voxelize_surface on the current stream: grid_out [N,G,G,G] f32 (every voxel written), range_gt [N,6] and
+        voxel_size [N,3] f32 on the scene's device."""
+        _lib.require_cuda(grid_out, range_gt, voxel_size)
+        n = self.num_envs
+        assert grid_out.dtype == torch.float32 and grid_out.is_contiguous() and grid_out.dim() == 4 and grid_out.shape[0] == n
+        assert range_gt.dtype == torch.float32 and range_gt.is_contiguous() and range_gt.shape == (n, 6)
+        assert voxel_size.dtype == torch.float32 and voxel_size.is_contiguous() and voxel_size.shape == (n, 3)
+        sc = self.c_struct()
+        _lib.check(_lib.load().gnbv_voxelize_surface(C.byref(sc), range_gt.data_ptr(), voxel_size.data_ptr(), int(grid_out.shape[1]),
+                                                     grid_out.data_ptr(), _lib.stream_ptr(self.device)), "gnbv_voxelize_surface")
+        return grid_out
+
+    def surface_points(self, per_env: int, seed: int = 0) -> List[torch.Tensor]:
+        """per_env points [per_env,3] f32 per env, uniform over the env's surface: triangles drawn with probability
+        proportional to area, then a uniform point on the triangle.  One seeded CPU generator in env order, fp64
+        arithmetic: the cloud is the same on every device.  An env without triangles gets [0,3]; an env whose triangles
+        all have zero area draws them uniformly.  The GT cloud (pc_gt) of ReplayFeedEvalEnv."""
+        if int(per_env) < 0:
+            raise ValueError("per_env must be >= 0")
+        gen = torch.Generator(device="cpu").manual_seed(int(seed))
+        out = []
+        for e in range(self.num_envs):
+            t = self.env_triangles(e)[0].detach().to("cpu", torch.float64)
+            if t.shape[0] == 0 or per_env == 0:
+                out.append(torch.zeros(0, 3, dtype=torch.float32, device=self.device))
+                continue
+            area = 0.5 * torch.linalg.cross(t[:, 1] - t[:, 0], t[:, 2] - t[:, 0], dim=-1).norm(dim=-1)
+            w = area if float(area.sum()) > 0 else torch.ones_like(area)
+            k = torch.multinomial(w, int(per_env), replacement=True, generator=gen)
+            r = torch.rand(int(per_env), 2, generator=gen, dtype=torch.float64)
+            s = r[:, :1].sqrt()
+            a, b, c = t[k, 0], t[k, 1], t[k, 2]
+            p = (1.0 - s) * a + (s * (1.0 - r[:, 1:])) * b + (s * r[:, 1:]) * c
+            out.append(p.to(self.device, torch.float32).contiguous())
+        return out
 
     def cell_box(self, e: int, c: int):
         """(lo, hi) [3] of local cell index c (x fastest) of env e."""

@@ -94,12 +94,18 @@ def make_scenes(num_envs: int, grid_size: int, seed: int = 1, device="cpu", max_
         inner = (inside(cx, 0, -hv)[:, :, None, None] & inside(cy, 1, -hv)[:, None, :, None]
                  & inside(cz, 2, -hv)[:, None, None, :])
         grid_gt = torch.maximum(grid_gt, (outer & ~inner).float())
-    side = int(math.ceil(math.sqrt(n)))
-    e = torch.arange(n)
-    origins = torch.stack([(e % side).float() * env_spacing, (e // side).float() * env_spacing, torch.zeros(n)], -1)
+    origins = default_env_origins(n, env_spacing)
     sc = Scene(bmin, bmax, grid_gt, rng, vox, grid_gt.sum(dim=(1, 2, 3)).clamp(min=1.0), origins)
     return Scene(*[t.to(device) for t in (sc.boxes_min, sc.boxes_max, sc.grid_gt, sc.range_gt, sc.voxel_size,
                                           sc.num_valid_voxel_gt, sc.env_origins)])
+
+
+def default_env_origins(num_envs: int, env_spacing: float = 5.0) -> torch.Tensor:
+    """[N,3] f32 world offsets of make_scenes' envs: a ceil(sqrt(N)) wide square lattice on the ground."""
+    n = int(num_envs)
+    side = int(math.ceil(math.sqrt(n)))
+    e = torch.arange(n)
+    return torch.stack([(e % side).float() * env_spacing, (e // side).float() * env_spacing, torch.zeros(n)], -1)
 
 
 def sample_actions(num_envs: int, cfg: TaskConfig, generator: torch.Generator, look_at_scene: bool = True) -> torch.Tensor:

@@ -208,6 +208,17 @@ int gnbv_render_depth(const GnbvMeshScene *scene /*[host]*/, const float *poses,
                       const float *inv_intri /*[host] [3,3]*/, int h, int w, float *c2w_out, float *depth_raw, float *seg_raw,
                       uint8_t *rgba, void *stream);
 
+/* Ground truth from the same triangles (a new entry point of ABI 5): surface voxelization of every env of the scene
+ * under the updater's voxel bounds (gnbv_pose_to_idx): per axis v = voxel_size[a], vmin = fp32(range_min[a] - fp32(0.5 * v)),
+ * voxel i = the closed interval [vmin + i*v, vmin + (i+1)*v] in fp64.  grid_out [N,g,g,g] = 1.0 where the voxel's closed
+ * box meets a closed triangle of the env (a degenerate triangle counts as its segment or point), 0.0 elsewhere.  Every
+ * voxel is written (no zero fill needed); deterministic.  Against the exact answer: no false negatives, and a false
+ * positive only within 2^-36 * (largest |coordinate| of the triangle and the voxel) of the triangle.  range_gt [N,6] and
+ * voxel_size [N,3] are device arrays: an env whose voxel size is not positive and finite cannot be refused without a
+ * host sync, so its grid is filled with NaN.  g outside 2..1024 or a bad scene returns hipErrorInvalidValue. */
+int gnbv_voxelize_surface(const GnbvMeshScene *scene /*[host]*/, const float *range_gt /*[N,6]*/, const float *voxel_size /*[N,3]*/,
+                          int g, float *grid_out /*[N,g,g,g] f32*/, void *stream);
+
 /* compute_reward (env_train_base.py:377-398), _reward_* / check_termination /
  * reset_idx (env_train_gennbv.py:377-457,535-556), update_extra_episode_info
  * (env_train_base.py:629-639). All pointers device, arrays [N] unless noted. [host struct] */
