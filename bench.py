@@ -12,6 +12,14 @@ across ranks (weak scaling), gradients are all-reduced over RCCL.
 
 Inputs are resident in HBM when the timed region starts (a pool of pre-rendered
 synthetic frames).  Rank 0 prints ONE JSON line.
+
+A plain run does what the headline needs: set up, warm up, time the K steps, write
+--dump-outputs, print the line (with the figures taken from the timed steps
+themselves: per-iteration times, phase breakdown, voxel and minibatch rooflines).
+`--full` adds everything that takes work of its own after the timed steps: the
+oracle replay of the last timed rollout (timed_state_check), the encoder roofline,
+the PPO loss delta vs the reference, the CPU baseline, the flat-row measurement,
+the device's rocm-smi clocks and, with N > 1, the exchange probe.
 """
 from __future__ import annotations
 
@@ -47,9 +55,11 @@ def parse():
                     "'ref': the reference's 0.05, under which a random-init policy on the synthetic feed stops some iterations early")
     ap.add_argument("--semantic", action="store_true", help="BASELINE configs[2]: the opt-in semantic branch over the two gray frames "
                     "(Hybrid_Encoder(semantic_branch=True): build-defined, the released reference never reads them)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-flat-rows", action="store_true", help="skip the second, shorter measurement with the reference's flat fp32 rows")
-    ap.add_argument("--no-state-check", action="store_true", help="skip the oracle replay of sampled envs over the last timed rollout")
+    ap.add_argument("--full", action="store_true", help="after the headline, also run the checks and measurements a plain run leaves out "
+                    "(state check, encoder roofline, PPO loss delta vs the reference, CPU baseline, flat rows, rocm-smi clocks, exchange probe)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-flat-rows", action="store_true", help="with --full: skip the second, shorter measurement with the reference's flat fp32 rows")
+    ap.add_argument("--no-state-check", action="store_true", help="with --full: skip the oracle replay of sampled envs over the last timed rollout")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed (rollout buffer, trained policy state, per-minibatch "
                          "training statistics) as DIR/<name>.npy, to compare two builds output for output")
@@ -490,14 +500,16 @@ def _workload_name(args) -> str:
             }.get(key, "custom workload")
 
 
-def device_identity(device) -> dict:
-    """What the timed numbers were taken on: marketing name, architecture, CU count, and -- from rocm-smi, after the timed region -- the
-    clocks, power cap and temperature of the device (box-to-box differences of +-1.5 % exceed a round's gains: VERDICT r5 weak #8)."""
+def device_identity(device, smi: bool = True) -> dict:
+    """What the timed numbers were taken on: marketing name, architecture, CU count, and -- with `smi`, from rocm-smi, after the timed
+    region -- the clocks, power cap and temperature of the device (box-to-box differences of +-1.5 % exceed a round's gains: VERDICT r5 weak #8)."""
     import subprocess
     import torch
     p = torch.cuda.get_device_properties(device)
     out = {"name": p.name, "arch": getattr(p, "gcnArchName", None), "compute_units": p.multi_processor_count,
            "hbm_gb": p.total_memory / 1e9, "torch": torch.__version__, "hip": getattr(torch.version, "hip", None)}
+    if not smi:
+        return out
     try:
         idx = torch.device(device).index or 0
         r = subprocess.run(["rocm-smi", "-d", str(idx), "--showclocks", "--showmaxpower", "--showpower", "--showtemp", "--showperflevel", "--json"],
@@ -568,6 +580,7 @@ def dry_run(args, world: int, rank: int) -> None:
 
 
 def main():
+    t_start = time.perf_counter()
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
@@ -605,6 +618,7 @@ def main():
         torch.cuda.synchronize()
 
     dummy = {"rollout": Phase(), "train": Phase()}
+    t_warm = time.perf_counter()
     for _ in range(args.warmup):
         one_iteration(algo, dummy)
     phases = {"rollout": Phase(), "train": Phase()}
@@ -625,7 +639,8 @@ def main():
         one_iteration(algo, phases)
         iter_ev[i + 1].record()
     barrier()
-    elapsed = time.perf_counter() - t0
+    t1 = time.perf_counter()
+    elapsed = t1 - t0
     iter_ms = [iter_ev[i].elapsed_time(iter_ev[i + 1]) for i in range(args.steps)]
     if world > 1:
         tt = torch.tensor([elapsed], device=device, dtype=torch.float64)
@@ -728,16 +743,17 @@ def main():
     if dumped is not None:
         out["dumped_outputs"] = dumped
     if dist.is_initialized():
-        try:  # (every rank: collectives) what the step's exchanges cost by themselves on this node -- ring or direct, answered by the numbers
-            from gennbv_amd import parallel as _par
-            out["dp_exchange_probe"] = _par.exchange_probe(algo)
-        except Exception as ex:
-            out["dp_exchange_probe"] = {"error": repr(ex)}
+        if args.full:
+            try:  # (every rank: collectives) what the step's exchanges cost by themselves on this node -- ring or direct, answered by the numbers
+                from gennbv_amd import parallel as _par
+                out["dp_exchange_probe"] = _par.exchange_probe(algo)
+            except Exception as ex:
+                out["dp_exchange_probe"] = {"error": repr(ex)}
         # Everything timed is done and reduced: the process group goes away NOW, so that ranks > 0 exit instead of sitting in a
         # collective teardown while rank 0 spends seconds in the CPU-side checks below (none of them communicates).
         barrier()
         dist.destroy_process_group()
-    if rank == 0 and args.backend == "hip" and not args.no_state_check:
+    if rank == 0 and args.full and args.backend == "hip" and not args.no_state_check:
         # Self-check of the TIMED tensors: sampled envs of the last timed rollout are replayed through the CPU oracle from an
         # episode boundary inside the buffer -- same frames, same actions -- and every stored observation row, reward, done flag and
         # the env's final probability / scanned grids are compared bit for bit (tests/state_check.py; the oracle is the checker only).
@@ -750,11 +766,12 @@ def main():
         except Exception as ex:
             out["timed_state_check"] = "error: " + repr(ex)
     if rank == 0:
-        out["device"] = device_identity(device)
+        out["device"] = device_identity(device, smi=args.full)
         try:
             out["train_roofline"] = train_roofline(algo, args, phases["train"].total_ms() / args.steps)
         except Exception as ex:
             out["train_roofline"] = {"error": repr(ex)}
+    if rank == 0 and args.full:
         if world == 1:  # (single-GPU diagnostics: a data-parallel encoder would exchange its BatchNorm sums with ranks that have left)
             try:
                 out["encoder_roofline"] = encoder_roofline(algo, args, device)
@@ -781,6 +798,8 @@ def main():
                 out["config"]["flat_rows"] = {"value": None, "error": repr(ex)}
     _flush_c_stdio()
     if rank == 0:
+        # this rank's wall clock around the steps (from the start of main(): interpreter start-up and exit are not in it)
+        out["wall_seconds"] = {"setup": t_warm - t_start, "warmup": t0 - t_warm, "timed": t1 - t0, "after_steps": time.perf_counter() - t1}
         sys.stdout.flush()
         print(json.dumps(out), flush=True)  # the ONE JSON line, last thing on stdout
 

@@ -62,3 +62,12 @@ def test_dump_outputs_writes_float_arrays_and_a_fixed_sample_of_large_ones(tmp_p
     assert np.load(tmp_path / "a" / "train_stats.npy").dtype == np.float64
     grid = np.load(tmp_path / "a" / "rollout_grid_i8_sample.npy")
     assert grid.shape == (bench.DUMP_SAMPLE,) and set(np.unique(grid)) <= {-1.0, 0.0, 1.0}
+
+
+def test_full_is_opt_in(monkeypatch):
+    """A plain run times the headline only; the checks and extra measurements after the timed steps need --full."""
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--full"])
+    assert bench.parse().full is True

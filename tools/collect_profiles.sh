@@ -5,7 +5,7 @@ R=${1:-r02}
 OUT=$GRAFT_REPO_ROOT/gpurun_out/profiles_$R
 mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
-python bench.py --steps 2 --warmup 1 2>/dev/null | tail -1 > $OUT/bench_n1.json
+python bench.py --steps 2 --warmup 1 --full 2>/dev/null | tail -1 > $OUT/bench_n1.json
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/prof_k
 rocprofv3 --kernel-trace --stats -d /tmp/prof_k -- python $GRAFT_REPO_ROOT/bench.py --steps 1 --warmup 1 --n-steps 16 --no-cpu-baseline --no-flat-rows --no-state-check > /tmp/prof_k.log 2>&1
