@@ -788,16 +788,15 @@ __global__ __launch_bounds__(split::kThreads) void k_conv2_wgrad_split_dma(
 // the outputs: T1[32 taps][16], S1, S2 per workgroup).  Workgroup = 16 waves = (sample, 4 plane pairs of the layer-1 volume),
 // one per CU, walking the 16 row pairs c.  A step = the four 2 x 2 x 32-voxel super-tiles (a, c) of the workgroup.
 //   waves 8-15 (staging): the 16 y1 rows of the NEXT step (8 planes x 2 rows, 32 KiB, each read from global memory exactly once,
-//       contiguous 16-byte requests two steps ahead) go to LDS as fp32 with an 80-byte voxel stride -- the accumulator layout
-//       reads 4 voxels of one channel per lane, and 80 bytes keep the two lane halves of a 32-lane LDS access on different
-//       banks; the next dy2 row of the 5 output planes the workgroup touches goes to a 3-row ring as scaled f16 hi | lo
+//       contiguous 16-byte requests two steps ahead) go to LDS as fp32, transposed: the accumulator layout reads 4 voxels of one
+//       channel per lane, one ds_read_b128 (dsplit::yslot; the x-tiled kernel keeps the older 80-byte voxel stride); the next dy2 row of the 5 output planes the workgroup touches goes to a 3-row ring as scaled f16 hi | lo
 //       planes [voxel][16 channels] with a zero voxel in front and behind (ox = -1, 15) -- out-of-range planes / rows are zeros.
 //   waves 0-7 (compute): wave = (plane pair, class set).  The eight parity classes (ez, ey, ex) of a super-tile need
 //       8 + 4 + 4 + 4 + 2 + 2 + 2 + 1 taps = 14 k-steps of two taps x 16 channels; set X = classes {000, 011, 101, 110} and
 //       set Y = {001, 010, 100, 111} hold 7 k-steps each (weights in registers: 2 x 7 fragments).  Per class: the k-steps'
 //       3 split MFMAs each, then the epilogue of the fp32 kernel unchanged -- ReLU mask and xhat from the staged y1, the
-//       channel sums, and the conv1 weight-gradient contraction T1 += x^T g on fp32 MFMAs with the int8 input slab
-//       (wave-private, requested one step ahead).
+//       channel sums, and the conv1 weight-gradient contraction T1 += x^T g with the input slab (f16, de-interleaved by x mod 4;
+//       requested one step ahead).
 // ---------------------------------------------------------------------------
 namespace dsplit {
 constexpr int kPairs = 4;
@@ -814,7 +813,21 @@ constexpr int kSets = 3, kKSteps = 5;       // class sets per plane pair / k-ste
 constexpr int kConsWaves = kPairs * kSets;  // 12 compute waves
 constexpr int kImgU4 = kSets * kKSteps * 2 * 64, kImgBytes = kImgU4 * 16;  // the B-operand image (all class sets): 30 720
 constexpr int kImgSlotU4 = 2048;            // its slot in the encoder workspace (behind the forward image)
-constexpr int kLdsBytes = 2 * kYBuf + kDyBytes + 2 * kSlabBuf + kImgBytes;
+constexpr int kLdsBytes = 2 * kYBuf + kDyBytes + 2 * kSlabBuf + kImgBytes;  // (k_conv2_dgrad_c1w_splitx)
+// k_conv2_dgrad_c1w_split's own layouts (round 7), read by one wide LDS access per operand of a class epilogue instead of 4 y1 dwords and
+// 8 int8 bytes behind exec-masked branches:
+//   y1: [x parity][voxel group g = j >> 2][channel slot][voxel j & 3] fp32 -- a lane's 4 voxels of its channel are one ds_read_b128.  The
+//       staging waves transpose on store (4 ds_write_b32 per 16-byte request); the channel slot of channel m = 4 q + i in group g is
+//       4 q + (i ^ ((q >> 1) | 2 (g & 1))), which keeps both the b128 reads and the b32 stores free of bank conflicts.
+//   input slab: f16 (converted once, on the store), every row DE-INTERLEAVED by input x mod 4 into sub-rows of 16 values, + a fifth sub-row
+//       x = 4 k + 4 (= sub-row 0 shifted by one; k = 15 is x = 64, past the grid: zero): the 4 voxels of a class lane are x = 16 g + 4 r + q
+//       with q = 2 ex + dx in 0 .. 4, i.e. 4 consecutive values of sub-row q -- one ds_read_b64.  Rows 176 bytes apart (2-way conflicts
+//       at most on the reads; 160 would be 3-way).
+constexpr int kYHalfT = 16 * kC * 4, kYRowT = 2 * kYHalfT, kYBufT = 2 * 2 * kPairs * kYRowT;  // 32 768 per step buffer
+constexpr int kXSub = 32, kXRow = 5 * kXSub + 16, kXBuf = kSlabPlanes * 5 * kXRow;           // 14 960 per step parity
+constexpr int kLdsBytesT = 2 * kYBufT + kDyBytes + 2 * kXBuf + kImgBytes;                     // 143 456
+static_assert(kXBuf % 16 == 0 && kYBufT % 16 == 0 && kLdsBytesT <= 160 * 1024, "LDS layout of k_conv2_dgrad_c1w_split");
+__host__ __device__ constexpr int yslot(int g, int m) { return 4 * (m >> 2) + ((m & 3) ^ (((m >> 2) >> 1) | ((g & 1) << 1))); }
 constexpr int kThreads = 1024, kProdThreads = 256;  // 12 compute + 4 staging waves, four per SIMD (<= 128 registers)
 constexpr int kYSlots = 2 * 2 * kPairs * 128 / kProdThreads;  // 16-byte requests per staging thread and step: 8
 constexpr int kDySlots = (kDyPlanes * 64 + kProdThreads - 1) / kProdThreads;  // 2
@@ -923,11 +936,57 @@ __device__ void prep_w2_split_in_passing(const float *__restrict__ W2, float *__
     prep_w2_split_items<false>(W2, w2img, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
 }
 
-template <int TY>
+// The BN1 ReLU mask fmaf(sc, y, sh) > 0 of one channel as ONE compare: for fixed (sc, sh), fmaf is monotone in y, so the floats y that
+// pass form a half-line -- pass(y) == ((y > thr) != flip) with flip = sc < 0 and thr the largest float on the non-passing side (sc >= 0)
+// or the largest passing float (sc < 0).  Found by bisection over the order of the finite floats with the very fmaf it replaces, so it is
+// exact for every sc and sh (signs, +-0, subnormals, sc == 0, NaN: never passes) -- no rounded -sh / sc.  For finite y; an infinite y can
+// differ only when sc == 0 or sh is infinite (fmaf gives NaN / inf there).  Python model and its check: tests/test_dgrad_epilogue_cpu.py.
+__device__ __forceinline__ float relu_threshold(float sc, float sh, bool &flip)
+{
+    flip = sc < 0.0f;
+    // order key of a float: k(f) = bits | 2^31 for sign 0, ~bits for sign 1 (monotone); finite floats = keys [k(-FLT_MAX), k(FLT_MAX)]
+    auto from_key = [](uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); };
+    constexpr uint32_t kLo = 0x00800000u, kHi = 0xff7fffffu;
+    uint32_t lo = kLo, hi = kHi + 1;  // the first key on the passing side of the (flipped) predicate lies in [lo, hi]
+#pragma unroll 4
+    for (int it = 0; it < 32; ++it) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        const bool t = (fmaf(sc, from_key(mid), sh) > 0.0f) != flip;
+        if (lo < hi) {
+            hi = t ? mid : hi;
+            lo = t ? lo : mid + 1;
+        }
+    }
+    return lo == kLo ? -__builtin_huge_valf() : from_key(lo - 1);
+}
+
+// One 16-byte slab piece (input x = 16 p .. 16 p + 15 of a row, p = lane & 3) -> f16 into the de-interleaved row of the layout above:
+// sub-row q < 4 gets x = 16 p + q + 4 i, sub-row 4 gets x = 16 p + 4 + 4 i (i = 0 .. 3), the last of them from the next piece's first byte
+// (lane + 1 of the same quad; x = 64 for p = 3: zero, as the old int8 row's zero pad byte).  int8 -> f16 as in the forward kernel: the byte b
+// ^ 0x80 under the exponent byte 0x64 is the f16 number 1024 + (b + 128), minus 1152 = b (exact).
+__device__ __forceinline__ void slab_store_f16(const uint4 &sv, char *dst /*row + 8 p*/, int lane)
+{
+    const h2 bias = {(_Float16)1152.0f, (_Float16)1152.0f};
+    auto cvt = [&](uint32_t hi_src, uint32_t lo_src, uint32_t q) {  // [f16(hi_src byte q) | f16(lo_src byte q)]
+        const uint32_t t = __builtin_amdgcn_perm(hi_src, lo_src, 0x0c000c00u | ((4u + q) << 16) | q) ^ 0x64806480u;
+        const h2 f = *reinterpret_cast<const h2 *>(&t) - bias;
+        return *reinterpret_cast<const uint32_t *>(&f);
+    };
+    uint32_t nx = (uint32_t)__builtin_amdgcn_mov_dpp((int)sv.x, 0x39 /*quad_perm [1, 2, 3, 0]*/, 0xf, 0xf, false);
+    nx = (lane & 3) == 3 ? 0u : nx;
+#pragma unroll
+    for (uint32_t q = 0; q < 4; ++q) *reinterpret_cast<uint2 *>(dst + q * dsplit::kXSub) = make_uint2(cvt(sv.y, sv.x, q), cvt(sv.w, sv.z, q));
+    *reinterpret_cast<uint2 *>(dst + 4 * dsplit::kXSub) = make_uint2(cvt(sv.z, sv.y, 0), cvt(nx, sv.w, 0));
+}
+
+// F16 = true: k_conv2_dgrad_c1w_split's layouts (transposed y1, f16 de-interleaved slab; the mask as (y > ythr) != yflip, see
+// relu_threshold).  F16 = false: k_conv2_dgrad_c1w_splitx's (80-byte-stride y1, int8 slab, fmaf(sc, y, sh) > 0).  Same arithmetic, same
+// order of every fp32 accumulation: bit-identical results.
+template <int TY, bool F16>
 __device__ __forceinline__ void dgrad_split_supertile(
-    const char *dyst, const char *ybuf, const int8_t *slab0, const int8_t *slab1, const uint4 *wimg /*this lane's column of the class set's image, in LDS*/,
+    const char *dyst, const char *ybuf, const void *slab0, const void *slab1, const uint4 *wimg /*this lane's column of the class set's image, in LDS*/,
     int ai, int c, bool z1ok, bool y0ok, bool y1ok, int O1, bool tok1, float sc, float sh,
-    float gscale, float &s2, f32x4 &T1a, f32x4 &T1b)
+    float gscale, float &s2, f32x4 &T1a, f32x4 &T1b, float ythr = 0.0f, bool yflip = false)
 {
     using namespace dsplit;
     const int lane = threadIdx.x & (kWave - 1), m = lane & 15, g = lane >> 4;
@@ -965,21 +1024,46 @@ __device__ __forceinline__ void dgrad_split_supertile(
             acc_hl = split::mfma_lo(ah, wl, acc_hl);
         }
         const f32x4 raw = acc_hh + (acc_lh + acc_hl);  // D[i = voxel 4g + r][j = ci = m], scaled by gs 2^10
-        uint32_t ylane = (uint32_t)((4 * g) * kYVox + m * 4);
-        asm volatile("" : "+v"(ylane));
-        const char *yrow = ybuf + ((2 * ai + ez) * 2 + ey) * kYRow + ex * kYHalf + ylane;
-        const int kOff = ((2 * ez) * 5 + 2 * ey) * kSlabRow + 2 * ex;
         float gsv[4];
+        if constexpr (F16) {
+            // every operand of the epilogue is ONE unconditional LDS read (a masked read became an exec-masked branch, and the one behind the
+            // ones-row select waited for all of the wave's LDS reads: lgkmcnt(0) per byte)
+            uint32_t ylane = (uint32_t)(g * 256 + yslot(g, m) * 16);
+            asm volatile("" : "+v"(ylane));
+            const f32x4 yv = *reinterpret_cast<const f32x4 *>(ybuf + ((2 * ai + ez) * 2 + ey) * kYRowT + ex * kYHalfT + ylane);
+            const int xoff = ((2 * ez) * 5 + 2 * ey) * kXRow + 2 * ex * kXSub;
+            const h4 x0 = *reinterpret_cast<const h4 *>(static_cast<const char *>(slab0) + xoff);
+            const uint2 x1r = *reinterpret_cast<const uint2 *>(static_cast<const char *>(slab1) + xoff);
+            const h2 ones2 = {ones_row, ones_row};
+            const uint32_t ones_u = *reinterpret_cast<const uint32_t *>(&ones2);
+            const uint2 x1s = tok1 ? x1r : make_uint2(ones_u, ones_u);  // (two dword selects, not four f16 ones)
+            const h4 x1 = *reinterpret_cast<const h4 *>(&x1s);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            // (the epilogue of dgrad_c1w_subtile: out-of-grid voxels are masked in g, so they never reach the sums or T1)
-            const bool ok = cls_ok && 2 * (4 * g + r) + ex < O1;  // x validity of voxel 4g + r (x = 2j + ex)
-            const float y = ok ? *reinterpret_cast<const float *>(yrow + r * kYVox) : 0.0f;
-            gsv[r] = (ok && fmaf(sc, y, sh) > 0.0f) ? raw[r] * gscale : 0.0f;  // g, scaled into f16 range
-            s2 = fmaf(gsv[r], y, s2);                                          // sum g y: S2 = rstd (sum g y - mean S1), after the loop
-            xs[(ci & 1) * 4 + r] = (_Float16)(short)slab0[kOff + 4 * r];
-            // second tap tile: taps 16 .. 26, and a ROW OF ONES at index 27 -- its row of T1 is sum g = S1, for free
-            xt[(ci & 1) * 4 + r] = tok1 ? (_Float16)(short)slab1[kOff + 4 * r] : ones_row;
+            for (int r = 0; r < 4; ++r) {
+                const bool ok = cls_ok && 2 * (4 * g + r) + ex < O1;  // x validity of voxel 4g + r (x = 2j + ex)
+                const float y = ok ? yv[r] : 0.0f;
+                gsv[r] = (ok && ((yv[r] > ythr) != yflip)) ? raw[r] * gscale : 0.0f;  // == fmaf(sc, y, sh) > 0 (relu_threshold)
+                s2 = fmaf(gsv[r], y, s2);
+                xs[(ci & 1) * 4 + r] = x0[r];
+                xt[(ci & 1) * 4 + r] = x1[r];
+            }
+        } else {
+            uint32_t ylane = (uint32_t)((4 * g) * kYVox + m * 4);
+            asm volatile("" : "+v"(ylane));
+            const char *yrow = ybuf + ((2 * ai + ez) * 2 + ey) * kYRow + ex * kYHalf + ylane;
+            const int kOff = ((2 * ez) * 5 + 2 * ey) * kSlabRow + 2 * ex;
+            const int8_t *sl0 = static_cast<const int8_t *>(slab0), *sl1 = static_cast<const int8_t *>(slab1);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                // (the epilogue of dgrad_c1w_subtile: out-of-grid voxels are masked in g, so they never reach the sums or T1)
+                const bool ok = cls_ok && 2 * (4 * g + r) + ex < O1;  // x validity of voxel 4g + r (x = 2j + ex)
+                const float y = ok ? *reinterpret_cast<const float *>(yrow + r * kYVox) : 0.0f;
+                gsv[r] = (ok && fmaf(sc, y, sh) > 0.0f) ? raw[r] * gscale : 0.0f;  // g, scaled into f16 range
+                s2 = fmaf(gsv[r], y, s2);                                          // sum g y: S2 = rstd (sum g y - mean S1), after the loop
+                xs[(ci & 1) * 4 + r] = (_Float16)(short)sl0[kOff + 4 * r];
+                // second tap tile: taps 16 .. 26, and a ROW OF ONES at index 27 -- its row of T1 is sum g = S1, for free
+                xt[(ci & 1) * 4 + r] = tok1 ? (_Float16)(short)sl1[kOff + 4 * r] : ones_row;
+            }
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -1013,9 +1097,9 @@ __device__ __forceinline__ void conv2_dgrad_c1w_split_body(
 {
     using namespace dsplit;
     extern __shared__ __attribute__((aligned(16))) char split_lds[];
-    char *ybufs = split_lds, *dyst = split_lds + 2 * kYBuf, *slabs = dyst + kDyBytes;
-    uint4 *wlds = reinterpret_cast<uint4 *>(slabs + 2 * kSlabBuf);
-    static_assert(kSlabRow == 80 && kSlabBuf % 16 == 0 && kSlabPieces <= kConsWaves * kWave, "one 16-byte slab request per compute lane");
+    char *ybufs = split_lds, *dyst = split_lds + 2 * kYBufT, *slabs = dyst + kDyBytes;
+    uint4 *wlds = reinterpret_cast<uint4 *>(slabs + 2 * kXBuf);
+    static_assert(kSlabPieces <= kConsWaves * kWave, "one 16-byte slab request per compute lane");
     const int NA = (O1 + 1) >> 1;  // 16 plane pairs / row pairs / voxels per x parity
     int b, a0, a1;
     const bool live = sample_plane_group(B, NA, kPairs, b, a0, a1, vblock);
@@ -1024,7 +1108,7 @@ __device__ __forceinline__ void conv2_dgrad_c1w_split_body(
     float s1 = 0.f, s2 = 0.f, t1_unscale = 0.0f, g_unscale = 0.0f;
     f32x4 T1a = {0.f, 0.f, 0.f, 0.f}, T1b = T1a;
     // (stale LDS may hold NaN patterns: the zero voxels around the dy2 rows and the rows of steps not yet staged must be finite)
-    for (int i = tid; i < (kLdsBytes - kImgBytes) / 16; i += kThreads) reinterpret_cast<uint4 *>(split_lds)[i] = make_uint4(0, 0, 0, 0);
+    for (int i = tid; i < (kLdsBytesT - kImgBytes) / 16; i += kThreads) reinterpret_cast<uint4 *>(split_lds)[i] = make_uint4(0, 0, 0, 0);
     for (int i = tid; i < kImgBytes / 16; i += kThreads) wlds[i] = w2img[i];
     __syncthreads();
     const int nsteps = NA;  // 16 row pairs (even)
@@ -1036,7 +1120,13 @@ __device__ __forceinline__ void conv2_dgrad_c1w_split_body(
         const uint32_t rowC = 2 * 16 * kC, planeC = rowC * O1;
         const uint32_t within = ptid & 127;
         const float *ybase = y1 + (size_t)b * O1 * planeC + within * 4;
-        const uint32_t yst = (within >> 6) * kYHalf + ((within >> 2) & 15) * kYVox + (within & 3) * 16;
+        // a request = channels 4 q .. 4 q + 3 of voxel j = 4 vg + r: stored transposed, channel 4 q + i at slot yslot(vg, 4 q + i) = 4 q + (i ^ s)
+        // -> byte (yst ^ 16 i) of the half row (address bits 4-5 of yst hold s, and 16 (4 q + s) ^ 16 i = 16 (4 q + (i ^ s)))
+        const uint32_t yq = within & 3, yj = (within >> 2) & 15, yvg = yj >> 2;
+        const uint32_t yst = (within >> 6) * kYHalfT + yvg * 256 + yslot(yvg, 4 * yq) * 16 + (yj & 3) * 4;
+        uint32_t ystv[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) ystv[i] = yst ^ (16u * i);
         // dy2: request k of a thread -> piece f = 256 k + ptid = (plane a0 - 1 + (f >> 6), voxel, channel quad); pieces past the
         // fifth plane are duplicates that are never stored
         const int dpiece = ptid & 63, dvox = dpiece >> 2;
@@ -1071,7 +1161,13 @@ __device__ __forceinline__ void conv2_dgrad_c1w_split_body(
             const int rowid = 2 * k + (ptid >> 7), pl = 2 * a0 + (rowid >> 1), row = 2 * c + (rowid & 1);  // (wave-uniform)
             return ld4_nt(ybase + (uint32_t)min(pl, O1 - 1) * planeC + (uint32_t)min(max(row, 0), O1 - 1) * rowC);
         };
-        auto y_store = [&](int k, const float4 &v, int c) { *reinterpret_cast<float4 *>(ybufs + (c & 1) * kYBuf + (2 * k + (ptid >> 7)) * kYRow + yst) = v; };
+        auto y_store = [&](int k, const float4 &v, int c) {
+            char *row = ybufs + (c & 1) * kYBufT + (2 * k + (ptid >> 7)) * kYRowT;
+            *reinterpret_cast<float *>(row + ystv[0]) = v.x;
+            *reinterpret_cast<float *>(row + ystv[1]) = v.y;
+            *reinterpret_cast<float *>(row + ystv[2]) = v.z;
+            *reinterpret_cast<float *>(row + ystv[3]) = v.w;
+        };
         static_assert(kYSlots == 8, "eight y1 requests per staging thread");
         struct StepRegs { float4 y0, y1, y2, y3, y4, y5, y6, y7, d0, d1; };  // (named members: as arrays these 40 registers ended up in scratch memory)
 #define GNBV_DS_LOAD(R, C)                                                                                                      \
@@ -1126,20 +1222,23 @@ __device__ __forceinline__ void conv2_dgrad_c1w_split_body(
         const float sc = scale1[m], sh = shift1[m];
         const bool tok1 = 16 + m < kTaps;
         const int t1 = tok1 ? 16 + m : 0;
-        // the int8 input slab under super-tile (a, c): planes 4 ai .. 4 ai + 4 of the step's shared slab (staged by the staging waves)
-        const int8_t *slab = reinterpret_cast<const int8_t *>(slabs) + ai * (4 * 5 * kSlabRow);
-        const int8_t *slab0 = slab + ((m / 9) * 5 + (m / 3) % 3) * kSlabRow + m % 3 + 16 * kq;
-        const int8_t *slab1 = slab + ((t1 / 9) * 5 + (t1 / 3) % 3) * kSlabRow + t1 % 3 + 16 * kq;
+        // the f16 input slab under super-tile (a, c): planes 4 ai .. 4 ai + 4 of the step's shared slab; lane part = row of tap m (t1), sub-row
+        // of its dx, values 4 kq .. 4 kq + 3
+        const char *slab = slabs + ai * (4 * 5 * kXRow);
+        const char *slab0 = slab + ((m / 9) * 5 + (m / 3) % 3) * kXRow + (m % 3) * kXSub + 8 * kq;
+        const char *slab1 = slab + ((t1 / 9) * 5 + (t1 / 3) % 3) * kXRow + (t1 % 3) * kXSub + 8 * kq;
         // ... which the compute waves stage themselves, ONE 16-byte piece per lane and step, one step ahead (unconditional in every wave:
         // a wave-uniform branch around the request would make the compiler wait for it at the join)
         const int8_t *in = grid_i8 + (rows ? rows[b] : (int64_t)b) * grid_row_stride;
         const int g3m16 = G * G * G - 16;
         const int sp = min(cw * kWave + lane, kSlabPieces - 1), srow = sp >> 2, szr = srow / 5, syr = srow - 5 * szr;
         const int sbase = min(4 * a0 + szr, G - 1) * G * G + 16 * (sp & 3);
-        char *sdst = slabs + srow * kSlabRow + 16 * (sp & 3);
+        char *sdst = slabs + srow * kXRow + 8 * (sp & 3);
         auto slab_req = [&](int c) { return ldu4_nt(in + min(sbase + min(4 * c + syr, G - 1) * G, g3m16)); };
         uint4 sv = slab_req(0);
-        *reinterpret_cast<uint4 *>(sdst) = sv;
+        bool yflip;
+        const float ythr = relu_threshold(sc, sh, yflip);  // (while the first slab piece is in flight)
+        slab_store_f16(sv, sdst, lane);
         sv = slab_req(1);
         const bool z1ok = 2 * a + 1 < O1;
         split_step_barrier();
@@ -1147,14 +1246,15 @@ __device__ __forceinline__ void conv2_dgrad_c1w_split_body(
         auto run = [&](auto ty_c) {
             constexpr int TY = decltype(ty_c)::value;
             for (int c = 0; c < nsteps; ++c) {
-                *reinterpret_cast<uint4 *>(sdst + ((c + 1) & 1) * kSlabBuf) = sv;  // step c + 1's piece (every wave left that buffer at the last barrier)
+                slab_store_f16(sv, sdst + ((c + 1) & 1) * kXBuf, lane);  // step c + 1's piece (every wave left that buffer at the last barrier)
                 sv = slab_req(c + 2);
                 __builtin_amdgcn_sched_barrier(0);
                 const bool y0ok = 2 * c < O1, y1ok = 2 * c + 1 < O1;
-                const char *ybuf = ybufs + (c & 1) * kYBuf;
-                const int sboff = (c & 1) * kSlabBuf;
+                const char *ybuf = ybufs + (c & 1) * kYBufT;
+                const int sboff = (c & 1) * kXBuf;
 #ifndef DSPLIT_ABL_NOCOMP  // (measurement build: the compute waves keep their slab requests and the barriers only -- the staging alone)
-                dgrad_split_supertile<TY>(dyst, ybuf, slab0 + sboff, slab1 + sboff, wimg, ai, c, z1ok, y0ok, y1ok, O1, tok1, sc, sh, gscale, s2, T1a, T1b);
+                dgrad_split_supertile<TY, true>(dyst, ybuf, slab0 + sboff, slab1 + sboff, wimg, ai, c, z1ok, y0ok, y1ok, O1, tok1, sc, sh, gscale, s2, T1a, T1b,
+                                                ythr, yflip);
 #endif
                 split_step_barrier();
             }

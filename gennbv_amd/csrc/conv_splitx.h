@@ -553,7 +553,7 @@ __global__ __launch_bounds__(dsplit::kThreads) void k_conv2_dgrad_c1w_splitx(
                     const bool y0ok = pair_ok && 2 * c < O1, y1ok = pair_ok && 2 * c + 1 < O1;
                     const char *ybuf = ybufs + (c & 1) * kYBuf;
                     const int sboff = (c & 1) * kSlabBuf;
-                    dgrad_split_supertile<TY>(dyst, ybuf, slab0 + sboff, slab1 + sboff, wimg, ai, c, z1ok, y0ok, y1ok, O1x, tok1, sc, sh, gscale, s2, T1a, T1b);
+                    dgrad_split_supertile<TY, false>(dyst, ybuf, slab0 + sboff, slab1 + sboff, wimg, ai, c, z1ok, y0ok, y1ok, O1x, tok1, sc, sh, gscale, s2, T1a, T1b);
                     split_step_barrier();
                 }
             };

@@ -2404,11 +2404,11 @@ GNBV_API int gnbv_encoder_grid_backward(const float *obs_grid, const int64_t *ro
         } else if (split_bwd) {
             static bool attr_dg = false;
             if (!attr_dg) {
-                const hipError_t e = hipFuncSetAttribute((const void *)k_conv2_dgrad_c1w_split, hipFuncAttributeMaxDynamicSharedMemorySize, dsplit::kLdsBytes);
+                const hipError_t e = hipFuncSetAttribute((const void *)k_conv2_dgrad_c1w_split, hipFuncAttributeMaxDynamicSharedMemorySize, dsplit::kLdsBytesT);
                 if (e != hipSuccess) return (int)e;
                 attr_dg = true;
             }
-            hipLaunchKernelGGL(k_conv2_dgrad_c1w_split, dim3(gd), dim3(dsplit::kThreads), dsplit::kLdsBytes, st, dy2_scratch, (const uint4 *)(w.w2split + split::kW2ImgU4),
+            hipLaunchKernelGGL(k_conv2_dgrad_c1w_split, dim3(gd), dim3(dsplit::kThreads), dsplit::kLdsBytesT, st, dy2_scratch, (const uint4 *)(w.w2split + split::kW2ImgU4),
                                (const float *)(w.w2split + split::kW2ImgU4 + dsplit::kImgSlotU4),
                                (const unsigned *)dy2_absmax, (const float *)y1, bn1, bn1 + kC, bn1 + 2 * kC, bn1 + 3 * kC, p->grid_i8, rows, p->grid_i8_row_stride,
                                batch, grid, O1, O2, wg1_part);
