@@ -379,7 +379,8 @@ __device__ __forceinline__ float grad_scale(const unsigned *absmax)
     const float amax = __uint_as_float(bits);
     int e = 0;
     (void)frexpf(amax, &e);  // amax = f 2^e, f in [0.5, 1)
-    const float sc = amax > 0.0f && amax < 3.0e38f ? ldexpf(1.0f, split::kGradBits - e) : 1.0f;
+    // (at most 2^126: inv_pow2 of it stays a normal float, and 2^(14 - e) no longer overflows for amax < 2^-114)
+    const float sc = amax > 0.0f && amax < 3.0e38f ? ldexpf(1.0f, min(split::kGradBits - e, 126)) : 1.0f;
     return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(sc)));  // (the same in every lane: keep it in a scalar register)
 }
 

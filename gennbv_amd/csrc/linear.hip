@@ -429,11 +429,13 @@ __device__ __forceinline__ lh8 ltr_pair(const char *p0, const char *p1)
     const ls8 r = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
     return *reinterpret_cast<const lh8 *>(&r);
 }
-__device__ __forceinline__ float pow2_scale_for(float amax)  // the power of two that puts amax into [2^13, 2^14); 1 for 0 / inf / nan
+// the power of two that puts amax into [2^13, 2^14); 1 for 0 / inf / nan.  At most 2^126 (rows with amax < 2^-113 land lower):
+// 2^(14 - e) was +inf below 2^-114 (0 * inf, inf - inf: a NaN row), and 1 / 2^127 is no longer a normal float.
+__device__ __forceinline__ float pow2_scale_for(float amax)
 {
     int e = 0;
     (void)frexpf(amax, &e);
-    return amax > 0.0f && amax < 3.0e38f ? ldexpf(1.0f, 14 - e) : 1.0f;
+    return amax > 0.0f && amax < 3.0e38f ? ldexpf(1.0f, min(14 - e, 126)) : 1.0f;
 }
 // fragment element offset (in halfs, within one [hi | lo] plane pair start) of row i, contraction index c
 __device__ __forceinline__ size_t frag_pos(int row, int c, int ksteps, int hl)
@@ -785,7 +787,7 @@ static int linear_bwd_dw(const void *workspace, const float *x, int M, int N, in
 GNBV_API int gnbv_linear_bwd_dw_fold(const void *workspace, const float *y, const float *scale, const float *shift, int P, int M, int N, int K, float *dw,
                                      double *sq_partial /*NULL: none*/, void *stream)
 {
-    GNBV_CHECK_ARG(scale && shift);
+    GNBV_CHECK_ARG(scale && shift && gnbv_linear_fold_ok(M, N, K, P));
     return linear_bwd_dw(workspace, y, M, N, K, dw, sq_partial, stream, scale, shift, P);
 }
 

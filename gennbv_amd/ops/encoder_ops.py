@@ -331,16 +331,20 @@ class _LinearReluFn(torch.autograd.Function):
                 mod._dw_sq_written = sq is not None
 
             def launch_dw():
+                # (a write-through target is a slice of the flat gradient buffer, which need not be 16-byte aligned: the kernel
+                # writes a temporary then, copied over -- the same arithmetic wherever the gradient lives, as in _wide_dw)
+                dst = dw if dw.data_ptr() % 16 == 0 else torch.empty(n, k, dtype=torch.float32, device=dev)
                 if bn_state is not None:
                     sc = bn_state.data_ptr() + 4 * 64
-                    _lib.check(lib.gnbv_linear_bwd_dw_fold(ws.data_ptr(), x.data_ptr(), sc, sc + 4 * 16, ctx.fold_p, m, n, k, dw.data_ptr(), _lib.ptr(sq),
+                    _lib.check(lib.gnbv_linear_bwd_dw_fold(ws.data_ptr(), x.data_ptr(), sc, sc + 4 * 16, ctx.fold_p, m, n, k, dst.data_ptr(), _lib.ptr(sq),
                                                            _lib.stream_ptr(dev)), "gnbv_linear_bwd_dw_fold")
-                    return
-                if sq is not None:
-                    _lib.check(lib.gnbv_linear_bwd_dw_sq(ws.data_ptr(), x.data_ptr(), m, n, k, dw.data_ptr(), sq.data_ptr(), _lib.stream_ptr(dev)),
+                elif sq is not None:
+                    _lib.check(lib.gnbv_linear_bwd_dw_sq(ws.data_ptr(), x.data_ptr(), m, n, k, dst.data_ptr(), sq.data_ptr(), _lib.stream_ptr(dev)),
                                "gnbv_linear_bwd_dw_sq")
-                    return
-                _lib.check(lib.gnbv_linear_bwd_dw(ws.data_ptr(), x.data_ptr(), m, n, k, dw.data_ptr(), _lib.stream_ptr(dev)), "gnbv_linear_bwd_dw")
+                else:
+                    _lib.check(lib.gnbv_linear_bwd_dw(ws.data_ptr(), x.data_ptr(), m, n, k, dst.data_ptr(), _lib.stream_ptr(dev)), "gnbv_linear_bwd_dw")
+                if dst is not dw:
+                    dw.copy_(dst)
             if defer:
                 evt = torch.cuda.Event()
                 evt.record(torch.cuda.current_stream(dev))  # (dW needs prep's images only, not the dx product)

@@ -103,7 +103,40 @@ def test_encoder_forward_backward_vs_torch_reference(g, b, conv2, monkeypatch):
     assert float((a - r).abs().max()) <= 2e-5 * float(r.abs().max()) + 1e-6
 
 
-@pytest.mark.parametrize("z1", ["0", "fp32", "splitx"])  # "fp32": GENNBV_CONV_SPLIT=0, the fp32-MFMA conv2 kernels ("0" runs the split-f16 ones at G = 64 / 128)
+@pytest.mark.parametrize("conv2", ["split", "splitx"])
+def test_encoder_backward_of_a_tiny_gradient(conv2, monkeypatch):
+    """d_feats 2^-118 backpropagated through the HIP encoder (G = 64, the split-f16 conv2 kernels): their gradient scale puts max |dy2|
+    into [2^13, 2^14) and was 2^(14 - e), +inf (and its inverse -inf) once max |dy2| fell below 2^-114.  Every gradient must be finite
+    and, rescaled by 2^118, within the tolerances of test_encoder_forward_backward_vs_torch_reference against fp64."""
+    g, b = 64, 4
+    monkeypatch.setenv("GENNBV_CONV_SPLIT", "1")
+    monkeypatch.setenv("GENNBV_SPLITX", "1" if conv2 == "splitx" else "")
+    hip, _, _ = pu.make_policy(g=g, device=DEV, backend="hip", det_weights=True)
+    ref, _, _ = pu.make_policy(g=g, device="cpu", backend="torch", det_weights=True)
+    ref = ref.double()
+    obs = _obs_clear_of_the_relu_threshold(ref, b, g)
+    d = torch.randn(b, 256, generator=torch.Generator().manual_seed(9), dtype=torch.float64)
+    for pol, dev, dt, scale in ((ref, "cpu", torch.float64, 1.0), (hip, DEV, torch.float32, 2.0 ** -118)):
+        pol.set_training_mode(True)
+        pol.zero_grad()
+        f = pol.features_extractor(obs.to(dev, dt))
+        assert f.shape == d.shape
+        f.backward((d * scale).to(dev, dt))
+    for (n1, p1), (n2, p2) in zip(ref.features_extractor.named_parameters(), hip.features_extractor.named_parameters()):
+        assert n1 == n2
+        got = p2.grad.double().cpu()
+        assert bool(torch.isfinite(got).all()), n2
+        got = got * 2.0 ** 118
+        r = p1.grad.double()
+        scale = float(r.abs().max())
+        err = float((r - got).abs().max())
+        if scale < 1e-9:  # (conv bias in front of BatchNorm: analytically zero gradient, as in the test above)
+            assert err < 1e-4 * max(1.0, b / 8), (n1, err)
+        else:
+            assert err <= 2e-5 * scale, (n1, err, scale)
+
+
+@pytest.mark.parametrize("z1",["0", "fp32", "splitx"])  # "fp32": GENNBV_CONV_SPLIT=0, the fp32-MFMA conv2 kernels ("0" runs the split-f16 ones at G = 64 / 128)
 @pytest.mark.parametrize("g,b", [(16, 5), (32, 3), (48, 2), (64, 4), (128, 1), (128, 2), (64, 128)])  # last: the bench's minibatch
 # ((128, 3) with these seeds holds a layer-1 pre-activation on the ReLU knife edge: the fp32-MFMA and the split kernels then miss the fp64
 # conv1 weight gradient by the same 2.8e-4 of its scale -- 0.0024914 and 0.0024921 --, a property of the sample, not of a kernel)
