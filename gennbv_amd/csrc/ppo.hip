@@ -589,20 +589,26 @@ __global__ __launch_bounds__(64 * kMaxHeads) void k_multicategorical_sample(Samp
         for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
         int act = amax;
         if (!a.deterministic) {
-            // inverse CDF: first index whose inclusive prefix sum of exp(l - max) exceeds u * sum
+            // inverse CDF: first index with non-zero mass whose inclusive prefix sum of exp(l - max) exceeds u * sum.  A category of
+            // probability 0 (exp underflows) is never returned: its log-prob of about -1e4 overflows the PPO ratio later.  The scan's
+            // sums are grouped per lane (not monotone in fp32: a zero-mass lane can round above its left neighbour and be the first
+            // to pass the target) and in another order than `s` (at u near 1 no lane may pass it: then the last category with mass).
             const float target = uniforms[(size_t)b * a.n_heads + h] * s;
             float carry = 0.0f;
-            act = d - 1;
+            act = amax;  // (the arg-max has exp(0) = 1: a category with mass)
             for (int j0 = 0; j0 < d; j0 += 64) {
                 const int j = j0 + lane;
-                float c = j < d ? expf(row[j] - mx) : 0.0f;
+                const float e = j < d ? expf(row[j] - mx) : 0.0f;
+                float c = e;
                 for (int o = 1; o < 64; o <<= 1) {
                     const float up = __shfl_up(c, o, 64);
                     if (lane >= o) c += up;
                 }
                 c += carry;
-                const unsigned long long hit = __ballot(j < d && c > target);
+                const unsigned long long hit = __ballot(e > 0.0f && c > target);
                 if (hit) { act = j0 + __ffsll((long long)hit) - 1; break; }
+                const unsigned long long mass = __ballot(e > 0.0f);
+                if (mass) act = j0 + 63 - __clzll((long long)mass);
                 carry = __shfl(c, 63, 64);
             }
         }
