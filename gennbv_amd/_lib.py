@@ -51,8 +51,10 @@ SIGNATURES = {
     "gnbv_env_obs_rgb": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _i64, _p]),
     "gnbv_env_observe": (_i, [_p, _p, _p, _i, _p, _p, _p, _p, _i, _p, _i64, _p, _p, _i, _i, _i, _i, _p, _p]),
     "gnbv_env_post_step": (_i, [_p, _p]),
+    "gnbv_env_post_step_contacts": (_i, [_p, _p, _p]),
     "gnbv_render_depth": (_i, [_p, _p, _i64, _p, _i, _i, _p, _p, _p, _p, _p]),
     "gnbv_voxelize_surface": (_i, [_p, _p, _p, _i, _p, _p]),
+    "gnbv_collide_cylinder": (_i, [_p, _p, _p, _i64, _f, _f, _i, _p, _p]),
     "gnbv_rollout_add": (_i, [_i, _i, _p, _p, _p, _p, _i, _f, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "gnbv_input_autocorr_row_ints": (_i, []),
     "gnbv_input_autocorr": (_i, [_p, _i64, _i, _i, _p, _i64, _p]),
@@ -115,6 +117,11 @@ class GnbvMeshScene(C.Structure):
     """include/gennbv_hip.h: GnbvMeshScene"""
     _fields_ = [("n", _i), ("tris", _p), ("tri_obj", _p), ("cell_lo", _p), ("cell_size", _p), ("cell_res", _p),
                 ("cell_base", _p), ("cell_start", _p), ("cell_tris", _p)]
+
+
+class GnbvMeshObjects(C.Structure):
+    """include/gennbv_hip.h: GnbvMeshObjects"""
+    _fields_ = [("n", _i), ("num_objects", _i), ("env_obj_start", _p), ("obj_aabb", _p), ("obj_tri_start", _p), ("obj_tris", _p)]
 
 
 class GnbvEncoderParams(C.Structure):

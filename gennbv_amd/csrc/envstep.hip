@@ -169,7 +169,9 @@ __global__ __launch_bounds__(256) void k_env_observe(const int64_t *__restrict__
 // ---------------------------------------------------------------------------
 constexpr int kPostThreads = 1024;
 
-__global__ __launch_bounds__(kPostThreads) void k_env_post_step(GnbvEnvPost a)
+// kContacts: reset also on contact[e] != 0 (gnbv_env_post_step_contacts); false is the kernel of gnbv_env_post_step
+template <bool kContacts>
+__global__ __launch_bounds__(kPostThreads) void k_env_post_step(GnbvEnvPost a, const uint8_t *__restrict__ contact)
 {
     __shared__ int s_wave[kPostThreads / kWave + 1];
     __shared__ int s_any;
@@ -196,9 +198,11 @@ __global__ __launch_bounds__(kPostThreads) void k_env_post_step(GnbvEnvPost a)
             const float r_short = __fmul_rn((float)(-extra), a.scale_short);
             rew = __fadd_rn(rew, r_short);
             if (a.only_positive) rew = rew < 0.0f ? 0.0f : rew;  // torch.clip(min=0.)
-            // check_termination :438-457 (no contact forces in a replay feed)
+            // check_termination :438-457: collision_buf (contacts of the drone body; none in a replay feed), | time_out, | coverage
+            bool collided = false;
+            if constexpr (kContacts) collided = contact[e] != 0;
             time_out = len >= a.max_episode_length;
-            reset = time_out || (ratio > a.coverage_threshold);
+            reset = collided || time_out || (ratio > a.coverage_threshold);
             const float r_term = __fmul_rn((reset && !time_out) ? 1.0f : 0.0f, a.scale_term);
             rew = __fadd_rn(rew, r_term);
             a.rewards[e] = rew;
@@ -346,15 +350,28 @@ GNBV_API int gnbv_env_observe(const int64_t *actions_in, const GnbvLattice *latt
     return gnbv_launch_status();
 }
 
+static bool env_post_args_ok(const GnbvEnvPost *args)
+{
+    return args && args->n > 0 && args->ring_len > 0 && args->coverage_count && args->num_valid_voxel_gt && args->prev_ratio &&
+           args->episode_length_buf && args->rewards && args->dones && args->reset_mask && args->step_time_out && args->extras_time_outs &&
+           args->coverage_ratio && args->episode_sums && args->cur_reward_sum && args->cur_episode_length && args->ring_reward &&
+           args->ring_length && args->ring_state && (!args->episode_info || (args->episode_state && args->max_episode_length_s > 0.0f));
+}
+
 GNBV_API int gnbv_env_post_step(const GnbvEnvPost *args, void *stream)
 {
-    GNBV_CHECK_ARG(args && args->n > 0 && args->ring_len > 0);
-    GNBV_CHECK_ARG(args->coverage_count && args->num_valid_voxel_gt && args->prev_ratio && args->episode_length_buf);
-    GNBV_CHECK_ARG(args->rewards && args->dones && args->reset_mask && args->step_time_out && args->extras_time_outs);
-    GNBV_CHECK_ARG(args->coverage_ratio && args->episode_sums && args->cur_reward_sum && args->cur_episode_length);
-    GNBV_CHECK_ARG(args->ring_reward && args->ring_length && args->ring_state);
-    GNBV_CHECK_ARG(!args->episode_info || (args->episode_state && args->max_episode_length_s > 0.0f));
-    hipLaunchKernelGGL(k_env_post_step, dim3(1), dim3(kPostThreads), 0, gnbv_stream(stream), *args);
+    GNBV_CHECK_ARG(env_post_args_ok(args));
+    hipLaunchKernelGGL(k_env_post_step<false>, dim3(1), dim3(kPostThreads), 0, gnbv_stream(stream), *args, nullptr);
+    return gnbv_launch_status();
+}
+
+GNBV_API int gnbv_env_post_step_contacts(const GnbvEnvPost *args, const uint8_t *contact, void *stream)
+{
+    GNBV_CHECK_ARG(env_post_args_ok(args));
+    if (contact == nullptr)
+        hipLaunchKernelGGL(k_env_post_step<false>, dim3(1), dim3(kPostThreads), 0, gnbv_stream(stream), *args, nullptr);
+    else
+        hipLaunchKernelGGL(k_env_post_step<true>, dim3(1), dim3(kPostThreads), 0, gnbv_stream(stream), *args, contact);
     return gnbv_launch_status();
 }
 

@@ -16,6 +16,10 @@ and at most MAX_CELLS_PER_AXIS.  A box scene (<= 96 triangles) gets a few hundre
 Ground truth comes from the same triangles: `ground_truth` voxelizes the surface with gnbv_voxelize_surface
 (csrc/voxelize.hip) under the updater's own voxel bounds, so the coverage reward can reach 1; `surface_points` samples
 the GT point cloud of the evaluation env.  env/mesh_io.py reads Wavefront OBJ files.
+
+Collision termination uses the same triangles as closed solids: `objects` indexes them per (env, object id) -- the
+objects of each env, each object's AABB and triangle list, CSR, built once with torch -- and `collide` runs
+gnbv_collide_cylinder (csrc/collide.hip) for a CollisionBody (env/collision.py) at given poses.
 """
 from __future__ import annotations
 
@@ -63,6 +67,7 @@ class MeshScene:
         self.cell_start, self.cell_tris = cell_start, cell_tris
         self.num_envs = int(cell_res.shape[0])
         self.device = tris.device
+        self._objects = None
 
     @property
     def num_triangles(self) -> int:
@@ -85,6 +90,63 @@ class MeshScene:
         s.cell_start = self.cell_start.data_ptr()
         s.cell_tris = self.cell_tris.data_ptr() if self.cell_tris.numel() else None
         return s
+
+    def objects(self) -> dict:
+        """The per-object index of gnbv_collide_cylinder (built on the first call, then kept), tensors on the scene's device:
+        env_obj_start [N+1] i32 (CSR: env e's objects), obj_id [K] i32 (ascending within an env), obj_aabb [K,6] f32
+        (xmin, ymin, zmin, xmax, ymax, zmax of the object's vertices), obj_tri_start [K+1] i32 and obj_tris i32 (CSR: the
+        object's triangle indices, ascending)."""
+        if self._objects is None:
+            dev, n, t = self.device, self.num_envs, self.num_triangles
+            key = self.tri_env.to(torch.int64) * 2 ** 31 + self.tri_obj.to(torch.int64)  # (env, id) in env order, then id order
+            order = torch.sort(key, stable=True).indices
+            uniq, inv, counts = torch.unique_consecutive(key[order], return_inverse=True, return_counts=True)
+            k = int(uniq.shape[0])
+            env_of = torch.div(uniq, 2 ** 31, rounding_mode="floor")
+            env_obj_start = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+            env_obj_start[1:] = torch.cumsum(torch.bincount(env_of, minlength=n), 0)
+            obj_tri_start = torch.zeros(k + 1, dtype=torch.int64, device=dev)
+            obj_tri_start[1:] = torch.cumsum(counts, 0)
+            v = self.tris[order]  # [T,3,3] in object order
+            idx = inv[:, None].expand(-1, 3)
+            lo = torch.full((k, 3), float("inf"), device=dev).scatter_reduce(0, idx, v.amin(1), "amin")
+            hi = torch.full((k, 3), float("-inf"), device=dev).scatter_reduce(0, idx, v.amax(1), "amax")
+            if t >= 2 ** 31:
+                raise ValueError("MeshScene.objects: too many triangles")
+            self._objects = {"env_obj_start": env_obj_start.to(torch.int32).contiguous(),
+                             "obj_id": (uniq - env_of * 2 ** 31).to(torch.int32).contiguous(),
+                             "obj_aabb": torch.cat([lo, hi], 1).to(torch.float32).contiguous(),
+                             "obj_tri_start": obj_tri_start.to(torch.int32).contiguous(),
+                             "obj_tris": order.to(torch.int32).contiguous()}
+        return self._objects
+
+    def objects_c_struct(self) -> "_lib.GnbvMeshObjects":
+        """include/gennbv_hip.h GnbvMeshObjects over `objects()` (the tensors live as long as the scene)."""
+        o = self.objects()
+        s = _lib.GnbvMeshObjects()
+        s.n, s.num_objects = self.num_envs, int(o["obj_id"].shape[0])
+        s.env_obj_start, s.obj_tri_start = o["env_obj_start"].data_ptr(), o["obj_tri_start"].data_ptr()
+        s.obj_aabb = o["obj_aabb"].data_ptr() if o["obj_aabb"].numel() else None
+        s.obj_tris = o["obj_tris"].data_ptr() if o["obj_tris"].numel() else None
+        return s
+
+    def collide(self, poses: torch.Tensor, body, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """gnbv_collide_cylinder on the current stream: contact code [N] u8 of the CollisionBody `body` (env/collision.py) at
+        poses [N, >= 6] f32 (x, y, z, roll, pitch, yaw; env-local, unit row stride): bit 0 a triangle meets the body, bit 1
+        none does and the centre is inside an object, bit 2 the body reaches z <= 0 (body.ground); 0 = free.  On the GPU only."""
+        if self.device.type != "cuda":
+            raise _lib.GennbvHipError("MeshScene.collide runs on the GPU only (no CPU fallback): build the MeshScene on a cuda device")
+        n = self.num_envs
+        _lib.require_cuda(poses, out)
+        assert poses.dtype == torch.float32 and poses.dim() == 2 and poses.shape[0] == n and poses.shape[1] >= 6 and poses.stride(1) == 1
+        if out is None:
+            out = torch.empty(n, dtype=torch.uint8, device=self.device)
+        assert out.dtype == torch.uint8 and out.shape == (n,) and out.is_contiguous()
+        sc, ob = self.c_struct(), self.objects_c_struct()
+        _lib.check(_lib.load().gnbv_collide_cylinder(C.byref(sc), C.byref(ob), poses.data_ptr(), poses.stride(0), float(body.radius),
+                                                     float(body.half_length), int(bool(body.ground)), out.data_ptr(),
+                                                     _lib.stream_ptr(self.device)), "gnbv_collide_cylinder")
+        return out
 
     # ------------------------------------------------------------------
     @staticmethod

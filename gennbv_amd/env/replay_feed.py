@@ -18,6 +18,12 @@ protocol the reference algorithm expects from `EnvWrapperGenNBVTrain`
 The flat observation is written in place by the kernels in the wrapper's key
 order [state | grid | state_rgb]; `step(..., obs_out=rows)` lets the rollout
 buffer hand its own storage to the env (no assemble + copy pass).
+
+`collision=CollisionBody(...)` (env/collision.py) adds the reference's collision
+termination: every step and reset tests the body at the step's poses against the
+mesh's solids (MeshScene.collide) into `collision_buf` [N] u8, and an env with
+contact resets with the termination reward (gnbv_env_post_step_contacts).  The
+mesh is `collision_mesh`, by default the RenderFeed's own.
 """
 from __future__ import annotations
 
@@ -94,7 +100,8 @@ class ReplayFeedEnv:
                    inv_intrinsics=kinv)
 
     def __init__(self, cfg: TaskConfig, scene: S.Scene, feed, device="cuda:0",
-                 max_episode_length: Optional[int] = None, inv_intrinsics: Optional[torch.Tensor] = None):
+                 max_episode_length: Optional[int] = None, inv_intrinsics: Optional[torch.Tensor] = None,
+                 collision=None, collision_mesh=None):
         self.lib = _lib.load()
         self.cfg = cfg
         self.device = torch.device(device)
@@ -106,6 +113,19 @@ class ReplayFeedEnv:
         self.closed_loop = bool(getattr(feed, "closed_loop", False))
         n = scene.grid_gt.shape[0]
         self.num_envs = n
+        # collision termination (check_termination's collision_buf): None keeps the replay feed's "no contacts"
+        self.collision = collision
+        self.collision_mesh = None
+        self.collision_buf = None
+        if collision is not None:
+            mesh = collision_mesh if collision_mesh is not None else getattr(feed, "mesh", None)
+            if mesh is None:
+                raise _lib.GennbvHipError("collision termination needs a mesh: pass collision_mesh (an open-loop feed has none)")
+            if mesh.num_envs != n:
+                raise ValueError(f"collision_mesh must hold {n} envs, got {mesh.num_envs}")
+            mesh.objects()  # the per-object index, built once
+            self.collision_mesh = mesh
+            self.collision_buf = torch.zeros(n, dtype=torch.uint8, device=self.device)
         self.grid_size = cfg.grid_size
         self.max_episode_length = int(cfg.max_episode_length if max_episode_length is None else max_episode_length)
         self.max_episode_length_s = cfg.episode_length_s
@@ -229,6 +249,8 @@ class ReplayFeedEnv:
             # closed loop (RenderFeed): the frame is rendered from the poses this step computes, so the fused
             # gnbv_env_observe (poses and the rgba read in one launch) cannot be used
             self._pre_step(actions_in, st)
+            if self.collision is not None:  # step order: pre-step -> collide -> render -> ... -> post-step with contacts
+                self.collision_mesh.collide(self.poses, self.collision, out=self.collision_buf)
             depth_raw, seg_raw, rgba, c2w = self.feed.render(self.poses)
             self._observe_slices(obs, stride, self._rgba_or_zero(rgba), rgb_off, st)
         elif self.fused_observe and getattr(lib, "gnbv_env_observe", None) is not None:
@@ -240,6 +262,8 @@ class ReplayFeedEnv:
                                             obs.data_ptr() + 4 * rgb_off, st), "gnbv_env_observe")
         else:
             self._observe_three_launches(actions_in, obs, stride, self._rgba_or_zero(rgba), rgb_off, st)
+        if self.collision is not None and not closed_loop:
+            self.collision_mesh.collide(self.poses, self.collision, out=self.collision_buf)
         # obs["grid"]: tri-class grid straight into the observation rows
         if compact:
             self.updater.update(depth_raw, seg_raw, c2w, self.poses, reset_mask=self.reset_mask, tri_i8_out=grid_i8_out, fp32_out=False)
@@ -250,7 +274,10 @@ class ReplayFeedEnv:
         # rewards / termination / reset bookkeeping
         self._ep_step += 1
         self._post.episode_info = self.episode_info_hist[self._ep_step % self._ep_hist].data_ptr()
-        _lib.check(lib.gnbv_env_post_step(C.byref(self._post), st), "gnbv_env_post_step")
+        if self.collision is not None:
+            _lib.check(lib.gnbv_env_post_step_contacts(C.byref(self._post), self.collision_buf.data_ptr(), st), "gnbv_env_post_step_contacts")
+        else:
+            _lib.check(lib.gnbv_env_post_step(C.byref(self._post), st), "gnbv_env_post_step")
         return obs
 
     def _rgba_or_zero(self, rgba):

@@ -219,6 +219,30 @@ int gnbv_render_depth(const GnbvMeshScene *scene /*[host]*/, const float *poses,
 int gnbv_voxelize_surface(const GnbvMeshScene *scene /*[host]*/, const float *range_gt /*[N,6]*/, const float *voxel_size /*[N,3]*/,
                           int g, float *grid_out /*[N,g,g,g] f32*/, void *stream);
 
+/* Collision termination (a new entry point of ABI 5): does the drone body of each env meet that env's scene?  The body is
+ * a closed solid cylinder of radius `radius` and half-length `half_length` (cf2x.urdf base_link: 0.1, 0.02) centred at the
+ * pose's (x, y, z), axis a = R e_z, R = Rz(yaw) Ry(pitch) Rx(roll) evaluated in fp64 from the fp32 poses.  Every object of an env
+ * (a MeshScene object id) is a closed solid: its triangles plus the points of its closed AABB where the generalized winding
+ * number of its triangles has |w| >= 1/2 (for a closed, consistently wound mesh: interior and surface).  The per-object index
+ * is built once by gennbv_amd/env/mesh_scene.py (MeshScene.objects).  [host struct]; every pointer in it is device. */
+typedef struct GnbvMeshObjects {
+    int n;                          /* envs, == GnbvMeshScene.n */
+    int num_objects;                /* K, all envs */
+    const int32_t *env_obj_start;   /* [N+1] CSR: the objects of env e are env_obj_start[e] .. env_obj_start[e+1] - 1 */
+    const float *obj_aabb;          /* [K,6] closed AABB of each object's triangles: xmin, ymin, zmin, xmax, ymax, zmax (NULL if K == 0) */
+    const int32_t *obj_tri_start;   /* [K+1] CSR offsets into obj_tris */
+    const int32_t *obj_tris;        /* the triangle indices (into GnbvMeshScene.tris) of each object (NULL if K == 0) */
+} GnbvMeshObjects;
+
+/* contact_out[e] = bit 0 (S): a triangle of env e meets the solid cylinder (one entirely inside it included) | bit 1 (I): (S)
+ * is false and the centre lies in an object's solid | bit 2 (G): ground != 0 and the body's lowest point
+ * z - (radius sqrt(1 - a_z^2) + half_length |a_z|) is <= 0.  0 = free.  poses [N, >= 6] (x, y, z, roll, pitch, yaw) with a row
+ * stride in floats; an env with a non-finite pose gets 0.  Deterministic (no atomics).  radius > 0 and half_length >= 0
+ * finite, a scene and an index of the same envs, else hipErrorInvalidValue. */
+int gnbv_collide_cylinder(const GnbvMeshScene *scene /*[host]*/, const GnbvMeshObjects *objects /*[host]*/, const float *poses,
+                          int64_t poses_row_stride /*floats*/, float radius, float half_length, int ground, uint8_t *contact_out /*[N]*/,
+                          void *stream);
+
 /* compute_reward (env_train_base.py:377-398), _reward_* / check_termination /
  * reset_idx (env_train_gennbv.py:377-457,535-556), update_extra_episode_info
  * (env_train_base.py:629-639). All pointers device, arrays [N] unless noted. [host struct] */
@@ -258,6 +282,12 @@ typedef struct GnbvEnvPost {
 } GnbvEnvPost;
 
 int gnbv_env_post_step(const GnbvEnvPost *args /*[host]*/, void *stream);
+/* The same with collision termination (a new entry point of ABI 5, no layout changes): check_termination's collision_buf
+ * (env_train_gennbv.py:438-457) is contact [N] u8 (gnbv_collide_cylinder's code; != 0 = collided), and an env resets when
+ * contact[e] != 0 || time_out || coverage ratio > threshold.  A collision is a reset that is not a time-out: it earns the
+ * termination reward, and its episode sums, ring-buffer entries and episode_info behave as on any other reset.
+ * contact == NULL: exactly gnbv_env_post_step. */
+int gnbv_env_post_step_contacts(const GnbvEnvPost *args /*[host]*/, const uint8_t *contact /*[N] or NULL*/, void *stream);
 
 /* Tail of one rollout step in one launch: the time-out bootstrap `rewards += gamma * squeeze(terminal_value * time_outs)`
  * (on_policy_algorithm_grid_obs.py:205-208; same fp32 operation order; terminal_value_stride = 1: env i uses
