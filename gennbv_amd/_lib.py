@@ -91,6 +91,12 @@ SIGNATURES = {
     "gnbv_adam_shard_step": (_i, [_p, _p, _p, _p, _i64, _p, _f, _f, _f, _f, _p, _p, _p]),
     "gnbv_chamfer_workspace_bytes": (_sz, [_i, _i]),
     "gnbv_chamfer_distance": (_i, [_p, _i, _p, _i, _p, _p, _sz, _p]),
+    "gnbv_scan_set_bytes": (_sz, [_i, _i64]),
+    "gnbv_scan_add_frame": (_i, [_p, _p, _p, _p, _p, _i, _i, _f, _p]),
+    "gnbv_scan_clear": (_i, [_p, _p, _p]),
+    "gnbv_scan_workspace_bytes": (_sz, [_i, _i64, _i64]),
+    "gnbv_scan_score": (_i, [_p, _p, _p, _p, _p, _p, _sz, _p]),
+    "gnbv_scan_export": (_i, [_p, _i, _p, _p, _sz, _p]),
     "gnbv_gae_sb3": (_i, [_p, _p, _p, _p, _p, _i, _i, _d, _d, _p, _p, _p]),
     "gnbv_gae_rsl": (_i, [_p, _p, _p, _p, _i, _i, _d, _d, _p, _p, _p]),
 }
@@ -122,6 +128,17 @@ class GnbvMeshScene(C.Structure):
 class GnbvMeshObjects(C.Structure):
     """include/gennbv_hip.h: GnbvMeshObjects"""
     _fields_ = [("n", _i), ("num_objects", _i), ("env_obj_start", _p), ("obj_aabb", _p), ("obj_tri_start", _p), ("obj_tris", _p)]
+
+
+class GnbvScanSet(C.Structure):
+    """include/gennbv_hip.h: GnbvScanSet"""
+    _fields_ = [("n", _i), ("capacity", _i64), ("table", _p), ("keys", _p), ("counts", _p), ("flags", _p)]
+
+
+class GnbvScanGt(C.Structure):
+    """include/gennbv_hip.h: GnbvScanGt"""
+    _fields_ = [("n", _i), ("num_points", _i64), ("pt_start", _p), ("pts", _p), ("orig", _p), ("node_start", _p), ("pow2", _p),
+                ("nodes", _p)]
 
 
 class GnbvEncoderParams(C.Structure):

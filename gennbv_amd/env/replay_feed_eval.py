@@ -10,6 +10,11 @@ rounded to 1 cm, de-duplicated and compared with the env's GT point cloud by Cha
 The back projection is the standalone A1/A2 kernels (`gnbv_post_process_depth`, `gnbv_back_projection`), the metric
 `gnbv_chamfer_distance` (gennbv_amd/eval/metrics.py).  GT clouds: the reference loads one `.pt` per scene (:95-101);
 without files the centres of the occupied GT voxels are used.
+
+`accuracy="device"` keeps each env's episode as a set of 1 cm keys on the device instead (gennbv_amd/eval/scan_accumulator.py):
+per step one launch adds the frame, the finished envs are scored and cleared without a host sync, and `ratios_accuracy` is
+filled from the device on first access after a step.  `reset()` returns the dict it scored into and starts a fresh one
+(env_eval_gennbv.py:122-124), on both paths.
 """
 from __future__ import annotations
 
@@ -19,9 +24,10 @@ import torch
 
 from .. import utils as U
 from ..eval import metrics as M
+from ..eval.scan_accumulator import ScanAccumulator
 from . import synthetic as S
 from .config import TaskConfig
-from .replay_feed import ReplayFeed, ReplayFeedEnv
+from .replay_feed import ReplayFeed, ReplayFeedEnv, _LazyEpisodeInfo
 
 
 class _RecordingFeed:
@@ -53,19 +59,56 @@ def gt_cloud_from_grid(grid_gt: torch.Tensor, range_gt: torch.Tensor, voxel_size
     return out
 
 
+class _LazyAccuracy(_LazyEpisodeInfo):
+    """ratios_accuracy of the device path: {str(env): accuracy} of the envs scored so far in this evaluation, filled with one
+    device -> host copy on the first access after an env step; raises if an env's scan set overflowed."""
+
+    def __init__(self, env):
+        dict.__init__(self)
+        self._env, self._seen = env, -1
+
+    def _fill(self):
+        env = self._env
+        if env is None or self._seen == env._acc_step:
+            return
+        self._seen = env._acc_step
+        for e, a in env.scan.results().items():
+            if not dict.__contains__(self, str(e)):
+                dict.__setitem__(self, str(e), a)
+
+
 class ReplayFeedEvalEnv(ReplayFeedEnv):
     def __init__(self, cfg: TaskConfig, scene: S.Scene, feed, device="cuda:0", max_episode_length: Optional[int] = None,
-                 pc_gt: Optional[List[torch.Tensor]] = None, collision=None, collision_mesh=None):
+                 pc_gt: Optional[List[torch.Tensor]] = None, collision=None, collision_mesh=None, accuracy: str = "host"):
         super().__init__(cfg, scene, _RecordingFeed(feed), device, max_episode_length, collision=collision, collision_mesh=collision_mesh)
         self.pc_gt = [p.to(self.device, torch.float32).contiguous() for p in
                       (pc_gt if pc_gt is not None else gt_cloud_from_grid(scene.grid_gt, scene.range_gt, scene.voxel_size))]
         assert len(self.pc_gt) == self.num_envs
         self._inv_intri = S.inverse_intrinsics(cfg.camera_height, cfg.camera_width, cfg.horizontal_fov)
         self.pts_target_list: List[List[torch.Tensor]] = [[] for _ in range(self.num_envs)]
-        self.ratios_accuracy = {}
+        if accuracy not in ("host", "device"):
+            raise ValueError(f"accuracy must be 'host' or 'device', not {accuracy!r}")
+        self.accuracy = accuracy
+        self.scan = None
+        self._acc_step = 0
+        if accuracy == "device":
+            h, w = cfg.camera_height, cfg.camera_width
+            self.scan = ScanAccumulator(self.num_envs, self.pc_gt, h, w, self._inv_intri, cfg.depth_sense_dist,
+                                        capacity_per_env=h * w * (int(self.max_episode_length) + 1), device=self.device)
+        self.ratios_accuracy = self._new_accuracy_dict()
+
+    def _new_accuracy_dict(self):
+        return _LazyAccuracy(self) if self.scan is not None else {}
 
     def _accumulate_and_score(self) -> None:
         depth_raw, seg_raw, _, c2w = self.feed.last
+        if self.scan is not None:
+            # the frame of this step belongs to the episode that may end on it: add, score the finished envs, then clear them
+            self.scan.add_frame(depth_raw, seg_raw, c2w)
+            self.scan.score(self.reset_buf)
+            self.scan.clear(self.reset_buf)
+            self._acc_step += 1
+            return
         depth, seg = U.post_process_depth(depth_raw, seg_raw, self.cfg.depth_sense_dist)
         pts = U.back_projection_fg(depth, seg, c2w, self._inv_intri)  # list of [n_i, 3]
         for e in range(self.num_envs):
@@ -77,11 +120,18 @@ class ReplayFeedEvalEnv(ReplayFeedEnv):
             self.pts_target_list[e] = []  # reset_idx (:321-322)
 
     def reset(self, obs_out=None):
-        self.pts_target_list = [[] for _ in range(self.num_envs)]
+        scored_into = self.ratios_accuracy
+        if self.scan is not None:
+            scored_into._freeze()  # the previous evaluation's values, before the device state starts over
+            self.scan.reset()
+        else:
+            self.pts_target_list = [[] for _ in range(self.num_envs)]
         obs = super().reset(obs_out)
         self._accumulate_and_score()
         self.extras["time_outs"] = self.extras_time_outs.bool()
-        return obs, self.rew_buf, self.reset_buf.bool(), self.extras, self.ratios_accuracy
+        # env_eval_gennbv.py:122-124: return the dict scored into, and score the next evaluation into a fresh one
+        self.ratios_accuracy = self._new_accuracy_dict()
+        return obs, self.rew_buf, self.reset_buf.bool(), self.extras, scored_into
 
     def step(self, actions: torch.Tensor, obs_out=None):
         obs, rew, dones, infos = super().step(actions, obs_out)
