@@ -2263,7 +2263,7 @@ GNBV_API int gnbv_encoder_grid_backward(const float *obs_grid, const int64_t *ro
 {
     GNBV_CHECK_ARG(p && (obs_grid || (p->grid_i8)) && y1 && y2 && bn_state && d_features && dy2_scratch && dz1_scratch && g && workspace);
     GNBV_CHECK_ARG(p->grid_i8 == nullptr || p->grid_i8_row_stride >= (int64_t)grid * grid * grid);
-    GNBV_CHECK_ARG(batch > 0 && grid >= 7 && workspace_bytes >= gnbv_encoder_workspace_bytes(batch, grid));
+    GNBV_CHECK_ARG(batch > 0 && grid >= 7 && workspace_bytes >= gnbv_encoder_workspace_bytes(batch, grid) && ((uintptr_t)workspace & 255) == 0);
     GNBV_CHECK_ARG(g->w1 && g->b1 && g->bn1_w && g->bn1_b && g->w2 && g->b2 && g->bn2_w && g->bn2_b);
     hipStream_t st = gnbv_stream(stream);
     const int O1 = out_size(grid), O2 = out_size(O1), P2 = O2 * O2 * O2;
