@@ -12,12 +12,11 @@ import pytest
 import torch
 
 from gennbv_amd import _lib
+from tests.abi_check import DEV, SENTINEL, TAIL, _check_written, _out, _ratio, _report, _stream
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 C_REL = 1e-6
 X_SCALE, W_SCALE = 2.0 ** 6, 2.0 ** 12  # (kLinXScale, kLinWScale)
-TAIL, SENTINEL = 64, 1234.5
 
 # (M, N, K): the real layers (fc_grid at 64^3 / 20^3, the pose branch, output_layer_rgb), then M in {16, 48, 112} (dx runs 1, 3 or 7
 # of its 8 row tiles, dW pads its contraction), N in {16, 48, 208} (dW runs a partial set of its 16 row tiles, dx pads its
@@ -26,25 +25,6 @@ SHAPES = [(128, 256, 256), (128, 256, 2400), (128, 256, 1024), (128, 256, 4096),
           (16, 256, 1000), (48, 128, 68), (112, 208, 100), (128, 16, 64), (128, 48, 1000), (16, 16, 64), (48, 208, 4096),
           (112, 48, 68), (128, 208, 100)]
 IDS = [f"{m}x{n}x{k}" for m, n, k in SHAPES]
-
-
-def _stream():
-    return _lib.stream_ptr(torch.device(DEV))
-
-
-def _out(*shape, dtype=torch.float32):
-    """An output buffer prefilled with NaN and followed by a TAIL-element sentinel: (the output view, the whole buffer)."""
-    n = math.prod(shape)
-    buf = torch.full((n + TAIL,), float("nan"), dtype=dtype, device=DEV)
-    buf[n:] = SENTINEL
-    return buf[:n].view(*shape), buf
-
-
-def _check_written(name, body, buf):
-    n = body.numel()
-    bad = int((~torch.isfinite(body)).sum())
-    assert bad == 0, f"{name}: {bad} of {n} elements not written or not finite"
-    assert bool((buf[n:] == SENTINEL).all()), f"{name}: the {TAIL} elements past the output were written"
 
 
 def _inputs(m, n, k, seed):
@@ -88,19 +68,6 @@ def _bound(a, b, bscale, floor=0.0):
     aa, ba = a.abs(), b.abs()
     amax = aa.amax(1, keepdim=True)
     return (C_REL * (aa @ ba) + (2.0 ** -25 / bscale) * aa.sum(1, keepdim=True) + 2.0 ** -37 * amax * ba.sum(0, keepdim=True)) + floor
-
-
-def _ratio(got, want, bound):
-    """Largest |got - want| / bound (an element whose bound is 0 must be exact)."""
-    err = (got.double() - want).abs()
-    r = torch.where(bound > 0, err / bound.clamp_min(1e-300), torch.where(err > 0, math.inf, 0.0))
-    return float(r.max())
-
-
-def _report(what, ratios):
-    line = f"[err/bound] {what}: " + ", ".join(f"{k} {v:.3f}" for k, v in ratios.items())
-    print(line)
-    return line
 
 
 def _check_vs_fp64(what, r, d_out, out, w, x, floor=0.0):
