@@ -97,6 +97,7 @@ SIGNATURES = {
     "gnbv_scan_workspace_bytes": (_sz, [_i, _i64, _i64]),
     "gnbv_scan_score": (_i, [_p, _p, _p, _p, _p, _p, _sz, _p]),
     "gnbv_scan_export": (_i, [_p, _i, _p, _p, _sz, _p]),
+    "gnbv_view_gain": (_i, [_p, _p]),
     "gnbv_gae_sb3": (_i, [_p, _p, _p, _p, _p, _i, _i, _d, _d, _p, _p, _p]),
     "gnbv_gae_rsl": (_i, [_p, _p, _p, _p, _i, _i, _d, _d, _p, _p, _p]),
 }
@@ -139,6 +140,13 @@ class GnbvScanGt(C.Structure):
     """include/gennbv_hip.h: GnbvScanGt"""
     _fields_ = [("n", _i), ("num_points", _i64), ("pt_start", _p), ("pts", _p), ("orig", _p), ("node_start", _p), ("pow2", _p),
                 ("nodes", _p)]
+
+
+class GnbvViewGain(C.Structure):
+    """include/gennbv_hip.h: GnbvViewGain"""
+    _fields_ = [("n", _i), ("k", _i), ("g", _i), ("tri_i8", _p), ("tri_row_stride", _i64), ("poses", _p), ("range_gt", _p),
+                ("voxel_size", _p), ("inv_intri", _p), ("h", _i), ("w", _i), ("stride", _i), ("range", _f), ("gain", _p),
+                ("c2w_out", _p), ("chunk", _i), ("ablate", _i)]
 
 
 class GnbvEncoderParams(C.Structure):

@@ -1,0 +1,120 @@
+"""Baseline view planners to compare a learned policy against: a uniformly random lattice pose and the greedy
+next-best-view planner over the view gain (ops/view_gain.py, csrc/viewgain.hip).
+
+Both speak the protocol `evaluate_policy_grid_obs` uses: `.policy(obs, deterministic=True) -> (actions, None, None)`,
+and `predict(obs)`; actions are int64 [N,6] on the lattice of the task (inside clip_pose_idx_low / clip_pose_idx_up).
+"""
+from __future__ import annotations
+
+from typing import Callable, Optional, Sequence
+
+import torch
+
+from ..env import synthetic as S
+from ..env.config import TaskConfig
+
+
+class LatticeCandidates:
+    """[N,K,6] int64 lattice actions from a seeded CPU generator (the same numbers whatever device they are used on),
+    uniform inside clip_pose_idx_low / clip_pose_idx_up; `look_at_scene` aims them like synthetic.sample_actions."""
+
+    def __init__(self, cfg: TaskConfig, k: int, seed: int, look_at_scene: bool = False):
+        self.cfg, self.k, self.look_at_scene = cfg, int(k), bool(look_at_scene)
+        self.gen = torch.Generator(device="cpu").manual_seed(int(seed))
+        self.low = torch.tensor(cfg.clip_pose_idx_low, dtype=torch.int64)
+        self.up = torch.tensor(cfg.clip_pose_idx_up, dtype=torch.int64)
+
+    def sample(self, num_envs: int, device="cpu") -> torch.Tensor:
+        m = int(num_envs) * self.k
+        if self.look_at_scene:
+            a = S.sample_actions(m, self.cfg, self.gen, look_at_scene=True)
+            a = torch.minimum(torch.maximum(a, self.low), self.up)
+        else:
+            a = torch.stack([torch.randint(int(lo), int(u) + 1, (m,), generator=self.gen) for lo, u in zip(self.low, self.up)], -1)
+        a = a.view(int(num_envs), self.k, 6)
+        dev = torch.device(device)
+        if dev.type == "cuda":  # pinned staging + asynchronous copy: no host synchronisation
+            a = a.pin_memory().to(dev, non_blocking=True)
+        return a
+
+    def poses(self, actions: torch.Tensor) -> torch.Tensor:
+        """poses_from_actions' arithmetic: action * action_unit + clip_pose_low, fp32."""
+        return S.poses_from_actions(actions, self.cfg).float()
+
+
+class RandomLatticePolicy:
+    """A uniformly random lattice pose per env and step."""
+
+    def __init__(self, cfg: TaskConfig, num_envs: int, seed: int):
+        self.num_envs = int(num_envs)
+        self.cands = LatticeCandidates(cfg, 1, seed)
+
+    def __call__(self, obs, deterministic: bool = True):
+        return self.cands.sample(self.num_envs, obs.device)[:, 0], None, None
+
+    @property
+    def policy(self):
+        return self
+
+    def predict(self, obs, state=None, episode_start=None, deterministic: bool = True):
+        return self(obs, deterministic)[0], state
+
+
+def choose(gain: torch.Tensor, weights: Sequence[int], contact: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """gain [N,K,3] int -> index [N] of the candidate with the largest w0 * unknown + w1 * unknown_hit (int64); candidates
+    with contact[N,K] != 0 score -1; ties go to the lowest candidate index."""
+    k = gain.shape[1]
+    score = int(weights[0]) * gain[..., 0].to(torch.int64) + int(weights[1]) * gain[..., 1].to(torch.int64)
+    if contact is not None:
+        score = torch.where(contact != 0, torch.full_like(score, -1), score)
+    # one key per candidate, strictly larger for the lower index at equal score: argmax has a single answer
+    key = score * k + (k - 1 - torch.arange(k, device=score.device))
+    return key.argmax(dim=1)
+
+
+class GreedyGainPolicy:
+    """Greedy next-best view: K random lattice candidates per env and step, the one with the largest
+    w0 * unknown + w1 * unknown_hit of the view gain against the observation's grid wins; with a CollisionBody on the
+    env (and `avoid_collisions`) candidates whose pose collides are never chosen unless all do.  No host
+    synchronisation inside a decision.  `gain_backend(tri [N,G^3], poses [N,K,6]) -> gain [N,K,3]` replaces the kernel in
+    tests only: the product path has no CPU fallback."""
+
+    def __init__(self, env, k: int = 32, weights=(1, 4), seed: int = 0, stride: int = 4, avoid_collisions: bool = True,
+                 look_at_scene: bool = False, gain_backend: Optional[Callable] = None):
+        cfg = env.cfg
+        self.env, self.cfg, self.k, self.weights = env, cfg, int(k), (int(weights[0]), int(weights[1]))
+        self.num_envs = int(env.num_envs)
+        self.cands = LatticeCandidates(cfg, k, seed, look_at_scene)
+        self.avoid_collisions = bool(avoid_collisions) and getattr(env, "collision", None) is not None
+        if gain_backend is None:
+            from ..ops.view_gain import ViewGain
+            u = env.updater
+            gain_backend = ViewGain(self.num_envs, self.k, cfg, u.range_gt, u.voxel_size_gt, inv_intrinsics=u.inv_intri_host,
+                                    stride=stride, device=env.device)
+        self.gain_backend = gain_backend
+        self._contact = None
+        self.last_gain = None
+
+    def __call__(self, obs, deterministic: bool = True):
+        cfg, n, k = self.cfg, self.num_envs, self.k
+        cand = self.cands.sample(n, obs.device)
+        poses = self.cands.poses(cand)
+        tri = obs[:, cfg.state_dim:cfg.state_dim + cfg.grid_dim]
+        gain = self.gain_backend(tri, poses)
+        self.last_gain = gain
+        contact = None
+        if self.avoid_collisions:
+            if self._contact is None:
+                self._contact = torch.zeros(k, n, dtype=torch.uint8, device=obs.device)
+            for j in range(k):  # one call per candidate column ([N,6] rows, stride K * 6)
+                self.env.collision_mesh.collide(poses[:, j], self.env.collision, out=self._contact[j])
+            contact = self._contact.t()
+        best = choose(gain, self.weights, contact)
+        return cand[torch.arange(n, device=cand.device), best], None, None
+
+    @property
+    def policy(self):
+        return self
+
+    def predict(self, obs, state=None, episode_start=None, deterministic: bool = True):
+        return self(obs, deterministic)[0], state

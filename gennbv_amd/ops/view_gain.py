@@ -1,0 +1,76 @@
+"""ViewGain: how much would each env's map change if its camera went to candidate pose j?  (csrc/viewgain.hip)
+
+For the tri-class grid an env holds now (the observation's grid slice) and K candidate poses per env, the voxel update's ray
+model is run hypothetically: per candidate three int32 -- distinct unknown voxels the rays of a pixel lattice would cross
+before their first occupied voxel, the same over the rays that meet one, and the number of those rays (the exact definition:
+include/gennbv_hip.h gnbv_view_gain).  One launch for all N x K candidates; outputs are preallocated and reused: a result is
+valid until the next call.  GPU only, no CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional
+
+import torch
+
+from .. import _lib
+from ..env import synthetic as S
+from ..env.config import TaskConfig
+
+MAX_GRID = 64  # the grid (2 bits per voxel) and two visited masks live in LDS: G^3 / 2 bytes
+
+
+class ViewGain:
+    def __init__(self, num_envs: int, k: int, cfg: TaskConfig, range_gt: torch.Tensor, voxel_size: torch.Tensor,
+                 inv_intrinsics: Optional[torch.Tensor] = None, stride: int = 4, range_m: Optional[float] = None,
+                 device="cuda:0", with_c2w: bool = False, chunk: int = 0):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.GennbvHipError("ViewGain runs on the GPU only (no CPU fallback)")
+        g = int(cfg.grid_size)
+        if g > MAX_GRID:
+            raise _lib.GennbvHipError(f"ViewGain keeps the grid and its visited masks in LDS: grid_size <= {MAX_GRID}, got {g} "
+                                      "(a slab form for larger grids is not written: DESIGN.md section 7)")
+        self.lib = _lib.load()
+        self.num_envs, self.k, self.g = int(num_envs), int(k), g
+        self.h, self.w, self.stride = int(cfg.camera_height), int(cfg.camera_width), int(stride)
+        self.range_m = float(abs(cfg.depth_sense_dist) if range_m is None else range_m)
+        kinv = S.inverse_intrinsics(self.h, self.w, cfg.horizontal_fov) if inv_intrinsics is None else inv_intrinsics
+        self.inv_intri_host = kinv.detach().to("cpu", torch.float32).contiguous()
+        assert self.inv_intri_host.shape == (3, 3)
+        dev = self.device
+        self.range_gt = range_gt.to(dev, torch.float32).contiguous()
+        self.voxel_size = voxel_size.to(dev, torch.float32).contiguous()
+        assert self.range_gt.shape == (self.num_envs, 6) and self.voxel_size.shape == (self.num_envs, 3)
+        self.gain = torch.empty(self.num_envs, self.k, 3, dtype=torch.int32, device=dev)
+        self.c2w = torch.empty(self.num_envs, self.k, 4, 4, dtype=torch.float32, device=dev) if with_c2w else None
+        a = _lib.GnbvViewGain()
+        a.n, a.k, a.g = self.num_envs, self.k, g
+        a.range_gt, a.voxel_size = self.range_gt.data_ptr(), self.voxel_size.data_ptr()
+        a.inv_intri = self.inv_intri_host.data_ptr()
+        a.h, a.w, a.stride, a.range = self.h, self.w, self.stride, self.range_m
+        a.gain, a.c2w_out = self.gain.data_ptr(), _lib.ptr(self.c2w)
+        a.chunk, a.ablate = int(chunk), 0
+        self._args = a
+
+    def __call__(self, tri: torch.Tensor, poses: torch.Tensor) -> torch.Tensor:
+        """tri: int8 rows [N, G^3] (or [N,G,G,G]; unit element stride, any row stride) or the fp32 grid slice of a flat
+        observation (converted with one .to(torch.int8)); poses [N,K,6] f32 (x, y, z, roll, pitch, yaw), env-local.
+        -> gain [N,K,3] int32 (unknown, unknown_hit, blocked)."""
+        _lib.require_cuda(tri, poses)
+        n, k, g3 = self.num_envs, self.k, self.g ** 3
+        if tri.dtype != torch.int8:
+            tri = tri.to(torch.int8)
+        if tri.shape[0] != n or tri.numel() != n * g3:
+            raise _lib.GennbvHipError(f"ViewGain: tri must hold [{n}, {g3}] voxels, got {tuple(tri.shape)}")
+        if tri.dim() != 2:
+            tri = tri.reshape(n, g3)
+        if tri.stride(1) != 1:
+            tri = tri.contiguous()
+        if poses.dtype != torch.float32 or poses.shape != (n, k, 6):
+            raise _lib.GennbvHipError(f"ViewGain: poses must be f32 [{n}, {k}, 6], got {poses.dtype} {tuple(poses.shape)}")
+        poses = poses.contiguous()
+        a = self._args
+        a.tri_i8, a.tri_row_stride, a.poses = tri.data_ptr(), max(int(tri.stride(0)), g3), poses.data_ptr()
+        _lib.check(self.lib.gnbv_view_gain(C.byref(a), _lib.stream_ptr(self.device)), "gnbv_view_gain")
+        return self.gain

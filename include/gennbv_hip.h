@@ -690,6 +690,42 @@ int gnbv_scan_score(const GnbvScanSet *set /*[host]*/, const GnbvScanGt *gt /*[h
  * points added since its last clear): xyz [counts[env], 3].  The set is not modified. */
 int gnbv_scan_export(const GnbvScanSet *set /*[host]*/, int env, float *xyz, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------------- */
+/* View gain (a new entry point of ABI 5): how much would env e's map change    */
+/* if its camera went to candidate pose j?  The voxel update's ray model run     */
+/* hypothetically against the tri-class grid, K candidates per env.              */
+/* ------------------------------------------------------------------------- */
+/* Env e holds tri [g,g,g] int8 (C order x, y, z; < 0 free, 0 unknown, > 0 occupied).  Candidate pose (x, y, z, roll, pitch,
+ * yaw), env-local:
+ *   - c2w = gnbv_render_depth's camera matrix of the pose (fp64 trig rounded to fp32, roll ignored);
+ *   - rays: the pixels u = stride/2 + i stride < w, v = stride/2 + j stride < h (integer division);
+ *   - the ray of (u, v) ends at the world point gnbv_back_projection gives that pixel at depth `range` (the canonical fp32
+ *     chain); source voxel = gnbv_pose_to_idx(x, y, z), target voxel = gnbv_pose_to_idx(end point), both unclamped (voxel
+ *     coordinates beyond +-2^24 saturate there);
+ *   - the ray visits the in-grid voxels of gnbv_bresenham3d's line from source to target in order and stops in front of the
+ *     first occupied one (not counted); a ray that met one is `blocked`.
+ * gain[e, j] = { distinct unknown voxels visited by any ray, the same over the blocked rays only, blocked rays }.  Integers
+ * with one right answer; every element is written; deterministic (no global atomics).  One launch, no workspace.
+ * g outside 2..64 (the grid and two visited masks live in LDS), stride < 1, range not positive and finite, or k < 1 return
+ * hipErrorInvalidValue.  [host struct]; pointers are device unless noted. */
+typedef struct GnbvViewGain {
+    int n, k, g;                    /* envs, candidates per env, grid edge */
+    const int8_t *tri_i8;           /* [n, g^3] with a row stride in BYTES (rows inside a larger buffer work) */
+    int64_t tri_row_stride;
+    const float *poses;             /* [n, k, 6] contiguous */
+    const float *range_gt;          /* [n, 6] */
+    const float *voxel_size;        /* [n, 3] */
+    const float *inv_intri;         /* [host] [3,3] the updater's inverse intrinsics */
+    int h, w, stride;               /* camera and the pixel lattice's step */
+    float range;                    /* metres */
+    int32_t *gain;                  /* [n, k, 3] */
+    float *c2w_out;                 /* [n, k, 4, 4] the matrices used, or NULL */
+    int chunk;                      /* candidates per workgroup, 0 = chosen from n and k (any value gives the same result) */
+    int ablate;                     /* measurements only, 0 otherwise: bit 0 walk without marking (the counts are then 0),
+                                     * bit 1 no second mask (unknown_hit is then 0) */
+} GnbvViewGain;
+int gnbv_view_gain(const GnbvViewGain *args /*[host]*/, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
