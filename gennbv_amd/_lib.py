@@ -55,6 +55,7 @@ SIGNATURES = {
     "gnbv_render_depth": (_i, [_p, _p, _i64, _p, _i, _i, _p, _p, _p, _p, _p]),
     "gnbv_voxelize_surface": (_i, [_p, _p, _p, _i, _p, _p]),
     "gnbv_collide_cylinder": (_i, [_p, _p, _p, _i64, _f, _f, _i, _p, _p]),
+    "gnbv_collide_cylinder_batch": (_i, [_p, _p, _p, _i, _i64, _f, _f, _i, _p, _p]),
     "gnbv_rollout_add": (_i, [_i, _i, _p, _p, _p, _p, _i, _f, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "gnbv_input_autocorr_row_ints": (_i, []),
     "gnbv_input_autocorr": (_i, [_p, _i64, _i, _i, _p, _i64, _p]),
@@ -98,6 +99,8 @@ SIGNATURES = {
     "gnbv_scan_score": (_i, [_p, _p, _p, _p, _p, _p, _sz, _p]),
     "gnbv_scan_export": (_i, [_p, _i, _p, _p, _sz, _p]),
     "gnbv_view_gain": (_i, [_p, _p]),
+    "gnbv_view_gain_slab_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "gnbv_view_gain_slab": (_i, [_p, _i, _p, _sz, _p]),
     "gnbv_gae_sb3": (_i, [_p, _p, _p, _p, _p, _i, _i, _d, _d, _p, _p, _p]),
     "gnbv_gae_rsl": (_i, [_p, _p, _p, _p, _i, _i, _d, _d, _p, _p, _p]),
 }

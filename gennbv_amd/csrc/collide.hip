@@ -141,15 +141,11 @@ __device__ __forceinline__ double wave_sum_xor(double v)
     return v;
 }
 
-__global__ __launch_bounds__(kWave * kWavesPerBlock) void k_collide_cylinder(GnbvMeshScene sc, GnbvMeshObjects ob,
-                                                                              const float *__restrict__ poses, int64_t poses_row_stride,
-                                                                              float radius, float half_length, int ground,
-                                                                              uint8_t *__restrict__ contact_out)
+// the contact code of env e's scene at pose p (one wave; the same value in every lane)
+__device__ __forceinline__ uint8_t collide_code(const GnbvMeshScene &sc, const GnbvMeshObjects &ob, int e, const float *__restrict__ p,
+                                                float radius, float half_length, int ground)
 {
-    const int e = blockIdx.x * kWavesPerBlock + (int)(threadIdx.x / kWave);
-    if (e >= sc.n) return;  // whole wave
     const int lane = threadIdx.x & (kWave - 1);
-    const float *p = poses + (size_t)e * poses_row_stride;
     const V3 c = v3((double)p[0], (double)p[1], (double)p[2]);
     const double roll = (double)p[3], pitch = (double)p[4], yaw = (double)p[5];
     const double cr = cos(roll), sr = sin(roll), cp = cos(pitch), sp = sin(pitch), cy = cos(yaw), sy = sin(yaw);
@@ -250,25 +246,71 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void k_collide_cylinder(Gnb
 
     // ---- (G): closed form
     const bool g_hit = finite && ground != 0 && c.z - ez <= 0.0;
-    if (lane == 0) contact_out[e] = (uint8_t)((s_hit ? 1 : 0) | (inside ? 2 : 0) | (g_hit ? 4 : 0));
+    return (uint8_t)((s_hit ? 1 : 0) | (inside ? 2 : 0) | (g_hit ? 4 : 0));
+}
+
+__global__ __launch_bounds__(kWave * kWavesPerBlock) void k_collide_cylinder(GnbvMeshScene sc, GnbvMeshObjects ob,
+                                                                              const float *__restrict__ poses, int64_t poses_row_stride,
+                                                                              float radius, float half_length, int ground,
+                                                                              uint8_t *__restrict__ contact_out)
+{
+    const int e = blockIdx.x * kWavesPerBlock + (int)(threadIdx.x / kWave);
+    if (e >= sc.n) return;  // whole wave
+    const uint8_t code = collide_code(sc, ob, e, poses + (size_t)e * poses_row_stride, radius, half_length, ground);
+    if ((threadIdx.x & (kWave - 1)) == 0) contact_out[e] = code;
+}
+
+// one wave per (env, candidate): item = e k + j, row item of poses
+__global__ __launch_bounds__(kWave * kWavesPerBlock) void k_collide_cylinder_batch(GnbvMeshScene sc, GnbvMeshObjects ob,
+                                                                                    const float *__restrict__ poses, int k,
+                                                                                    int64_t poses_row_stride, float radius,
+                                                                                    float half_length, int ground,
+                                                                                    uint8_t *__restrict__ contact_out)
+{
+    const int item = blockIdx.x * kWavesPerBlock + (int)(threadIdx.x / kWave);
+    if (item >= sc.n * k) return;  // whole wave
+    const uint8_t code = collide_code(sc, ob, item / k, poses + (size_t)item * poses_row_stride, radius, half_length, ground);
+    if ((threadIdx.x & (kWave - 1)) == 0) contact_out[item] = code;
 }
 
 }  // namespace
 
+static bool collide_args_ok(const GnbvMeshScene *scene, const GnbvMeshObjects *objects, const float *poses, int64_t poses_row_stride,
+                            float radius, float half_length, const uint8_t *contact_out)
+{
+    if (scene == nullptr || objects == nullptr || poses == nullptr || contact_out == nullptr) return false;
+    const GnbvMeshScene &sc = *scene;
+    const GnbvMeshObjects &ob = *objects;
+    return sc.n > 0 && ob.n == sc.n && ob.num_objects >= 0 && poses_row_stride >= 6 && std::isfinite(radius) && radius > 0.0f &&
+           std::isfinite(half_length) && half_length >= 0.0f && sc.cell_lo != nullptr && sc.cell_size != nullptr &&
+           sc.cell_res != nullptr && sc.cell_base != nullptr && sc.cell_start != nullptr && ob.env_obj_start != nullptr &&
+           ob.obj_tri_start != nullptr &&
+           // tris / cell_tris / obj_aabb / obj_tris may be NULL when no env has a triangle
+           (ob.num_objects == 0 || (ob.obj_aabb != nullptr && ob.obj_tris != nullptr && sc.tris != nullptr));
+}
+
 GNBV_API int gnbv_collide_cylinder(const GnbvMeshScene *scene, const GnbvMeshObjects *objects, const float *poses, int64_t poses_row_stride,
                                    float radius, float half_length, int ground, uint8_t *contact_out, void *stream)
 {
-    GNBV_CHECK_ARG(scene != nullptr && objects != nullptr && poses != nullptr && contact_out != nullptr);
+    GNBV_CHECK_ARG(collide_args_ok(scene, objects, poses, poses_row_stride, radius, half_length, contact_out));
     const GnbvMeshScene sc = *scene;
     const GnbvMeshObjects ob = *objects;
-    GNBV_CHECK_ARG(sc.n > 0 && ob.n == sc.n && ob.num_objects >= 0 && poses_row_stride >= 6);
-    GNBV_CHECK_ARG(std::isfinite(radius) && radius > 0.0f && std::isfinite(half_length) && half_length >= 0.0f);
-    GNBV_CHECK_ARG(sc.cell_lo != nullptr && sc.cell_size != nullptr && sc.cell_res != nullptr && sc.cell_base != nullptr);
-    GNBV_CHECK_ARG(sc.cell_start != nullptr && ob.env_obj_start != nullptr && ob.obj_tri_start != nullptr);
-    // tris / cell_tris / obj_aabb / obj_tris may be NULL when no env has a triangle
-    GNBV_CHECK_ARG(ob.num_objects == 0 || (ob.obj_aabb != nullptr && ob.obj_tris != nullptr && sc.tris != nullptr));
     const int blocks = (sc.n + kWavesPerBlock - 1) / kWavesPerBlock;
     hipLaunchKernelGGL(k_collide_cylinder, dim3(blocks), dim3(kWave * kWavesPerBlock), 0, gnbv_stream(stream), sc, ob, poses,
+                       poses_row_stride, radius, half_length, ground, contact_out);
+    return gnbv_launch_status();
+}
+
+GNBV_API int gnbv_collide_cylinder_batch(const GnbvMeshScene *scene, const GnbvMeshObjects *objects, const float *poses, int k,
+                                         int64_t poses_row_stride, float radius, float half_length, int ground, uint8_t *contact_out,
+                                         void *stream)
+{
+    GNBV_CHECK_ARG(collide_args_ok(scene, objects, poses, poses_row_stride, radius, half_length, contact_out));
+    const GnbvMeshScene sc = *scene;
+    const GnbvMeshObjects ob = *objects;
+    GNBV_CHECK_ARG(k >= 1 && (int64_t)sc.n * k <= 0x7fffffff);
+    const int blocks = (int)(((int64_t)sc.n * k + kWavesPerBlock - 1) / kWavesPerBlock);
+    hipLaunchKernelGGL(k_collide_cylinder_batch, dim3(blocks), dim3(kWave * kWavesPerBlock), 0, gnbv_stream(stream), sc, ob, poses, k,
                        poses_row_stride, radius, half_length, ground, contact_out);
     return gnbv_launch_status();
 }

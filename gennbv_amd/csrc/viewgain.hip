@@ -21,6 +21,8 @@
 //     4. wave reductions -> per-wave partials in LDS -> lane 0 sums them in wave order and stores the three integers.  No
 //        global atomics, every output is written once by one lane: deterministic;
 //     5. the workgroup clears both masks (16-byte stores) before the next candidate.
+//
+//   k_vg_prep, k_vg_fate, k_vg_slab   the same integers for grids up to 128^3 (gnbv_view_gain_slab): further down.
 #include <cmath>
 
 #include "common.h"
@@ -31,6 +33,7 @@ namespace {
 
 constexpr int kMaxThreads = 1024;
 constexpr int kMaxGrid = 64;          // LDS: G^3 / 4 (grid) + 2 * G^3 / 8 (masks) bytes = 128 KiB at 64^3
+constexpr int kMaxSlabGrid = 128;     // gnbv_view_gain_slab (the ray word keeps x in 8 bits, the step count in 8)
 constexpr int kCamBatch = 16;         // camera matrices built at a time
 constexpr float kCoordClamp = 16777216.0f;  // voxel coordinates saturate at +-2^24: the 64-bit closed form stays exact
 
@@ -67,24 +70,34 @@ __device__ __forceinline__ long long floor_div(long long num, long long den)
     return q;
 }
 
-// steps [lo, hi] of a minor axis (start p0, direction s, extent d; the dominant extent is da > 0) whose coordinate
-// p0 + s nb(i) may lie in [0, g): one step wider than the exact range on both sides
-__device__ __forceinline__ void minor_range(int p0, int s, int d, int da, int g, long long &lo, long long &hi)
+// the same in 32 bits, den > 0 (make_slab_walk's near rays)
+__device__ __forceinline__ int floor_div(int num, int den)
 {
-    const long long mlo = s > 0 ? -(long long)p0 : (long long)p0 - (g - 1);  // nb(i) must reach mlo ...
-    const long long mhi = s > 0 ? (long long)(g - 1) - p0 : (long long)p0;    // ... and not pass mhi
+    const int q = num / den;
+    return q - (num - q * den < 0 ? 1 : 0);
+}
+
+// steps [lo, hi] of a minor axis (start p0, direction s, extent d; the dominant extent is da > 0) whose coordinate
+// p0 + s nb(i) may lie in [b0, b1]: one step wider than the exact range on both sides.  T: long long, or int where the
+// products fit (make_slab_walk)
+template <typename T>
+__device__ __forceinline__ void minor_range(int p0, int s, int d, int da, int b0, int b1, T &lo, T &hi)
+{
+    const T mlo = s > 0 ? (T)b0 - p0 : (T)p0 - b1;  // nb(i) must reach mlo ...
+    const T mhi = s > 0 ? (T)b1 - p0 : (T)p0 - b0;  // ... and not pass mhi
     if (mhi < 0 || (mlo > 0 && d == 0)) {
         hi = -1;
         return;
     }
     if (d == 0) return;
     // first i with nb(i) >= m (m >= 1): ceil((2 da m - da) / (2 d))
-    if (mlo > 0) lo = max(lo, floor_div(2LL * da * mlo - da + 2LL * d - 1, 2LL * d) - 1);
-    hi = min(hi, floor_div(2LL * da * (mhi + 1) - da + 2LL * d - 1, 2LL * d));
+    if (mlo > 0) lo = max(lo, floor_div((T)2 * da * mlo - da + (T)2 * d - 1, (T)2 * d) - 1);
+    hi = min(hi, floor_div((T)2 * da * (mhi + 1) - da + (T)2 * d - 1, (T)2 * d));
 }
 
 struct RayWalk {  // the walk of one ray restricted to the steps [ilo, ihi]
     int n;        // steps to take (0: the ray never meets the grid)
+    int i0;       // the first of them, counted from the source
     int pb, pc, p1, p2, lin;
     int sb, sc, two_da, two_db, two_dc, la, lb, lc;  // la, lb, lc: signed linear-index strides of the three axes
 };
@@ -108,8 +121,8 @@ __device__ __forceinline__ RayWalk make_walk(int x0, int y0, int z0, int x1, int
     lo = max(lo, 0LL);
     hi = min(hi, (long long)da);
     if (da > 0) {
-        minor_range(pb, sb, db, da, g, lo, hi);
-        if (hi >= lo) minor_range(pc, sc, dc, da, g, lo, hi);
+        minor_range(pb, sb, db, da, 0, g - 1, lo, hi);
+        if (hi >= lo) minor_range(pc, sc, dc, da, 0, g - 1, lo, hi);
     }
     if (hi < lo) return r;
     long long nb = 0, nc = 0;
@@ -118,6 +131,7 @@ __device__ __forceinline__ RayWalk make_walk(int x0, int y0, int z0, int x1, int
         nc = floor_div(2LL * dc * lo + da, 2LL * da);
     }
     r.n = (int)(hi - lo + 1);  // <= g + 2
+    r.i0 = (int)lo;
     pa += sa * (int)lo;
     r.pb = pb + sb * (int)nb;
     r.pc = pc + sc * (int)nc;
@@ -131,14 +145,15 @@ __device__ __forceinline__ RayWalk make_walk(int x0, int y0, int z0, int x1, int
     return r;
 }
 
-// visit(lin) for every in-grid voxel of the walk, in order; visit returns true to stop.  Returns whether it stopped.
+// visit(lin, i) for every in-grid voxel of the walk, in order (i: the step, counted from r.i0); visit returns true to stop.
+// Returns whether it stopped.
 template <typename Visit>
 __device__ __forceinline__ bool run_walk(RayWalk r, int g, Visit &&visit)
 {
     const unsigned ug = (unsigned)g;
     for (int i = 0; i < r.n; ++i) {
         if ((unsigned)r.pb < ug && (unsigned)r.pc < ug) {
-            if (visit(r.lin)) return true;
+            if (visit(r.lin, i)) return true;
         }
         if (r.p1 >= 0) { r.pb += r.sb; r.lin += r.lb; r.p1 -= r.two_da; }
         if (r.p2 >= 0) { r.pc += r.sc; r.lin += r.lc; r.p2 -= r.two_da; }
@@ -160,6 +175,37 @@ __device__ __forceinline__ uint32_t pack_codes4(uint32_t bytes4)
     return code;
 }
 
+// the camera matrix of pose q (k_render_camera's arithmetic: fp64 trig rounded to fp32, roll ignored; -ffp-contract=off)
+__device__ __forceinline__ void camera_of_pose(const float *q, float *m)
+{
+    const double pitch = (double)q[4], yaw = (double)q[5];
+    const double cp = cos(pitch), sp = sin(pitch), cy = cos(yaw), sy = sin(yaw);
+    const double fx = cp * cy, fy = cp * sy, fz = -sp;
+    const double rx = sy, ry = -cy, rz = 0.0;
+    const double dx = fy * rz - fz * ry, dy = fz * rx - fx * rz, dz = fx * ry - fy * rx;
+    m[0] = (float)rx; m[1] = (float)dx; m[2] = (float)fx; m[3] = q[0];
+    m[4] = (float)ry; m[5] = (float)dy; m[6] = (float)fy; m[7] = q[1];
+    m[8] = (float)rz; m[9] = (float)dz; m[10] = (float)fz; m[11] = q[2];
+    m[12] = 0.f; m[13] = 0.f; m[14] = 0.f; m[15] = 1.f;
+}
+
+// word w of a row's 2-bit codes: voxels 16 w .. 16 w + 15 (0 past the row's end)
+__device__ __forceinline__ uint32_t pack_word(const int8_t *row, int w, int g3, int aligned)
+{
+    const int base = w * 16;
+    uint32_t code = 0;
+    if (aligned && base + 16 <= g3) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(row + base);
+        code = pack_codes4(v.x) | (pack_codes4(v.y) << 8) | (pack_codes4(v.z) << 16) | (pack_codes4(v.w) << 24);
+    } else {
+        for (int b = 0; b < 16 && base + b < g3; ++b) {
+            const int t = (int)row[base + b];
+            code |= (t > 0 ? 1u : (t < 0 ? 3u : 0u)) << (2 * b);
+        }
+    }
+    return code;
+}
+
 __global__ __launch_bounds__(kMaxThreads) void k_view_gain(VgParams p)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t s_mem[];
@@ -175,20 +221,7 @@ __global__ __launch_bounds__(kMaxThreads) void k_view_gain(VgParams p)
 
     // ---- 1. the env's grid, 2 bits per voxel
     const int8_t *row = p.tri + (size_t)e * p.tri_row_stride;
-    for (int w = tid; w < p.grid_words; w += nthreads) {
-        const int base = w * 16;
-        uint32_t code = 0;
-        if (p.tri_aligned && base + 16 <= g3) {
-            const uint4 v = *reinterpret_cast<const uint4 *>(row + base);
-            code = pack_codes4(v.x) | (pack_codes4(v.y) << 8) | (pack_codes4(v.z) << 16) | (pack_codes4(v.w) << 24);
-        } else {
-            for (int b = 0; b < 16 && base + b < g3; ++b) {
-                const int t = (int)row[base + b];
-                code |= (t > 0 ? 1u : (t < 0 ? 3u : 0u)) << (2 * b);
-            }
-        }
-        s_grid[w] = code;
-    }
+    for (int w = tid; w < p.grid_words; w += nthreads) s_grid[w] = pack_word(row, w, g3, p.tri_aligned);
     uint4 *s_masks4 = reinterpret_cast<uint4 *>(s_a);
     const int mask_quads = p.mask_words / 2;  // both masks, 4 words at a time (mask_words is a multiple of 4)
     for (int w = tid; w < mask_quads; w += nthreads) s_masks4[w] = make_uint4(0u, 0u, 0u, 0u);
@@ -203,16 +236,8 @@ __global__ __launch_bounds__(kMaxThreads) void k_view_gain(VgParams p)
             // ---- 2a. cameras of the next kCamBatch candidates (k_render_camera's arithmetic; -ffp-contract=off)
             if (tid < kCamBatch && j + tid < j1) {
                 const float *q = p.poses + ((size_t)e * p.k + j + tid) * 6;
-                const double pitch = (double)q[4], yaw = (double)q[5];
-                const double cp = cos(pitch), sp = sin(pitch), cy = cos(yaw), sy = sin(yaw);
-                const double fx = cp * cy, fy = cp * sy, fz = -sp;
-                const double rx = sy, ry = -cy, rz = 0.0;
-                const double dx = fy * rz - fz * ry, dy = fz * rx - fx * rz, dz = fx * ry - fy * rx;
                 float *m = s_cam[tid];
-                m[0] = (float)rx; m[1] = (float)dx; m[2] = (float)fx; m[3] = q[0];
-                m[4] = (float)ry; m[5] = (float)dy; m[6] = (float)fy; m[7] = q[1];
-                m[8] = (float)rz; m[9] = (float)dz; m[10] = (float)fz; m[11] = q[2];
-                m[12] = 0.f; m[13] = 0.f; m[14] = 0.f; m[15] = 1.f;
+                camera_of_pose(q, m);
                 if (p.c2w_out != nullptr) {
                     float *o = p.c2w_out + ((size_t)e * p.k + j + tid) * 16;
 #pragma unroll
@@ -237,7 +262,7 @@ __global__ __launch_bounds__(kMaxThreads) void k_view_gain(VgParams p)
             const int x1 = axis_to_idx(wp[0], rmin_x, vx), y1 = axis_to_idx(wp[1], rmin_y, vy), z1 = axis_to_idx(wp[2], rmin_z, vz);
             const RayWalk rw = make_walk(x0, y0, z0, x1, y1, z1, g);
             if (rw.n == 0) continue;
-            const bool blocked = run_walk(rw, g, [&](int lin) {
+            const bool blocked = run_walk(rw, g, [&](int lin, int) {
                 const uint32_t cls = (s_grid[lin >> 4] >> ((lin & 15) * 2)) & 3u;
                 if (cls == 1u) return true;
                 if (cls == 0u && mark) {
@@ -249,7 +274,7 @@ __global__ __launch_bounds__(kMaxThreads) void k_view_gain(VgParams p)
             if (blocked) {
                 ++n_blocked;
                 if (mark && second)
-                    run_walk(rw, g, [&](int lin) {
+                    run_walk(rw, g, [&](int lin, int) {
                         const uint32_t cls = (s_grid[lin >> 4] >> ((lin & 15) * 2)) & 3u;
                         if (cls == 1u) return true;
                         if (cls == 0u) {
@@ -288,19 +313,321 @@ __global__ __launch_bounds__(kMaxThreads) void k_view_gain(VgParams p)
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// Grids above 64^3 (gnbv_view_gain_slab): the grid and its masks no longer fit in LDS, so a candidate's voxels are split into
+// slabs of x-planes and a ray is known by its FATE before any slab sees it.  Per batch of envs (the workspace holds one batch):
+//
+//   k_vg_prep   the batch's grids packed to 2 bits per voxel in global memory (512 KiB per env at 128^3: an env's workgroups
+//               run on one XCD, whose L2 keeps it), the camera matrix and source voxel of every candidate, gain zeroed;
+//   k_vg_fate   one ray per lane, workgroup (env, candidate, 256 rays): the ray's end voxel, then k_view_gain's walk against
+//               the packed grid, read-only.  Per ray a 16-byte record {end voxel, first in-grid step} and a 4-byte word
+//               {steps to mark, blocked, the x-extent of those steps}: the steps run from the first in-grid voxel to the one
+//               in front of the first occupied voxel (the in-grid steps of a line are contiguous: the grid is convex).
+//               `blocked` is complete after this pass (one atomicAdd per workgroup);
+//   k_vg_slab   workgroup (env, chunk of candidates, slab [X0, X1)): the slab's part of the packed grid and of both visited
+//               masks in LDS ((X1 - X0) G^2 / 2 bytes).  A ray whose marked x-extent misses the slab is rejected on its
+//               4-byte word alone.  Otherwise its steps are cut to the slab: exactly if x is the dominant axis, by the
+//               closed form of the minors (minor_range with [X0, X1 - 1]) if not, one step wide on both sides and guarded by
+//               a test of the slab-local index in the loop (y and z need none: every recorded step is in the grid).  The ray
+//               walks once: mask A, and mask B too if it is blocked.  Distinct counts as in k_view_gain; the slabs
+//               partition the voxels by x, so a candidate's counts are the sums over its slabs: int32 atomicAdd, one per
+//               workgroup, candidate and count -- integer sums, the same bits in any order.
+//
+// tests/test_view_gain_slab_cpu.py holds a Python model of the record and of the slab cut, checked against the oracle's
+// Bresenham.
+constexpr int kFateThreads = 256;
+constexpr int kCamWords = 20;                      // per candidate in the workspace: c2w [16] f32, source voxel [3] i32, pad
+constexpr size_t kSlabLdsBudget = 128 * 1024;      // default slab height: grid + masks within this
+constexpr size_t kSlabLdsMax = 160 * 1024 - 256;   // a requested height is reduced to fit (static LDS: 128 B)
+constexpr size_t kBatchBytes = (size_t)128 << 20;  // ray records of one batch of envs
+constexpr int kSlabWorkgroups = 2560;              // k_vg_slab workgroups per batch the default chunk aims at
+
+struct VsParams {
+    int k, g, chunk, chunks, slab, nslab;
+    const int8_t *tri;
+    int64_t tri_row_stride;
+    int tri_aligned;
+    const float *poses, *range_gt, *voxel_size;
+    Intrinsics kinv;
+    int stride, nu, nrays, rblocks;
+    float range;
+    int32_t *gain;
+    float *c2w_out;
+    int pack_words, grid_words, mask_words, ablate;
+    uint32_t *packed;  // [batch, pack_words]
+    float *cams;       // [batch, k, kCamWords]
+    int4 *rec;         // [batch, k, nrays]
+    uint32_t *meta;    // [batch, k, nrays]
+};
+
+__global__ __launch_bounds__(256) void k_vg_prep(VsParams p, int e0, int ne)
+{
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int g3 = p.g * p.g * p.g;
+    if (t < (int64_t)ne * p.pack_words) {
+        const int el = (int)(t / p.pack_words), w = (int)(t - (int64_t)el * p.pack_words);
+        p.packed[t] = pack_word(p.tri + (size_t)(e0 + el) * p.tri_row_stride, w, g3, p.tri_aligned);
+    }
+    if (t < (int64_t)ne * p.k * 3) p.gain[(size_t)e0 * p.k * 3 + t] = 0;
+    if (t < (int64_t)ne * p.k) {
+        const int el = (int)(t / p.k), e = e0 + el;
+        const size_t c = (size_t)e0 * p.k + t;  // (e, j) over all envs
+        const float *q = p.poses + c * 6;
+        float m[16];
+        camera_of_pose(q, m);
+        float *o = p.cams + (size_t)t * kCamWords;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) o[i] = m[i];
+        if (p.c2w_out != nullptr) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) p.c2w_out[c * 16 + i] = m[i];
+        }
+        int *src = reinterpret_cast<int *>(o + 16);
+        src[0] = axis_to_idx(q[0], p.range_gt[e * 6 + 1], p.voxel_size[e * 3 + 0]);
+        src[1] = axis_to_idx(q[1], p.range_gt[e * 6 + 3], p.voxel_size[e * 3 + 1]);
+        src[2] = axis_to_idx(q[2], p.range_gt[e * 6 + 5], p.voxel_size[e * 3 + 2]);
+        src[3] = 0;
+    }
+}
+
+__global__ __launch_bounds__(kFateThreads) void k_vg_fate(VsParams p, int e0, int ne)
+{
+    __shared__ int s_blocked[kFateThreads / kWave];
+    // XCD-aware block -> (env, candidate, ray block): all workgroups of an env run on one XCD (voxel.hip k_hit_mask)
+    const int b = blockIdx.x, xcd = b & 7, slot = b >> 3;
+    const int per_env = p.k * p.rblocks;
+    const int el = (slot / per_env) * 8 + xcd;
+    if (el >= ne) return;
+    const int rem = slot % per_env, j = rem / p.rblocks, rb = rem - j * p.rblocks;
+    const int e = e0 + el, tid = threadIdx.x, g = p.g;
+    const size_t cj = (size_t)el * p.k + j;
+    const float *M = p.cams + cj * kCamWords;
+    const int *src = reinterpret_cast<const int *>(M + 16);
+    const int x0 = src[0], y0 = src[1], z0 = src[2];
+    const uint32_t *G = p.packed + (size_t)el * p.pack_words;
+    const int r = rb * kFateThreads + tid;
+    int n_blocked = 0;
+    if (r < p.nrays) {
+        const float rmin_x = p.range_gt[e * 6 + 1], rmin_y = p.range_gt[e * 6 + 3], rmin_z = p.range_gt[e * 6 + 5];
+        const float vx = p.voxel_size[e * 3 + 0], vy = p.voxel_size[e * 3 + 1], vz = p.voxel_size[e * 3 + 2];
+        const int iv = r / p.nu, iu = r - iv * p.nu;
+        const int u = p.stride / 2 + iu * p.stride, v = p.stride / 2 + iv * p.stride;
+        float wp[3];
+        pixel_to_world(p.range, (float)u, (float)v, p.kinv, M, wp);
+        const int x1 = axis_to_idx(wp[0], rmin_x, vx), y1 = axis_to_idx(wp[1], rmin_y, vy), z1 = axis_to_idx(wp[2], rmin_z, vz);
+        const RayWalk rw = make_walk(x0, y0, z0, x1, y1, z1, g);
+        int first = 0, last = -1, lin_first = 0, lin_last = 0;
+        bool blocked = false;
+        if (rw.n > 0)
+            blocked = run_walk(rw, g, [&](int lin, int i) {
+                if (((G[lin >> 4] >> ((lin & 15) * 2)) & 3u) == 1u) return true;
+                if (last < 0) { first = i; lin_first = lin; }
+                last = i; lin_last = lin;
+                return false;
+            });
+        n_blocked = blocked ? 1 : 0;
+        const int count = last < 0 ? 0 : last - first + 1;  // <= g
+        const int gg = g * g, xf = lin_first / gg, xl = lin_last / gg;
+        p.rec[cj * p.nrays + r] = make_int4(x1, y1, z1, rw.n > 0 ? rw.i0 + first : 0);
+        p.meta[cj * p.nrays + r] = (uint32_t)count | (blocked ? 256u : 0u) | ((uint32_t)min(xf, xl) << 16) | ((uint32_t)max(xf, xl) << 24);
+    }
+    n_blocked = wave_reduce_sum(n_blocked);
+    if ((tid & (kWave - 1)) == 0) s_blocked[tid / kWave] = n_blocked;
+    __syncthreads();
+    if (tid == 0) {
+        int c = 0;
+        for (int w = 0; w < kFateThreads / kWave; ++w) c += s_blocked[w];
+        if (c != 0) atomicAdd(p.gain + ((size_t)e * p.k + j) * 3 + 2, c);
+    }
+}
+
+struct SlabWalk {  // the steps of one ray inside one slab
+    int n, lin;    // lin: index inside the slab, (x - X0) g^2 + y g + z
+    int p1, p2, two_da, two_db, two_dc, la, lb, lc;
+};
+
+// The recorded steps [first, first + count) of the ray (x0, y0, z0) -> (x1, y1, z1), cut to x in [X0, X1).  Axis order,
+// decision variables and the jump to the first step are make_walk's.  T = int for rays of fewer than 2^14 steps: a recorded
+// ray meets the grid, so |x0| <= da + g, the steps are <= da, and every product below stays under 2^30.
+template <typename T>
+__device__ __forceinline__ SlabWalk make_slab_walk(int x0, int y0, int z0, int x1, int y1, int z1, int g, int first, int count,
+                                                   int X0, int X1)
+{
+    SlabWalk r;
+    r.n = 0;
+    const int dx = abs(x1 - x0), dy = abs(y1 - y0), dz = abs(z1 - z0);
+    const int sx = x0 < x1 ? 1 : -1, sy = y0 < y1 ? 1 : -1, sz = z0 < z1 ? 1 : -1;
+    const int dm = max(max(dx, dy), dz);
+    int pa, pb, pc, da, db, dc, sa, sb, sc, sta, stb, stc;
+    const int gg = g * g;
+    if (dm == dx)      { pa = x0; pb = y0; pc = z0; da = dx; db = dy; dc = dz; sa = sx; sb = sy; sc = sz; sta = gg; stb = g; stc = 1; }
+    else if (dm == dy) { pa = y0; pb = x0; pc = z0; da = dy; db = dx; dc = dz; sa = sy; sb = sx; sc = sz; sta = g; stb = gg; stc = 1; }
+    else               { pa = z0; pb = x0; pc = y0; da = dz; db = dx; dc = dy; sa = sz; sb = sx; sc = sy; sta = 1; stb = gg; stc = g; }
+    T lo = first, hi = (T)first + count - 1;
+    if (dm == dx) {  // x dominant: x0 + sx i in [X0, X1 - 1], exact
+        lo = max(lo, sa > 0 ? (T)X0 - pa : (T)pa - (X1 - 1));
+        hi = min(hi, sa > 0 ? (T)(X1 - 1) - pa : (T)pa - X0);
+    } else {         // x is the first minor (da > 0 here)
+        minor_range<T>(pb, sb, db, da, X0, X1 - 1, lo, hi);
+    }
+    if (hi < lo) return r;
+    T nb = 0, nc = 0;
+    if (da > 0 && lo > 0) {
+        nb = floor_div((T)2 * db * lo + da, (T)2 * da);
+        nc = floor_div((T)2 * dc * lo + da, (T)2 * da);
+    }
+    r.n = (int)(hi - lo + 1);
+    pa += sa * (int)lo;
+    pb += sb * (int)nb;
+    pc += sc * (int)nc;
+    r.p1 = (int)((T)2 * db * (lo + 1) - da - (T)2 * da * nb);
+    r.p2 = (int)((T)2 * dc * (lo + 1) - da - (T)2 * da * nc);
+    r.lin = pa * sta + pb * stb + pc * stc - X0 * gg;
+    r.two_da = 2 * da; r.two_db = 2 * db; r.two_dc = 2 * dc;
+    r.la = sa * sta; r.lb = sb * stb; r.lc = sc * stc;
+    return r;
+}
+
+__global__ __launch_bounds__(kMaxThreads) void k_vg_slab(VsParams p, int e0, int ne)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_mem[];
+    __shared__ int s_part[kMaxThreads / kWave][2];
+
+    const int tid = threadIdx.x, nthreads = blockDim.x;
+    // XCD-aware block -> (env, chunk, slab): all workgroups of an env run on one XCD, as in k_vg_fate
+    const int b = blockIdx.x, xcd = b & 7, slot = b >> 3;
+    const int per_env = p.chunks * p.nslab;
+    const int el = (slot / per_env) * 8 + xcd;
+    if (el >= ne) return;
+    const int rem = slot % per_env, ch = rem / p.nslab, sl = rem - ch * p.nslab;
+    const int e = e0 + el, g = p.g, gg = g * g;
+    const int j0 = ch * p.chunk, j1 = min(p.k, j0 + p.chunk);
+    const int X0 = sl * p.slab, X1 = min(g, X0 + p.slab);
+    const unsigned svox = (unsigned)((X1 - X0) * gg);
+    uint32_t *s_grid = s_mem, *s_a = s_mem + p.grid_words, *s_b = s_a + p.mask_words;
+
+    // ---- the slab's voxels, 2 bits each, from voxel X0 g^2 of the packed grid (not a word boundary in general; the packed
+    //      row ends with a spare word, and the bits past the slab's last voxel are never looked at)
+    const uint32_t *G = p.packed + (size_t)el * p.pack_words;
+    for (int w = tid; w < (int)((svox + 15) / 16); w += nthreads) {
+        const int off = X0 * gg + 16 * w, gw = off >> 4, sh = (off & 15) * 2;
+        s_grid[w] = sh != 0 ? (G[gw] >> sh) | (G[gw + 1] << (32 - sh)) : G[gw];
+    }
+    uint4 *s_masks4 = reinterpret_cast<uint4 *>(s_a);
+    const int mask_quads = p.mask_words / 2;
+    for (int w = tid; w < mask_quads; w += nthreads) s_masks4[w] = make_uint4(0u, 0u, 0u, 0u);
+    const bool mark = (p.ablate & 1) == 0, second = (p.ablate & 2) == 0;
+
+    for (int j = j0; j < j1; ++j) {
+        __syncthreads();  // grid loaded; masks clear
+        const size_t cj = (size_t)el * p.k + j;
+        const int *src = reinterpret_cast<const int *>(p.cams + cj * kCamWords + 16);
+        const int x0 = src[0], y0 = src[1], z0 = src[2];
+        const uint32_t *meta = p.meta + cj * p.nrays;
+        const int4 *rec = p.rec + cj * p.nrays;
+        int n_unknown = 0, n_unknown_hit = 0;
+        for (int r = tid; r < p.nrays; r += nthreads) {
+            const uint32_t m = meta[r];
+            const int count = (int)(m & 255u), xa = (int)((m >> 16) & 255u), xb = (int)(m >> 24);
+            if (count == 0 || xb < X0 || xa >= X1) continue;  // nothing to mark, or not in this slab
+            const bool blocked = (m & 256u) != 0u && second;
+            const int4 q = rec[r];
+            const int reach = max(max(abs(q.x - x0), abs(q.y - y0)), abs(q.z - z0));
+            SlabWalk w = reach < (1 << 14) ? make_slab_walk<int>(x0, y0, z0, q.x, q.y, q.z, g, q.w, count, X0, X1)
+                                           : make_slab_walk<long long>(x0, y0, z0, q.x, q.y, q.z, g, q.w, count, X0, X1);
+            for (int i = 0; i < w.n; ++i) {
+                if ((unsigned)w.lin < svox) {  // x inside the slab (y, z are inside the grid on every recorded step)
+                    const uint32_t cls = (s_grid[w.lin >> 4] >> ((w.lin & 15) * 2)) & 3u;
+                    if (cls == 0u && mark) {
+                        const uint32_t bit = 1u << (w.lin & 31);
+                        n_unknown += (atomicOr(&s_a[w.lin >> 5], bit) & bit) == 0u;
+                        if (blocked) n_unknown_hit += (atomicOr(&s_b[w.lin >> 5], bit) & bit) == 0u;
+                    }
+                }
+                if (w.p1 >= 0) { w.lin += w.lb; w.p1 -= w.two_da; }
+                if (w.p2 >= 0) { w.lin += w.lc; w.p2 -= w.two_da; }
+                w.lin += w.la;
+                w.p1 += w.two_db;
+                w.p2 += w.two_dc;
+            }
+        }
+        n_unknown = wave_reduce_sum(n_unknown);
+        n_unknown_hit = wave_reduce_sum(n_unknown_hit);
+        if ((tid & (kWave - 1)) == 0) {
+            s_part[tid / kWave][0] = n_unknown;
+            s_part[tid / kWave][1] = n_unknown_hit;
+        }
+        __syncthreads();  // every ray of candidate j is done: partials complete, masks free
+        if (tid == 0) {
+            int a = 0, c = 0;
+            for (int w = 0; w < nthreads / kWave; ++w) {
+                a += s_part[w][0];
+                c += s_part[w][1];
+            }
+            int32_t *o = p.gain + ((size_t)e * p.k + j) * 3;
+            if (a != 0) atomicAdd(o, a);
+            if (c != 0) atomicAdd(o + 1, c);
+        }
+        // (ordered in front of the next candidate's rays by the barrier at the loop's head, as in k_view_gain)
+        if (j + 1 < j1 && mark)
+            for (int w = tid; w < mask_quads; w += nthreads) s_masks4[w] = make_uint4(0u, 0u, 0u, 0u);
+    }
+}
+
+// what both host entry points of the slab path derive from the sizes
+struct VsPlan {
+    int nu, nrays, pack_words, batch;
+    size_t off_cams, off_rec, off_meta, bytes;
+};
+
+inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+inline bool vs_plan(int n, int k, int g, int h, int w, int stride, VsPlan &pl)
+{
+    if (!(n > 0 && k > 0 && g >= 2 && g <= kMaxSlabGrid && h > 0 && w > 0 && stride >= 1 && h <= 32768 && w <= 32768)) return false;
+    const int half = stride / 2;
+    pl.nu = half < w ? (w - half + stride - 1) / stride : 0;
+    const int nv = half < h ? (h - half + stride - 1) / stride : 0;
+    pl.nrays = pl.nu * nv;
+    const int g3 = g * g * g;
+    pl.pack_words = (((g3 + 15) / 16) + 1 + 3) & ~3;  // + 1: k_vg_slab reads one word past an unaligned slab
+    // envs per batch: the ray records of a batch stay near kBatchBytes, so that the slab pass finds them in the last-level cache
+    const size_t per_env = (size_t)k * (size_t)(pl.nrays > 0 ? pl.nrays : 1) * 20;
+    size_t batch = kBatchBytes / per_env;
+    batch = batch < 8 ? 8 : batch;
+    pl.batch = batch > (size_t)n ? n : (int)batch;
+    const size_t bn = (size_t)pl.batch, rays = bn * k * pl.nrays;
+    pl.off_cams = align256(bn * pl.pack_words * sizeof(uint32_t));
+    pl.off_rec = align256(pl.off_cams + bn * k * kCamWords * sizeof(float));
+    pl.off_meta = align256(pl.off_rec + rays * sizeof(int4));
+    pl.bytes = align256(pl.off_meta + rays * sizeof(uint32_t));
+    return true;
+}
+
+inline size_t slab_lds_bytes(int g, int s, int &grid_words, int &mask_words)
+{
+    const int vox = s * g * g;
+    grid_words = (((vox + 15) / 16) + 3) & ~3;
+    mask_words = (((vox + 31) / 32) + 3) & ~3;
+    return (size_t)(grid_words + 2 * mask_words) * sizeof(uint32_t);
+}
+
 }  // namespace
+
+static bool view_gain_args_ok(const GnbvViewGain &a, int max_grid)
+{
+    return a.n > 0 && a.k > 0 && a.g >= 2 && a.g <= max_grid && a.h > 0 && a.w > 0 && a.stride >= 1 && a.h <= 32768 && a.w <= 32768 &&
+           std::isfinite(a.range) && a.range > 0.0f && a.chunk >= 0 && a.ablate >= 0 && a.ablate <= 3 && a.tri_i8 != nullptr &&
+           a.poses != nullptr && a.range_gt != nullptr && a.voxel_size != nullptr && a.inv_intri != nullptr && a.gain != nullptr &&
+           a.tri_row_stride >= (int64_t)a.g * a.g * a.g;
+}
 
 GNBV_API int gnbv_view_gain(const GnbvViewGain *args, void *stream)
 {
     GNBV_CHECK_ARG(args != nullptr);
     const GnbvViewGain a = *args;
-    GNBV_CHECK_ARG(a.n > 0 && a.k > 0 && a.g >= 2 && a.g <= kMaxGrid && a.h > 0 && a.w > 0 && a.stride >= 1);
-    GNBV_CHECK_ARG(a.h <= 32768 && a.w <= 32768);
-    GNBV_CHECK_ARG(std::isfinite(a.range) && a.range > 0.0f && a.chunk >= 0 && a.ablate >= 0 && a.ablate <= 3);
-    GNBV_CHECK_ARG(a.tri_i8 != nullptr && a.poses != nullptr && a.range_gt != nullptr && a.voxel_size != nullptr);
-    GNBV_CHECK_ARG(a.inv_intri != nullptr && a.gain != nullptr);
+    GNBV_CHECK_ARG(view_gain_args_ok(a, kMaxGrid));
     const int g3 = a.g * a.g * a.g;
-    GNBV_CHECK_ARG(a.tri_row_stride >= g3);
     VgParams p;
     p.n = a.n; p.k = a.k; p.g = a.g;
     // candidates per workgroup: enough workgroups for two per compute unit, but the grid is packed once per workgroup
@@ -339,5 +666,79 @@ GNBV_API int gnbv_view_gain(const GnbvViewGain *args, void *stream)
         hipFuncSetAttribute((const void *)k_view_gain, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return (int)hipGetLastError();
     hipLaunchKernelGGL(k_view_gain, dim3((unsigned)(a.n * p.chunks)), dim3(threads), lds, gnbv_stream(stream), p);
+    return gnbv_launch_status();
+}
+
+GNBV_API size_t gnbv_view_gain_slab_workspace_bytes(int n, int k, int g, int h, int w, int stride)
+{
+    VsPlan pl;
+    return vs_plan(n, k, g, h, w, stride, pl) ? pl.bytes : 0;
+}
+
+GNBV_API int gnbv_view_gain_slab(const GnbvViewGain *args, int slab, void *workspace, size_t workspace_bytes, void *stream)
+{
+    GNBV_CHECK_ARG(args != nullptr);
+    const GnbvViewGain a = *args;
+    GNBV_CHECK_ARG(view_gain_args_ok(a, kMaxSlabGrid) && slab >= 0);
+    VsPlan pl;
+    GNBV_CHECK_ARG(vs_plan(a.n, a.k, a.g, a.h, a.w, a.stride, pl));
+    GNBV_CHECK_ARG(workspace != nullptr && workspace_bytes >= pl.bytes && ((uintptr_t)workspace & 15) == 0);
+    VsParams p;
+    p.k = a.k; p.g = a.g;
+    // slab height: the fewest slabs whose grid + masks fit the LDS budget, of equal height; a requested height is kept if it fits
+    int s = slab > a.g ? a.g : slab;
+    if (s == 0) {
+        int ns = 1;
+        while (slab_lds_bytes(a.g, (a.g + ns - 1) / ns, p.grid_words, p.mask_words) > kSlabLdsBudget) ++ns;
+        s = (a.g + ns - 1) / ns;
+    }
+    while (slab_lds_bytes(a.g, s, p.grid_words, p.mask_words) > kSlabLdsMax) --s;  // s = 1: 2 * 8 KiB at 128^3
+    const size_t lds = slab_lds_bytes(a.g, s, p.grid_words, p.mask_words);
+    p.slab = s;
+    p.nslab = (a.g + s - 1) / s;
+    const int batch_pad = (pl.batch + 7) / 8 * 8;  // the XCD-aware grids are whole multiples of 8 envs
+    int chunk = a.chunk;
+    if (chunk == 0) {  // ten workgroups per compute unit even out the slabs' unequal shares of the rays (512 envs x 128^3, K = 32:
+                       // 24.5 / 23.2 / 22.8 ms at 16 / 8 / 4 candidates per workgroup; the slab's grid is re-read per workgroup)
+        const int want = (kSlabWorkgroups + pl.batch * p.nslab - 1) / (pl.batch * p.nslab);
+        chunk = (a.k + want - 1) / want;
+    }
+    chunk = chunk < 1 ? 1 : (chunk > a.k ? a.k : chunk);
+    p.chunk = chunk;
+    p.chunks = (a.k + chunk - 1) / chunk;
+    p.rblocks = (pl.nrays + kFateThreads - 1) / kFateThreads;
+    GNBV_CHECK_ARG((int64_t)batch_pad * p.chunks * p.nslab <= 0x7fffffff && (int64_t)batch_pad * a.k * p.rblocks <= 0x7fffffff);
+    p.tri = a.tri_i8;
+    p.tri_row_stride = a.tri_row_stride;
+    p.tri_aligned = (((uintptr_t)a.tri_i8 | (uintptr_t)a.tri_row_stride) & 15) == 0;
+    p.poses = a.poses; p.range_gt = a.range_gt; p.voxel_size = a.voxel_size;
+    for (int i = 0; i < 9; ++i) p.kinv.k[i] = a.inv_intri[i];
+    p.stride = a.stride; p.nu = pl.nu; p.nrays = pl.nrays;
+    p.range = a.range;
+    p.gain = a.gain;
+    p.c2w_out = a.c2w_out;
+    p.pack_words = pl.pack_words;
+    p.ablate = a.ablate;
+    char *ws = static_cast<char *>(workspace);
+    p.packed = reinterpret_cast<uint32_t *>(ws);
+    p.cams = reinterpret_cast<float *>(ws + pl.off_cams);
+    p.rec = reinterpret_cast<int4 *>(ws + pl.off_rec);
+    p.meta = reinterpret_cast<uint32_t *>(ws + pl.off_meta);
+    int threads = ((pl.nrays > 0 ? pl.nrays : 1) + kWave - 1) / kWave * kWave;
+    const int cap = lds > 32 * 1024 ? kMaxThreads : 256;
+    threads = threads > cap ? cap : threads;
+    hipStream_t st = gnbv_stream(stream);
+    if (lds > 64 * 1024 &&
+        hipFuncSetAttribute((const void *)k_vg_slab, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        return (int)hipGetLastError();
+    for (int e0 = 0; e0 < a.n; e0 += pl.batch) {  // the workspace is reused: the stream orders the batches
+        const int ne = a.n - e0 < pl.batch ? a.n - e0 : pl.batch, ne_pad = (ne + 7) / 8 * 8;
+        int64_t items = (int64_t)ne * pl.pack_words;
+        if ((int64_t)ne * a.k * 3 > items) items = (int64_t)ne * a.k * 3;
+        hipLaunchKernelGGL(k_vg_prep, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, p, e0, ne);
+        if (pl.nrays == 0) continue;
+        hipLaunchKernelGGL(k_vg_fate, dim3((unsigned)(ne_pad * a.k * p.rblocks)), dim3(kFateThreads), 0, st, p, e0, ne);
+        hipLaunchKernelGGL(k_vg_slab, dim3((unsigned)(ne_pad * p.chunks * p.nslab)), dim3(threads), lds, st, p, e0, ne);
+    }
     return gnbv_launch_status();
 }

@@ -148,6 +148,30 @@ class MeshScene:
                                                      _lib.stream_ptr(self.device)), "gnbv_collide_cylinder")
         return out
 
+    def collide_candidates(self, poses: torch.Tensor, body, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """gnbv_collide_cylinder_batch on the current stream: contact code [N,K] u8 of `body` at poses [N, K, >= 6] f32 (unit
+        element stride, rows (e, j) evenly spaced), one launch; out[e, j] == collide(poses[:, j])[e], bit for bit."""
+        if self.device.type != "cuda":
+            raise _lib.GennbvHipError("MeshScene.collide_candidates runs on the GPU only (no CPU fallback): build the MeshScene on a "
+                                      "cuda device")
+        n = self.num_envs
+        _lib.require_cuda(poses, out)
+        assert poses.dtype == torch.float32 and poses.dim() == 3 and poses.shape[0] == n and poses.shape[2] >= 6 and poses.stride(2) == 1
+        k = int(poses.shape[1])
+        if k > 1 and n > 1 and poses.stride(0) != k * poses.stride(1):
+            poses = poses.contiguous()
+        row = int(poses.stride(1)) if k > 1 else int(poses.stride(0))
+        if row < 6:  # a dimension of size 1 may carry any stride
+            poses, row = poses.contiguous(), int(poses.shape[2])
+        if out is None:
+            out = torch.empty(n, k, dtype=torch.uint8, device=self.device)
+        assert out.dtype == torch.uint8 and out.shape == (n, k) and out.is_contiguous()
+        sc, ob = self.c_struct(), self.objects_c_struct()
+        _lib.check(_lib.load().gnbv_collide_cylinder_batch(C.byref(sc), C.byref(ob), poses.data_ptr(), k, row, float(body.radius),
+                                                           float(body.half_length), int(bool(body.ground)), out.data_ptr(),
+                                                           _lib.stream_ptr(self.device)), "gnbv_collide_cylinder_batch")
+        return out
+
     # ------------------------------------------------------------------
     @staticmethod
     def from_boxes(scene: S.Scene, device=None) -> "MeshScene":

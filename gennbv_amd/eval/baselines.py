@@ -1,5 +1,5 @@
 """Baseline view planners to compare a learned policy against: a uniformly random lattice pose and the greedy
-next-best-view planner over the view gain (ops/view_gain.py, csrc/viewgain.hip).
+next-best-view planner over the view gain (ops/view_gain.py, csrc/viewgain.hip; grids up to 128^3).
 
 Both speak the protocol `evaluate_policy_grid_obs` uses: `.policy(obs, deterministic=True) -> (actions, None, None)`,
 and `predict(obs)`; actions are int64 [N,6] on the lattice of the task (inside clip_pose_idx_low / clip_pose_idx_up).
@@ -87,10 +87,10 @@ class GreedyGainPolicy:
         self.cands = LatticeCandidates(cfg, k, seed, look_at_scene)
         self.avoid_collisions = bool(avoid_collisions) and getattr(env, "collision", None) is not None
         if gain_backend is None:
-            from ..ops.view_gain import ViewGain
+            from ..ops.view_gain import make_view_gain
             u = env.updater
-            gain_backend = ViewGain(self.num_envs, self.k, cfg, u.range_gt, u.voxel_size_gt, inv_intrinsics=u.inv_intri_host,
-                                    stride=stride, device=env.device)
+            gain_backend = make_view_gain(self.num_envs, self.k, cfg, u.range_gt, u.voxel_size_gt, inv_intrinsics=u.inv_intri_host,
+                                          stride=stride, device=env.device)
         self.gain_backend = gain_backend
         self._contact = None
         self.last_gain = None
@@ -104,11 +104,17 @@ class GreedyGainPolicy:
         self.last_gain = gain
         contact = None
         if self.avoid_collisions:
-            if self._contact is None:
-                self._contact = torch.zeros(k, n, dtype=torch.uint8, device=obs.device)
-            for j in range(k):  # one call per candidate column ([N,6] rows, stride K * 6)
-                self.env.collision_mesh.collide(poses[:, j], self.env.collision, out=self._contact[j])
-            contact = self._contact.t()
+            mesh = self.env.collision_mesh
+            if hasattr(mesh, "collide_candidates"):  # all N x K poses in one launch
+                if self._contact is None:
+                    self._contact = torch.zeros(n, k, dtype=torch.uint8, device=obs.device)
+                contact = mesh.collide_candidates(poses, self.env.collision, out=self._contact)
+            else:
+                if self._contact is None:
+                    self._contact = torch.zeros(k, n, dtype=torch.uint8, device=obs.device)
+                for j in range(k):  # one call per candidate column ([N,6] rows, stride K * 6)
+                    mesh.collide(poses[:, j], self.env.collision, out=self._contact[j])
+                contact = self._contact.t()
         best = choose(gain, self.weights, contact)
         return cand[torch.arange(n, device=cand.device), best], None, None
 

@@ -5,6 +5,9 @@ model is run hypothetically: per candidate three int32 -- distinct unknown voxel
 before their first occupied voxel, the same over the rays that meet one, and the number of those rays (the exact definition:
 include/gennbv_hip.h gnbv_view_gain).  One launch for all N x K candidates; outputs are preallocated and reused: a result is
 valid until the next call.  GPU only, no CPU fallback.
+
+ViewGain keeps an env's grid in LDS (grid_size <= 64); ViewGainSlab computes the same integers for grid_size <= 128 through
+gnbv_view_gain_slab (the rays' fates first, then slabs of x-planes) with a preallocated workspace; make_view_gain picks.
 """
 from __future__ import annotations
 
@@ -18,9 +21,12 @@ from ..env import synthetic as S
 from ..env.config import TaskConfig
 
 MAX_GRID = 64  # the grid (2 bits per voxel) and two visited masks live in LDS: G^3 / 2 bytes
+MAX_GRID_SLAB = 128  # ViewGainSlab
 
 
 class ViewGain:
+    _max_grid = MAX_GRID
+
     def __init__(self, num_envs: int, k: int, cfg: TaskConfig, range_gt: torch.Tensor, voxel_size: torch.Tensor,
                  inv_intrinsics: Optional[torch.Tensor] = None, stride: int = 4, range_m: Optional[float] = None,
                  device="cuda:0", with_c2w: bool = False, chunk: int = 0):
@@ -28,9 +34,10 @@ class ViewGain:
         if self.device.type != "cuda":
             raise _lib.GennbvHipError("ViewGain runs on the GPU only (no CPU fallback)")
         g = int(cfg.grid_size)
-        if g > MAX_GRID:
-            raise _lib.GennbvHipError(f"ViewGain keeps the grid and its visited masks in LDS: grid_size <= {MAX_GRID}, got {g} "
-                                      "(a slab form for larger grids is not written: DESIGN.md section 7)")
+        if g > self._max_grid:
+            raise _lib.GennbvHipError(f"{type(self).__name__}: grid_size <= {self._max_grid}, got {g}" + (
+                " (ViewGain keeps the grid and its visited masks in LDS; ViewGainSlab / make_view_gain go up to "
+                f"{MAX_GRID_SLAB})" if self._max_grid == MAX_GRID else ""))
         self.lib = _lib.load()
         self.num_envs, self.k, self.g = int(num_envs), int(k), g
         self.h, self.w, self.stride = int(cfg.camera_height), int(cfg.camera_width), int(stride)
@@ -72,5 +79,38 @@ class ViewGain:
         poses = poses.contiguous()
         a = self._args
         a.tri_i8, a.tri_row_stride, a.poses = tri.data_ptr(), max(int(tri.stride(0)), g3), poses.data_ptr()
-        _lib.check(self.lib.gnbv_view_gain(C.byref(a), _lib.stream_ptr(self.device)), "gnbv_view_gain")
+        self._launch(a)
         return self.gain
+
+    def _launch(self, a):
+        _lib.check(self.lib.gnbv_view_gain(C.byref(a), _lib.stream_ptr(self.device)), "gnbv_view_gain")
+
+
+class ViewGainSlab(ViewGain):
+    """The same operator for grid_size <= 128 (gnbv_view_gain_slab): ViewGain's arguments plus `slab`, the x-planes per
+    slab (0 = chosen from the grid size; any height gives the same integers).  The workspace is allocated once, here."""
+    _max_grid = MAX_GRID_SLAB
+
+    def __init__(self, num_envs: int, k: int, cfg: TaskConfig, range_gt: torch.Tensor, voxel_size: torch.Tensor,
+                 inv_intrinsics: Optional[torch.Tensor] = None, stride: int = 4, range_m: Optional[float] = None,
+                 device="cuda:0", with_c2w: bool = False, chunk: int = 0, slab: int = 0):
+        super().__init__(num_envs, k, cfg, range_gt, voxel_size, inv_intrinsics, stride, range_m, device, with_c2w, chunk)
+        self.slab = int(slab)
+        self.workspace_bytes = int(self.lib.gnbv_view_gain_slab_workspace_bytes(self.num_envs, self.k, self.g, self.h, self.w,
+                                                                                self.stride))
+        if self.workspace_bytes == 0:
+            raise _lib.GennbvHipError(f"ViewGainSlab: sizes refused (n {num_envs}, k {k}, g {self.g}, camera {self.h}x{self.w}, "
+                                      f"stride {stride})")
+        self.workspace = torch.empty(self.workspace_bytes, dtype=torch.uint8, device=self.device)
+
+    def _launch(self, a):
+        _lib.check(self.lib.gnbv_view_gain_slab(C.byref(a), self.slab, self.workspace.data_ptr(), self.workspace_bytes,
+                                                _lib.stream_ptr(self.device)), "gnbv_view_gain_slab")
+
+
+def make_view_gain(num_envs: int, k: int, cfg: TaskConfig, *args, **kwargs) -> ViewGain:
+    """ViewGain for grid_size <= 64 (one launch, the grid in LDS), ViewGainSlab above; `slab` is passed to the latter only."""
+    if int(cfg.grid_size) <= MAX_GRID:
+        kwargs.pop("slab", None)
+        return ViewGain(num_envs, k, cfg, *args, **kwargs)
+    return ViewGainSlab(num_envs, k, cfg, *args, **kwargs)

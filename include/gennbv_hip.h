@@ -242,6 +242,12 @@ typedef struct GnbvMeshObjects {
 int gnbv_collide_cylinder(const GnbvMeshScene *scene /*[host]*/, const GnbvMeshObjects *objects /*[host]*/, const float *poses,
                           int64_t poses_row_stride /*floats*/, float radius, float half_length, int ground, uint8_t *contact_out /*[N]*/,
                           void *stream);
+/* K candidate poses per env in one launch (one wave per (env, candidate)): contact_out[e, j] is bit-identical to what
+ * gnbv_collide_cylinder stores for env e at pose (e, j).  poses [N, K, >= 6] with the stride between consecutive (e, j) rows in
+ * floats; k >= 1, N * k <= 2^31 - 1, else as gnbv_collide_cylinder. */
+int gnbv_collide_cylinder_batch(const GnbvMeshScene *scene /*[host]*/, const GnbvMeshObjects *objects /*[host]*/, const float *poses,
+                                int k, int64_t poses_row_stride /*floats*/, float radius, float half_length, int ground,
+                                uint8_t *contact_out /*[N,K]*/, void *stream);
 
 /* compute_reward (env_train_base.py:377-398), _reward_* / check_termination /
  * reset_idx (env_train_gennbv.py:377-457,535-556), update_extra_episode_info
@@ -706,8 +712,8 @@ int gnbv_scan_export(const GnbvScanSet *set /*[host]*/, int env, float *xyz, voi
  *     first occupied one (not counted); a ray that met one is `blocked`.
  * gain[e, j] = { distinct unknown voxels visited by any ray, the same over the blocked rays only, blocked rays }.  Integers
  * with one right answer; every element is written; deterministic (no global atomics).  One launch, no workspace.
- * g outside 2..64 (the grid and two visited masks live in LDS), stride < 1, range not positive and finite, or k < 1 return
- * hipErrorInvalidValue.  [host struct]; pointers are device unless noted. */
+ * g outside 2..64 (the grid and two visited masks live in LDS; gnbv_view_gain_slab below goes to 128), stride < 1, range not
+ * positive and finite, or k < 1 return hipErrorInvalidValue.  [host struct]; pointers are device unless noted. */
 typedef struct GnbvViewGain {
     int n, k, g;                    /* envs, candidates per env, grid edge */
     const int8_t *tri_i8;           /* [n, g^3] with a row stride in BYTES (rows inside a larger buffer work) */
@@ -725,6 +731,22 @@ typedef struct GnbvViewGain {
                                      * bit 1 no second mask (unknown_hit is then 0) */
 } GnbvViewGain;
 int gnbv_view_gain(const GnbvViewGain *args /*[host]*/, void *stream);
+
+/* The same quantity, bit for bit, for 2 <= g <= 128 (new entry points of ABI 5).  The grid no longer fits in LDS, so the call
+ * runs three kernels per batch of envs on the caller's stream: the grids packed to 2 bits per voxel and the cameras; every
+ * ray's fate (where it enters the grid, where it stops; `blocked` is complete here); then workgroups (env, chunk of candidates,
+ * slab of `slab` x-planes) mark the slab's part of the two visited masks in LDS and add their distinct counts to gain with
+ * int32 atomicAdd: integer sums, so the result is deterministic and does not depend on `slab` (0 = chosen from g: 16 at 128^3;
+ * a height whose grid + masks exceed a workgroup's LDS is reduced to the largest that fits, 19 at 128^3) or on `chunk`.
+ * Every element of gain is written.  No host synchronisation, no allocation.
+ * The workspace (16-B aligned, caller-owned, reused by every call) holds ONE batch of envs: 20 bytes per ray (n_b k rays),
+ * g^3 / 4 bytes per env and 80 bytes per candidate, n_b = the envs whose ray records fill 128 MiB (at least 8, at most n), so
+ * it stops growing with n: 155 MB at 512 envs x 128^3, 240x320, stride 4, k = 32 (n_b = 43), where one batch for all envs
+ * would take 1.57 GB of records and 268 MB of grids.
+ * Returns hipErrorInvalidValue for everything gnbv_view_gain refuses (with g up to 128), slab < 0, and a NULL, misaligned or
+ * too small workspace; gnbv_view_gain_slab_workspace_bytes returns 0 for sizes the call would refuse. */
+size_t gnbv_view_gain_slab_workspace_bytes(int n, int k, int g, int h, int w, int stride);
+int gnbv_view_gain_slab(const GnbvViewGain *args /*[host]*/, int slab, void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

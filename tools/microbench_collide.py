@@ -8,6 +8,8 @@ Cases:
   boxes      256 envs, make_scenes box scenes at BASELINE configs[1] geometry (64^3 grid; <= 96 triangles per env),
              cf2x body at random lattice poses
   dense      256 envs, two UV spheres + boxes per env (~20 k triangles: the cell grid at work), the same poses
+  batch_k32  the box scenes, 256 x 32 random lattice poses: one collide_candidates call (gnbv_collide_cylinder_batch) against
+             the 32 collide calls it replaces, alternated in one process
   env_step   closed-loop ReplayFeedEnv.step at 256 x 240x320 x 64^3, without and with a CollisionBody, alternated in one process
 
 Kernel times come from a separate `rocprofv3 --kernel-trace --stats -- python tools/microbench_collide.py` run.
@@ -49,6 +51,32 @@ def collide_case(name, mesh, cfg, args):
     return r
 
 
+def batch_case(args, k=32):
+    from gennbv_amd.eval.baselines import LatticeCandidates
+    cfg = baseline_config(1)
+    n = 256
+    mesh = MeshScene.from_boxes(S.make_scenes(n, cfg.grid_size, seed=1), device=DEV)
+    lc = LatticeCandidates(cfg, k, seed=3)
+    poses = lc.poses(lc.sample(n)).to(DEV)
+    body = CollisionBody()
+    out_b = torch.empty(n, k, dtype=torch.uint8, device=DEV)
+    out_c = torch.empty(k, n, dtype=torch.uint8, device=DEV)
+
+    def columns():
+        for j in range(k):
+            mesh.collide(poses[:, j], body, out=out_c[j])
+    res = {"batched": [], "columns": []}
+    for _ in range(args.repeats):
+        res["batched"] += time_calls(lambda: mesh.collide_candidates(poses, body, out=out_b), args.iters, 1, warmup=2)
+        res["columns"] += time_calls(columns, args.iters, 1, warmup=2)
+    r = {"case": "batch_k32", "envs": n, "k": k, "equal": bool(torch.equal(out_b, out_c.t())),
+         "contact_frac": float((out_b != 0).float().mean())}
+    for name, us in res.items():
+        r[name] = stats(us)
+    r["columns_over_batched"] = r["columns"]["us_median"] / r["batched"]["us_median"]
+    return r
+
+
 def env_step_case(args):
     from gennbv_amd.env.render_feed import RenderFeed
     from gennbv_amd.env.replay_feed import ReplayFeedEnv
@@ -82,7 +110,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--cases", default="boxes,dense,env_step")
+    ap.add_argument("--cases", default="boxes,dense,batch_k32,env_step")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -94,6 +122,8 @@ def main():
             r = collide_case(c, MeshScene.from_boxes(S.make_scenes(256, cfg.grid_size, seed=1), device=DEV), cfg, args)
         elif c == "dense":
             r = collide_case(c, dense_mesh(256), cfg, args)
+        elif c == "batch_k32":
+            r = batch_case(args)
         elif c == "env_step":
             r = env_step_case(args)
         else:

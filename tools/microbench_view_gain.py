@@ -1,6 +1,6 @@
-"""Microbenchmark of the view gain (gnbv_view_gain) beside the closed-loop env step it precedes.
+"""Microbenchmark of the view gain (gnbv_view_gain, gnbv_view_gain_slab) beside the closed-loop env step it precedes.
 
-    python tools/microbench_view_gain.py [--repeats 7] [--iters 5] [--cases ...] [--out FILE.json]
+    python tools/microbench_view_gain.py [--repeats 7] [--iters 5] [--cases ...] [--slabs 0,8] [--chunk 0] [--out FILE.json]
 
 Device events around `iters` back-to-back calls, after warm-up, `repeats` times; reported: median / min / max us per call.
 Cases (N, G, camera, stride, K):
@@ -8,7 +8,10 @@ Cases (N, G, camera, stride, K):
   g64_k32     256, 64^3, 240x320, 4, 32     on all-unknown grids and on mid-episode grids (10 closed-loop steps of random
   g64_k128    256, 64^3, 240x320, 4, 128    lattice poses), with the ablations: walk without marking, marking without the
   g20_k32     256, 20^3, 400x400, 4, 32     second mask
+  g128_k32    512, 128^3, 240x320, 4, 32    (BASELINE configs[4]'s shard; the slab path, once per slab height of --slabs,
+                                            with its workspace bytes)
   env_step    closed-loop ReplayFeedEnv.step at 256 x 240x320 x 64^3 in the same process: the yardstick
+  env_step128 the same at 512 x 240x320 x 128^3 (--envs128 to change the 512 of both 128^3 cases)
   torch       what the existing API offers for one small case (per candidate: utils.bresenham3D_pycuda on the lattice targets
               + torch set operations), timed once and checked equal to the kernel
 
@@ -32,7 +35,7 @@ from gennbv_amd.env import synthetic as S  # noqa: E402
 from gennbv_amd.env.config import TaskConfig  # noqa: E402
 from gennbv_amd.env.mesh_scene import MeshScene  # noqa: E402
 from gennbv_amd.eval.baselines import LatticeCandidates  # noqa: E402
-from gennbv_amd.ops.view_gain import ViewGain  # noqa: E402
+from gennbv_amd.ops.view_gain import ViewGain, make_view_gain  # noqa: E402
 from tools.microbench_render import time_calls  # noqa: E402
 
 DEV = "cuda:0"
@@ -55,17 +58,22 @@ def mid_episode_grid(cfg, n, scene, steps=10):
     gen = torch.Generator().manual_seed(5)
     for _ in range(steps):
         obs = env.step(S.sample_actions(n, cfg, gen).to(DEV))[0]
-    return obs[:, cfg.state_dim:cfg.state_dim + cfg.grid_dim].to(torch.int8).contiguous()
+    tri = obs[:, cfg.state_dim:cfg.state_dim + cfg.grid_dim].to(torch.int8).contiguous()
+    del env, obs
+    torch.cuda.empty_cache()
+    return tri
 
 
-def gain_case(name, n, g, h, w, stride, k, args):
+def gain_case(name, n, g, h, w, stride, k, args, slab=0):
     cfg = TaskConfig(camera_width=w, camera_height=h, grid_size=g)
     scene = S.make_scenes(n, g, seed=1)
     lc = LatticeCandidates(cfg, k, seed=3)
     poses = lc.poses(lc.sample(n)).to(DEV)
-    vg = ViewGain(n, k, cfg, scene.range_gt, scene.voxel_size, stride=stride, device=DEV)
     grids = {"all_unknown": torch.zeros(n, g ** 3, dtype=torch.int8, device=DEV), "mid_episode": mid_episode_grid(cfg, n, scene)}
-    out = {"case": name, "envs": n, "grid": g, "h": h, "w": w, "stride": stride, "k": k}
+    vg = make_view_gain(n, k, cfg, scene.range_gt, scene.voxel_size, stride=stride, device=DEV, slab=slab, chunk=args.chunk)
+    out = {"case": name, "envs": n, "grid": g, "h": h, "w": w, "stride": stride, "k": k, "chunk": args.chunk}
+    if hasattr(vg, "workspace_bytes"):
+        out.update(slab=slab, workspace_bytes=vg.workspace_bytes)
     for gname, tri in grids.items():
         for aname, ablate in (("full", 0), ("no_second_mask", 2), ("walk_only", 1)):
             vg._args.ablate = ablate
@@ -76,10 +84,9 @@ def gain_case(name, n, g, h, w, stride, k, args):
     return out
 
 
-def env_step_case(args):
-    n = 256
-    cfg = TaskConfig(camera_width=320, camera_height=240, grid_size=64)
-    env = closed_env(cfg, n, S.make_scenes(n, 64, seed=1))
+def env_step_case(args, name="env_step", n=256, g=64):
+    cfg = TaskConfig(camera_width=320, camera_height=240, grid_size=g)
+    env = closed_env(cfg, n, S.make_scenes(n, g, seed=1))
     env.reset()
     gen = torch.Generator().manual_seed(5)
     acts = [S.sample_actions(n, cfg, gen).to(DEV) for _ in range(8)]
@@ -88,7 +95,7 @@ def env_step_case(args):
     def step():
         env.step(acts[k[0] % len(acts)])
         k[0] += 1
-    out = {"case": "env_step", "envs": n, "h": 240, "w": 320, "grid": 64}
+    out = {"case": name, "envs": n, "h": 240, "w": 320, "grid": g}
     out.update(stats(time_calls(step, args.iters, args.repeats)))
     return out
 
@@ -156,18 +163,27 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--iters", type=int, default=5)
-    ap.add_argument("--cases", default="g64_k32,g64_k128,g20_k32,env_step,torch")
+    ap.add_argument("--cases", default="g64_k32,g64_k128,g20_k32,g128_k32,env_step,env_step128,torch")
+    ap.add_argument("--slabs", default="0", help="slab heights of the g128 case, comma-separated (0 = the default)")
+    ap.add_argument("--envs128", type=int, default=512)
+    ap.add_argument("--chunk", type=int, default=0, help="candidates per workgroup (0 = chosen)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("microbench_view_gain needs a GPU")
     table = {"g64_k32": (256, 64, 240, 320, 4, 32), "g64_k128": (256, 64, 240, 320, 4, 128), "g20_k32": (256, 20, 400, 400, 4, 32)}
     results = []
+    table["g128_k32"] = (args.envs128, 128, 240, 320, 4, 32)
+    cases = []
     for c in args.cases.split(","):
+        cases += [(c, int(s)) for s in args.slabs.split(",")] if c == "g128_k32" else [(c, 0)]
+    for c, slab in cases:
         if c in table:
-            r = gain_case(c, *table[c], args)
+            r = gain_case(c, *table[c], args, slab=slab)
         elif c == "env_step":
             r = env_step_case(args)
+        elif c == "env_step128":
+            r = env_step_case(args, c, args.envs128, 128)
         elif c == "torch":
             r = torch_case(args)
         else:
