@@ -101,6 +101,7 @@ SIGNATURES = {
     "gnbv_view_gain": (_i, [_p, _p]),
     "gnbv_view_gain_slab_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "gnbv_view_gain_slab": (_i, [_p, _i, _p, _sz, _p]),
+    "gnbv_view_cover": (_i, [_p, _p, _p]),
     "gnbv_gae_sb3": (_i, [_p, _p, _p, _p, _p, _i, _i, _d, _d, _p, _p, _p]),
     "gnbv_gae_rsl": (_i, [_p, _p, _p, _p, _i, _i, _d, _d, _p, _p, _p]),
 }
@@ -150,6 +151,13 @@ class GnbvViewGain(C.Structure):
     _fields_ = [("n", _i), ("k", _i), ("g", _i), ("tri_i8", _p), ("tri_row_stride", _i64), ("poses", _p), ("range_gt", _p),
                 ("voxel_size", _p), ("inv_intri", _p), ("h", _i), ("w", _i), ("stride", _i), ("range", _f), ("gain", _p),
                 ("c2w_out", _p), ("chunk", _i), ("ablate", _i)]
+
+
+class GnbvViewCover(C.Structure):
+    """include/gennbv_hip.h: GnbvViewCover"""
+    _fields_ = [("n", _i), ("k", _i), ("g", _i), ("poses", _p), ("range_gt", _p), ("voxel_size", _p), ("inv_intri", _p),
+                ("h", _i), ("w", _i), ("stride", _i), ("depth_sense_dist", _f), ("gt_bits", _p), ("scanned_bits", _p),
+                ("cover", _p), ("seen_bits", _p), ("chunk", _i), ("window", _i)]
 
 
 class GnbvEncoderParams(C.Structure):

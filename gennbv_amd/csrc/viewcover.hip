@@ -1,0 +1,287 @@
+// viewcover.hip -- view coverage of candidate camera poses against an env's ground truth, on MI355X.
+//
+// "Which ground-truth voxels would the env's voxel update mark if the camera of env e stood at pose p?"  (DESIGN.md "View
+// coverage, observable ground truth and the oracle planner"; include/gennbv_hip.h gnbv_view_cover has the exact definition.)
+// For env e, candidate j and the pixel lattice u = s/2 + i s, v = s/2 + j s: the pixel's ray is traced with the renderer's own
+// code (raytrace.h trace_pixel: the same bits as k_render_depth), a foreground hit is back-projected with the voxel update's
+// canonical chain (backproject.h process_depth, pixel_to_world) and mapped to its voxel with the update's keep test
+// (voxel.hip point_to_voxel, restated below with explicit _rn intrinsics).  No image is ever stored.
+//
+//   k_view_cover<WIN>   workgroup (env, chunk of candidates[, window of bit-set words]):
+//     1. 16 lanes build the camera matrices of the next 16 candidates (raytrace.h camera_of_pose: fp64 trig, off the
+//        per-candidate path);
+//     2. one wave per 8 x 8 tile of lattice pixels (ray coherence, as the renderer), one ray per lane;
+//     3. the seen set S is a bit set in LDS (G^3 / 8 bytes: 32 KiB at 64^3, 137 KiB at 104^3): atomicOr returns the old word,
+//        and the lane that set a bit first reads the env's gt and scanned words (L2-resident: an env's workgroups run on one
+//        XCD) and counts |S & gt| and |S & gt & ~scanned|;
+//     4. wave reductions -> per-wave partials in LDS -> lane 0 sums them in wave order and stores the three integers;
+//     5. seen_bits: the non-zero words of (bit set & gt) are OR-ed into global memory (device-scope atomicOr);
+//     6. the workgroup clears the bit set (16-byte stores) before the next candidate.  With cover == NULL (accumulate only)
+//        nothing is counted, the bit set is never cleared and it is flushed once, after the last candidate.
+//   WIN (G > 105: the bit set exceeds the 144 KiB a workgroup keeps for it): the words are split into windows as in
+//   k_hit_mask<.., WIN>; every window's workgroup traces all rays and keeps only its words.  The windows partition the voxels, so the per-window counts
+//   are added with int32 atomicAdd (k_vc_zero clears cover first): integer sums, the same bits in any order.  `hits` is
+//   counted by window 0 only.
+#include "common.h"
+#include "backproject.h"
+#include "raytrace.h"
+#include "../../include/gennbv_hip.h"
+
+namespace {
+
+constexpr int kTile = 8;            // 8 x 8 lattice pixels = one wave
+constexpr int kMaxThreads = 1024;
+constexpr int kMaxGrid = 128;
+constexpr int kCamBatch = 16;       // camera matrices built at a time
+constexpr size_t kLdsBitsMax = 144 * 1024;  // the bit set's share of the 160 KiB (static LDS: 1.2 KiB)
+
+struct VcParams {
+    GnbvMeshScene sc;
+    int n, k, g, chunk, chunks, windows, nw, vwords, words;
+    const float *poses, *range_gt, *voxel_size;
+    Intrinsics kinv;
+    int h, w, stride, nu, nv, tiles_x, tiles;
+    float sense_dist;
+    const uint32_t *gt, *scanned;
+    int32_t *cover;
+    uint32_t *seen;
+};
+
+struct CoverFrame {  // per-env constants of scanned_pts_to_idx_3D (voxel.hip load_frame)
+    float vmin[3], vmax[3], vox[3];
+};
+
+__device__ __forceinline__ CoverFrame load_cover_frame(const float *range6, const float *vox3)
+{
+    CoverFrame f;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float v = vox3[a];
+        const float half = __fmul_rn(0.5f, v);
+        f.vox[a] = v;
+        f.vmax[a] = __fadd_rn(range6[2 * a], half);
+        f.vmin[a] = __fsub_rn(range6[2 * a + 1], half);
+    }
+    return f;
+}
+
+// voxel.hip point_to_voxel: the linear voxel index (x*G + y)*G + z, or -1 when the point is dropped (strict bounds)
+__device__ __forceinline__ int cover_point_to_voxel(const float *p, const CoverFrame &f, int g)
+{
+    bool keep = true;
+    int ix[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float q = __fdiv_rn(__fsub_rn(p[a], f.vmin[a]), f.vox[a]);
+        const float fl = floorf(q);
+        keep = keep && (f.vmax[a] > p[a]) && (p[a] > f.vmin[a]);
+        int i = (fl == fl && fabsf(fl) < 1.0e9f) ? (int)fl : 0;
+        i = i < 0 ? 0 : (i > g - 1 ? g - 1 : i);
+        ix[a] = i;
+    }
+    return keep ? (ix[0] * g + ix[1]) * g + ix[2] : -1;
+}
+
+__global__ __launch_bounds__(256) void k_vc_zero(int32_t *cover, int64_t count)
+{
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < count) cover[t] = 0;
+}
+
+template <bool WIN>
+__global__ __launch_bounds__(kMaxThreads) void k_view_cover(VcParams p)
+{
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_bits[];
+    __shared__ float s_cam[kCamBatch][16];
+    __shared__ int s_part[kMaxThreads / kWave][3];
+
+    const int tid = threadIdx.x, nthreads = blockDim.x;
+    // XCD-aware block -> (env, chunk[, window]): all workgroups of an env run on one XCD (voxel.hip k_hit_mask)
+    const int b = blockIdx.x, xcd = b & 7, slot = b >> 3;
+    const int per_env = p.chunks * p.windows;
+    const int e = (slot / per_env) * 8 + xcd;
+    if (e >= p.n) return;
+    const int rem = slot % per_env, ch = rem % p.chunks, win = WIN ? rem / p.chunks : 0;
+    const int w0 = win * p.nw;                                  // first bit-set word of this workgroup
+    const int nw = WIN ? min(p.nw, p.vwords - w0) : p.vwords;   // a multiple of 4 (nw and vwords are)
+    const int j0 = ch * p.chunk, j1 = min(p.k, j0 + p.chunk);
+    const int g = p.g;
+
+    uint4 *s_bits4 = reinterpret_cast<uint4 *>(s_bits);
+    for (int i = tid; i < nw / 4; i += nthreads) s_bits4[i] = make_uint4(0u, 0u, 0u, 0u);
+
+    const CoverFrame f = load_cover_frame(p.range_gt + e * 6, p.voxel_size + e * 3);
+    const uint32_t *gt = p.gt + (size_t)e * p.words;
+    const uint32_t *scanned = p.scanned != nullptr ? p.scanned + (size_t)e * p.words : nullptr;
+    const bool count = p.cover != nullptr;
+    const int wave = tid / kWave, nwaves = nthreads / kWave, lane = tid & (kWave - 1);
+    const int half = p.stride / 2;
+
+    // (bit set & gt) -> seen_bits: the non-zero words, 16 bytes at a time; `clear` also empties the words a lane flushed
+    auto flush = [&](bool clear) {
+        uint32_t *out = p.seen + (size_t)e * p.words + w0;
+        for (int i = tid; i < nw / 4; i += nthreads) {
+            const uint4 s = s_bits4[i];
+            const uint4 t = *reinterpret_cast<const uint4 *>(gt + w0 + 4 * i);
+            if ((s.x & t.x) != 0u) atomicOr(&out[4 * i + 0], s.x & t.x);
+            if ((s.y & t.y) != 0u) atomicOr(&out[4 * i + 1], s.y & t.y);
+            if ((s.z & t.z) != 0u) atomicOr(&out[4 * i + 2], s.z & t.z);
+            if ((s.w & t.w) != 0u) atomicOr(&out[4 * i + 3], s.w & t.w);
+            if (clear) s_bits4[i] = make_uint4(0u, 0u, 0u, 0u);
+        }
+    };
+
+    for (int j = j0; j < j1; ++j) {
+        const int cslot = (j - j0) % kCamBatch;
+        if (cslot == 0) {
+            // ---- 1. cameras of the next kCamBatch candidates (the slots' last readers passed the barrier that ended j - 1)
+            if (tid < kCamBatch && j + tid < j1) camera_of_pose(p.poses + ((size_t)e * p.k + j + tid) * 6, s_cam[tid]);
+        }
+        __syncthreads();  // cameras ready; bit set clear
+
+        // ---- 2 / 3. one wave per tile of lattice pixels, one ray per lane
+        const float *M = s_cam[cslot];
+        int n_new = 0, n_seen = 0, n_hits = 0;
+        for (int tile = wave; tile < p.tiles; tile += nwaves) {
+            const int iu = (tile % p.tiles_x) * kTile + (lane & 7);
+            const int iv = (tile / p.tiles_x) * kTile + (lane >> 3);
+            if (iu >= p.nu || iv >= p.nv) continue;
+            const float fu = (float)(half + iu * p.stride), fv = (float)(half + iv * p.stride);
+            float best;
+            int obj;
+            trace_pixel(p.sc, e, M, p.kinv.k, fu, fv, best, obj);
+            if (obj <= 0) continue;  // the render's seg 0: the update's `seg > 50` drops the pixel
+            const float d = process_depth(-best, p.sense_dist);
+            float wp[3];
+            pixel_to_world(d, fu, fv, p.kinv, M, wp);
+            const int lin = cover_point_to_voxel(wp, f, g);
+            if (lin < 0) continue;
+            if (!WIN || win == 0) ++n_hits;
+            const unsigned wi = (unsigned)((lin >> 5) - w0);
+            if (wi >= (unsigned)nw) continue;  // another window's word
+            const uint32_t bit = 1u << (lin & 31);
+            const uint32_t old = atomicOr(&s_bits[wi], bit);
+            if (count && (old & bit) == 0u && (gt[lin >> 5] & bit) != 0u) {
+                ++n_seen;
+                if (scanned == nullptr || (scanned[lin >> 5] & bit) == 0u) ++n_new;
+            }
+        }
+
+        // ---- 4. the three sums, in wave order
+        if (count) {
+            n_new = wave_reduce_sum(n_new);
+            n_seen = wave_reduce_sum(n_seen);
+            n_hits = wave_reduce_sum(n_hits);
+            if (lane == 0) {
+                s_part[wave][0] = n_new;
+                s_part[wave][1] = n_seen;
+                s_part[wave][2] = n_hits;
+            }
+        }
+        __syncthreads();  // every ray of candidate j is done: partials and bit set complete, camera slot free
+        if (!count) continue;  // accumulate only: the bit set keeps growing
+        if (tid == 0) {
+            int a = 0, c = 0, d = 0;
+            for (int w = 0; w < nwaves; ++w) {
+                a += s_part[w][0];
+                c += s_part[w][1];
+                d += s_part[w][2];
+            }
+            int32_t *o = p.cover + ((size_t)e * p.k + j) * 3;
+            if (WIN) {
+                if (a != 0) atomicAdd(o, a);
+                if (c != 0) atomicAdd(o + 1, c);
+                if (d != 0) atomicAdd(o + 2, d);
+            } else {
+                o[0] = a; o[1] = c; o[2] = d;
+            }
+        }
+        // ---- 5 / 6. flush, then clear for the next candidate (a lane clears the words it flushed: no barrier between the
+        //      two; the clear is ordered in front of the next rays by the barrier at the loop's head; lane 0 reads s_part
+        //      before it arrives there, the waves write it after)
+        if (p.seen != nullptr) {
+            flush(true);
+        } else if (j + 1 < j1) {
+            for (int i = tid; i < nw / 4; i += nthreads) s_bits4[i] = make_uint4(0u, 0u, 0u, 0u);
+        }
+    }
+    if (!count) flush(false);  // (the barrier that ended the last candidate completed the bit set)
+}
+
+}  // namespace
+
+GNBV_API int gnbv_view_cover(const GnbvMeshScene *scene, const GnbvViewCover *args, void *stream)
+{
+    GNBV_CHECK_ARG(scene != nullptr && args != nullptr);
+    const GnbvViewCover a = *args;
+    const GnbvMeshScene sc = *scene;
+    GNBV_CHECK_ARG(a.n > 0 && a.n <= 65535 && sc.n == a.n && a.k >= 1 && a.g >= 2 && a.g <= kMaxGrid && a.stride >= 1);
+    GNBV_CHECK_ARG(a.h > 0 && a.w > 0 && a.h <= 32768 && a.w <= 32768 && a.chunk >= 0 && a.window >= 0);
+    GNBV_CHECK_ARG(a.poses != nullptr && a.range_gt != nullptr && a.voxel_size != nullptr && a.inv_intri != nullptr && a.gt_bits != nullptr);
+    GNBV_CHECK_ARG(a.cover != nullptr || a.seen_bits != nullptr);
+    GNBV_CHECK_ARG(sc.cell_lo != nullptr && sc.cell_size != nullptr && sc.cell_res != nullptr && sc.cell_base != nullptr);
+    GNBV_CHECK_ARG(sc.cell_start != nullptr);  // tris / tri_obj / cell_tris may be NULL when no env has a triangle
+    GNBV_CHECK_ARG((((uintptr_t)a.gt_bits | (uintptr_t)a.scanned_bits | (uintptr_t)a.seen_bits) & 15) == 0);
+    VcParams p;
+    p.sc = sc;
+    p.n = a.n; p.k = a.k; p.g = a.g;
+    const int g3 = a.g * a.g * a.g;
+    p.words = gnbv_grid_bit_words(a.g);             // the updater's row length (a multiple of 64 words)
+    p.vwords = (((g3 + 31) / 32) + 3) & ~3;         // the words that hold voxels, to 16 bytes (<= words)
+    // windows: the fewest equal windows whose words fit the LDS; a requested window is kept if it fits
+    int nw = a.window;
+    if (nw == 0) {
+        const int wins = (int)(((size_t)p.vwords * 4 + kLdsBitsMax - 1) / kLdsBitsMax);
+        nw = (p.vwords + wins - 1) / wins;
+    }
+    nw = (nw + 3) & ~3;
+    if ((size_t)nw * 4 > kLdsBitsMax) nw = (int)(kLdsBitsMax / 4);
+    if (nw > p.vwords) nw = p.vwords;
+    p.nw = nw;
+    p.windows = (p.vwords + nw - 1) / nw;
+    // candidates per workgroup: two workgroups per compute unit when n allows it; the cameras and the frame are built per workgroup
+    int chunk = a.chunk;
+    if (chunk == 0) {
+        const int want = (512 + a.n * p.windows - 1) / (a.n * p.windows);  // chunks per env
+        chunk = (a.k + want - 1) / want;
+    }
+    chunk = chunk < 1 ? 1 : (chunk > a.k ? a.k : chunk);
+    p.chunk = chunk;
+    p.chunks = (a.k + chunk - 1) / chunk;
+    const int64_t blocks = (int64_t)((a.n + 7) / 8 * 8) * p.chunks * p.windows;
+    GNBV_CHECK_ARG(blocks <= 0x7fffffff);
+    p.poses = a.poses; p.range_gt = a.range_gt; p.voxel_size = a.voxel_size;
+    for (int i = 0; i < 9; ++i) p.kinv.k[i] = a.inv_intri[i];
+    p.h = a.h; p.w = a.w; p.stride = a.stride;
+    const int half = a.stride / 2;
+    p.nu = half < a.w ? (a.w - half + a.stride - 1) / a.stride : 0;
+    p.nv = half < a.h ? (a.h - half + a.stride - 1) / a.stride : 0;
+    p.tiles_x = (p.nu + kTile - 1) / kTile;
+    p.tiles = p.tiles_x * ((p.nv + kTile - 1) / kTile);
+    p.sense_dist = a.depth_sense_dist;
+    p.gt = reinterpret_cast<const uint32_t *>(a.gt_bits);
+    p.scanned = reinterpret_cast<const uint32_t *>(a.scanned_bits);
+    p.cover = a.cover;
+    p.seen = reinterpret_cast<uint32_t *>(a.seen_bits);
+    const size_t lds = (size_t)nw * sizeof(uint32_t);
+    int threads = (p.tiles > 0 ? p.tiles : 1) * kWave;
+    threads = threads > kMaxThreads ? kMaxThreads : threads;
+    hipStream_t st = gnbv_stream(stream);
+    if (p.windows > 1) {
+        if (a.cover != nullptr) {
+            const int64_t cnt = (int64_t)a.n * a.k * 3;
+            hipLaunchKernelGGL(k_vc_zero, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, a.cover, cnt);
+        }
+        // (per call: the attribute belongs to the current device's copy of the kernel)
+        if (lds > 64 * 1024 &&
+            hipFuncSetAttribute((const void *)k_view_cover<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+            return (int)hipGetLastError();
+        hipLaunchKernelGGL(k_view_cover<true>, dim3((unsigned)blocks), dim3(threads), lds, st, p);
+    } else {
+        if (lds > 64 * 1024 &&
+            hipFuncSetAttribute((const void *)k_view_cover<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+            return (int)hipGetLastError();
+        hipLaunchKernelGGL(k_view_cover<false>, dim3((unsigned)blocks), dim3(threads), lds, st, p);
+    }
+    return gnbv_launch_status();
+}

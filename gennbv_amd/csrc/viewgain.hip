@@ -27,6 +27,7 @@
 
 #include "common.h"
 #include "backproject.h"
+#include "raytrace.h"  // camera_of_pose: k_render_camera's arithmetic (fp64 trig rounded to fp32, roll ignored)
 #include "../../include/gennbv_hip.h"
 
 namespace {
@@ -173,20 +174,6 @@ __device__ __forceinline__ uint32_t pack_codes4(uint32_t bytes4)
         code |= (t > 0 ? 1u : (t < 0 ? 3u : 0u)) << (2 * b);
     }
     return code;
-}
-
-// the camera matrix of pose q (k_render_camera's arithmetic: fp64 trig rounded to fp32, roll ignored; -ffp-contract=off)
-__device__ __forceinline__ void camera_of_pose(const float *q, float *m)
-{
-    const double pitch = (double)q[4], yaw = (double)q[5];
-    const double cp = cos(pitch), sp = sin(pitch), cy = cos(yaw), sy = sin(yaw);
-    const double fx = cp * cy, fy = cp * sy, fz = -sp;
-    const double rx = sy, ry = -cy, rz = 0.0;
-    const double dx = fy * rz - fz * ry, dy = fz * rx - fx * rz, dz = fx * ry - fy * rx;
-    m[0] = (float)rx; m[1] = (float)dx; m[2] = (float)fx; m[3] = q[0];
-    m[4] = (float)ry; m[5] = (float)dy; m[6] = (float)fy; m[7] = q[1];
-    m[8] = (float)rz; m[9] = (float)dz; m[10] = (float)fz; m[11] = q[2];
-    m[12] = 0.f; m[13] = 0.f; m[14] = 0.f; m[15] = 1.f;
 }
 
 // word w of a row's 2-bit codes: voxels 16 w .. 16 w + 15 (0 past the row's end)

@@ -14,7 +14,8 @@ and at most MAX_CELLS_PER_AXIS.  A box scene (<= 96 triangles) gets a few hundre
 100 k.
 
 Ground truth comes from the same triangles: `ground_truth` voxelizes the surface with gnbv_voxelize_surface
-(csrc/voxelize.hip) under the updater's own voxel bounds, so the coverage reward can reach 1; `surface_points` samples
+(csrc/voxelize.hip) under the updater's own voxel bounds; `observable_ground_truth` restricts it to the voxels a camera
+can see (gnbv_view_cover, csrc/viewcover.hip), so the coverage reward can reach 1; `surface_points` samples
 the GT point cloud of the evaluation env.  env/mesh_io.py reads Wavefront OBJ files.
 
 Collision termination uses the same triangles as closed solids: `objects` indexes them per (env, object id) -- the
@@ -327,6 +328,60 @@ class MeshScene:
         self.voxelize_into(grid, rng_d, vox_d)
         empty = torch.zeros(n, 0, 3, dtype=torch.float32, device=dev)
         return S.Scene(empty, empty.clone(), grid, rng_d, vox_d, grid.sum(dim=(1, 2, 3)).clamp(min=1.0), env_origins.contiguous())
+
+    def observable_ground_truth(self, grid_size: int, poses: torch.Tensor, cfg, range_gt: Optional[torch.Tensor] = None,
+                                base: Optional[S.Scene] = None, inv_intrinsics: Optional[torch.Tensor] = None,
+                                env_origins: Optional[torch.Tensor] = None, batch: int = 64) -> S.Scene:
+        """The ground truth a camera can see: `base` (a synthetic.Scene to restrict, e.g. make_scenes' own GT; default
+        `self.ground_truth(grid_size, range_gt, env_origins)`; with `base` the voxel frame is base's and `range_gt` is refused) with grid_gt = base.grid_gt AND (voxels the voxel update
+        marks from at least one of poses [N,K,6] f32, env-local, at stride 1 with cfg's camera: gnbv_view_cover's seen
+        set); num_valid_voxel_gt = its count (at least 1); everything else as in `base`.  Surface voxels no camera
+        reaches -- faces lying on the ground, faces buried in another object, the insides of closed shells -- leave the
+        coverage denominator, so a perfect planner's coverage is 1.  This is a LOWER BOUND of the truly observable set
+        that grows with the view set: a voxel only seen from a pose outside `poses` is dropped.  The intended view set is
+        eval.baselines.LatticeCandidates(cfg, k, seed, look_at_scene=True) with a few hundred views per env.  K may be
+        large: the candidates run in batches of `batch`.  On the GPU only."""
+        import dataclasses
+
+        from ..ops.view_cover import ViewCover
+        g, n, dev = int(grid_size), self.num_envs, self.device
+        if dev.type != "cuda":
+            raise _lib.GennbvHipError("MeshScene.observable_ground_truth runs on the GPU only (no CPU fallback): "
+                                      "build the MeshScene on a cuda device")
+        if base is None:
+            base = self.ground_truth(g, range_gt, env_origins)
+        elif range_gt is not None:
+            raise ValueError("observable_ground_truth: pass either base (its own range_gt / voxel_size are used) or range_gt, not both")
+        grid = base.grid_gt.to(dev, torch.float32).contiguous()
+        if grid.shape != (n, g, g, g):
+            raise ValueError(f"base.grid_gt must be [{n}, {g}, {g}, {g}], got {tuple(grid.shape)}")
+        poses = torch.as_tensor(poses).to(dev, torch.float32)
+        if poses.dim() != 3 or poses.shape[0] != n or poses.shape[2] != 6 or poses.shape[1] < 1:
+            raise ValueError(f"poses must be [{n}, K, 6] with K >= 1, got {tuple(poses.shape)}")
+        if int(cfg.grid_size) != g:
+            cfg = dataclasses.replace(cfg, grid_size=g)
+        rng_d = base.range_gt.to(dev, torch.float32).contiguous()  # the frame is base's, whole
+        vox_d = base.voxel_size.to(dev, torch.float32).contiguous()
+        lib, st = _lib.load(), _lib.stream_ptr(dev)
+        words = int(lib.gnbv_grid_bit_words(g))
+        gt_bits = torch.zeros(n, words, dtype=torch.int32, device=dev)
+        flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        _lib.check(lib.gnbv_pack_grid_bits(grid.data_ptr(), n, g, gt_bits.data_ptr(), flag.data_ptr(), st), "gnbv_pack_grid_bits")
+        if int(flag.item()) != 0:
+            raise ValueError("observable_ground_truth needs a binary base.grid_gt (0 / 1)")
+        seen = torch.zeros_like(gt_bits)
+        k, batch = int(poses.shape[1]), max(1, int(batch))
+        ops = {}
+        for j0 in range(0, k, batch):
+            kb = min(batch, k - j0)
+            if kb not in ops:
+                ops[kb] = ViewCover(self, cfg, rng_d, vox_d, kb, stride=1, inv_intrinsics=inv_intrinsics, device=dev)
+            ops[kb].accumulate(poses[:, j0:j0 + kb].contiguous(), gt_bits, seen)
+        out = torch.empty_like(grid)
+        _lib.check(lib.gnbv_unpack_grid_bits(seen.data_ptr(), n, g, out.data_ptr(), st), "gnbv_unpack_grid_bits")
+        origins = base.env_origins if env_origins is None else torch.as_tensor(env_origins)
+        return S.Scene(base.boxes_min.to(dev), base.boxes_max.to(dev), out, rng_d, vox_d, out.sum(dim=(1, 2, 3)).clamp(min=1.0),
+                       origins.to(dev, torch.float32).contiguous())
 
     def voxelize_into(self, grid_out: torch.Tensor, range_gt: torch.Tensor, voxel_size: torch.Tensor) -> torch.Tensor:
         """gnbv_voxelize_surface on the current stream: grid_out [N,G,G,G] f32 (every voxel written), range_gt [N,6] and

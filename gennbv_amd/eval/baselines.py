@@ -1,7 +1,9 @@
-"""Baseline view planners to compare a learned policy against: a uniformly random lattice pose and the greedy
-next-best-view planner over the view gain (ops/view_gain.py, csrc/viewgain.hip; grids up to 128^3).
+"""Baseline view planners to compare a learned policy against: a uniformly random lattice pose, the greedy
+next-best-view planner over the view gain (ops/view_gain.py, csrc/viewgain.hip; grids up to 128^3) and the one-step
+oracle over the view coverage (ops/view_cover.py, csrc/viewcover.hip): the candidate that really adds the most
+ground-truth voxels.
 
-Both speak the protocol `evaluate_policy_grid_obs` uses: `.policy(obs, deterministic=True) -> (actions, None, None)`,
+All speak the protocol `evaluate_policy_grid_obs` uses: `.policy(obs, deterministic=True) -> (actions, None, None)`,
 and `predict(obs)`; actions are int64 [N,6] on the lattice of the task (inside clip_pose_idx_low / clip_pose_idx_up).
 """
 from __future__ import annotations
@@ -116,6 +118,66 @@ class GreedyGainPolicy:
                     mesh.collide(poses[:, j], self.env.collision, out=self._contact[j])
                 contact = self._contact.t()
         best = choose(gain, self.weights, contact)
+        return cand[torch.arange(n, device=cand.device), best], None, None
+
+    @property
+    def policy(self):
+        return self
+
+    def predict(self, obs, state=None, episode_start=None, deterministic: bool = True):
+        return self(obs, deterministic)[0], state
+
+
+class OracleGainPolicy:
+    """One-step oracle, the upper baseline beside GreedyGainPolicy: K random lattice candidates per env and step, and the
+    one whose view really adds the most ground-truth voxels to the scanned set wins -- new_gt of the view coverage
+    (ops/view_cover.py) of the env's own scene (`env.feed.mesh`), ground truth and scanned set (`env.updater.gt_bits`,
+    `.scanned_bits`), i.e. at stride 1 exactly the coverage_count increment the env pays for the step.  It reads the scene
+    geometry and the ground truth, which no deployable planner has.  Ties go to the lowest candidate index; with a
+    CollisionBody on the env (and `avoid_collisions`) candidates whose pose collides are never chosen unless all do.
+    `last_cover` [N,K,3] keeps the last decision's integers.  No host synchronisation inside a decision.  It needs the
+    packed updater (a binary ground truth) and a closed-loop feed with a mesh; anything else is refused.
+    `cover_backend(poses [N,K,6], gt_bits, scanned_bits) -> cover [N,K,3]` replaces the kernel in tests only: the product
+    path has no CPU fallback.
+
+    On a step whose env is done the env resets, and the next step forces the init action whatever is chosen: the choice
+    for that env is moot, and its new_gt (computed against the finished episode's scanned set) is not what the step pays."""
+
+    def __init__(self, env, k: int = 32, seed: int = 0, stride: int = 1, avoid_collisions: bool = True,
+                 look_at_scene: bool = False, cover_backend: Optional[Callable] = None):
+        from .. import _lib
+        cfg = env.cfg
+        self.env, self.cfg, self.k = env, cfg, int(k)
+        self.num_envs = int(env.num_envs)
+        self.cands = LatticeCandidates(cfg, k, seed, look_at_scene)
+        self.avoid_collisions = bool(avoid_collisions) and getattr(env, "collision", None) is not None
+        u = env.updater
+        if not getattr(u, "packed", False):
+            raise _lib.GennbvHipError("OracleGainPolicy needs the packed updater (a binary ground truth: gt_bits / scanned_bits)")
+        if cover_backend is None:
+            mesh = getattr(env.feed, "mesh", None)
+            if mesh is None:
+                raise _lib.GennbvHipError("OracleGainPolicy needs the scene's mesh (a closed-loop RenderFeed): env.feed has none")
+            from ..ops.view_cover import ViewCover
+            cover_backend = ViewCover(mesh, cfg, u.range_gt, u.voxel_size_gt, self.k, stride=stride, inv_intrinsics=u.inv_intri_host,
+                                      device=env.device)
+        self.cover_backend = cover_backend
+        self._contact = None
+        self.last_cover = None
+
+    def __call__(self, obs, deterministic: bool = True):
+        n, k = self.num_envs, self.k
+        cand = self.cands.sample(n, obs.device)
+        poses = self.cands.poses(cand)
+        u = self.env.updater
+        cover = self.cover_backend(poses, u.gt_bits, u.scanned_bits)
+        self.last_cover = cover
+        contact = None
+        if self.avoid_collisions:
+            if self._contact is None:
+                self._contact = torch.zeros(n, k, dtype=torch.uint8, device=obs.device)
+            contact = self.env.collision_mesh.collide_candidates(poses, self.env.collision, out=self._contact)
+        best = choose(cover, (1, 0), contact)
         return cand[torch.arange(n, device=cand.device), best], None, None
 
     @property

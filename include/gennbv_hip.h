@@ -748,6 +748,50 @@ int gnbv_view_gain(const GnbvViewGain *args /*[host]*/, void *stream);
 size_t gnbv_view_gain_slab_workspace_bytes(int n, int k, int g, int h, int w, int stride);
 int gnbv_view_gain_slab(const GnbvViewGain *args /*[host]*/, int slab, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------------------- */
+/* View coverage (a new entry point of ABI 5): which ground-truth voxels would  */
+/* the voxel update mark if env e's camera stood at candidate pose j?  The      */
+/* renderer's trace and the update's back-projection, fused: no image is stored. */
+/* ------------------------------------------------------------------------- */
+/* For env e of `scene`, candidate pose (x, y, z, roll, pitch, yaw), env-local, and the pixel-lattice step `stride`:
+ *   - c2w = gnbv_render_depth's camera matrix of the pose, bit for bit (fp64 trig rounded to fp32, roll ignored);
+ *   - pixels u = stride/2 + i stride < w, v = stride/2 + j stride < h (integer division, as gnbv_view_gain); stride 1 is every pixel;
+ *   - the pixel's (depth_raw, seg_raw) is exactly what gnbv_render_depth writes for that env, camera and pixel (one shared
+ *     trace: csrc/raytrace.h); the pixel is foreground iff it hits an object (seg 255, the update's seg > 50);
+ *   - a foreground pixel's world point is the update's: the depth clamp of gnbv_post_process_depth with depth_sense_dist, the
+ *     canonical fp32 chain of gnbv_back_projection; it is kept under gnbv_points_to_idx's strict bounds and mapped to its
+ *     voxel floor(RN((p - vmin) / v)) clamped to [0, g-1];
+ *   - S(e, j) = the distinct voxels of the kept foreground points.  At stride 1 with the env's own h, w, inverse intrinsics
+ *     and sense distance, S is exactly the hit mask gnbv_update_occ_grid* forms from that view, and S & gt & ~scanned is
+ *     exactly what it adds to scanned_bits.
+ * cover[e, j] = { |S & gt & ~scanned|, |S & gt|, kept foreground lattice pixels }: integers with one right answer, every
+ * element written on every call.  seen_bits[e] |= S & gt over all k candidates (device-scope atomicOr of the non-zero words;
+ * the caller zeroes it, or keeps accumulating).  The bit layout is gnbv_pack_grid_bits' (bit v = voxel (x*g+y)*g+z, rows of
+ * gnbv_grid_bit_words(g) words, 16-byte aligned).  One workgroup per (env, chunk of candidates) keeps S in LDS (g <= 105:
+ * up to 144 KiB); above, the words are split into windows of `window` words and the per-window counts are added with int32
+ * atomicAdd after a zeroing launch -- integer sums, so the result depends neither on `chunk` nor on `window`.  Deterministic.  No host
+ * synchronisation, no allocation, no workspace.
+ * Returns hipErrorInvalidValue for g outside 2..128, n outside 1..65535, stride < 1, k < 1, h or w outside 1..32768, chunk or window < 0, cover
+ * and seen_bits both NULL, a NULL required pointer (scene, poses, range_gt, voxel_size, inv_intri, gt_bits, the scene's cell
+ * arrays), a misaligned bit row, or scene->n != n.  [host struct]; pointers are device unless noted. */
+typedef struct GnbvViewCover {
+    int n, k, g;                    /* envs (== scene->n), candidates per env, grid edge */
+    const float *poses;             /* [n, k, 6] contiguous */
+    const float *range_gt;          /* [n, 6] */
+    const float *voxel_size;        /* [n, 3] */
+    const float *inv_intri;         /* [host] [3,3] the updater's inverse intrinsics */
+    int h, w, stride;               /* camera and the pixel lattice's step */
+    float depth_sense_dist;         /* the updater's (negative: depth_raw is clamped from below), e.g. -50 */
+    const int32_t *gt_bits;         /* [n, words], words = gnbv_grid_bit_words(g) */
+    const int32_t *scanned_bits;    /* [n, words], or NULL = nothing scanned */
+    int32_t *cover;                 /* [n, k, 3] (new_gt, seen_gt, hits), or NULL */
+    int32_t *seen_bits;             /* [n, words], or NULL */
+    int chunk;                      /* candidates per workgroup, 0 = chosen from n and k (any value gives the same result) */
+    int window;                     /* bit-set words per workgroup, 0 = chosen from g (the fewest windows that fit the LDS; any
+                                     * value gives the same result; rounded up to 4, reduced to what fits) */
+} GnbvViewCover;
+int gnbv_view_cover(const GnbvMeshScene *scene /*[host]*/, const GnbvViewCover *args /*[host]*/, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
