@@ -102,6 +102,8 @@ SIGNATURES = {
     "gnbv_view_gain_slab_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "gnbv_view_gain_slab": (_i, [_p, _i, _p, _sz, _p]),
     "gnbv_view_cover": (_i, [_p, _p, _p]),
+    "gnbv_view_cover_masks": (_i, [_p, _p, _p, _p]),
+    "gnbv_cover_greedy": (_i, [_p, _p]),
     "gnbv_gae_sb3": (_i, [_p, _p, _p, _p, _p, _i, _i, _d, _d, _p, _p, _p]),
     "gnbv_gae_rsl": (_i, [_p, _p, _p, _p, _i, _i, _d, _d, _p, _p, _p]),
 }
@@ -158,6 +160,12 @@ class GnbvViewCover(C.Structure):
     _fields_ = [("n", _i), ("k", _i), ("g", _i), ("poses", _p), ("range_gt", _p), ("voxel_size", _p), ("inv_intri", _p),
                 ("h", _i), ("w", _i), ("stride", _i), ("depth_sense_dist", _f), ("gt_bits", _p), ("scanned_bits", _p),
                 ("cover", _p), ("seen_bits", _p), ("chunk", _i), ("window", _i)]
+
+
+class GnbvCoverGreedy(C.Structure):
+    """include/gennbv_hip.h: GnbvCoverGreedy"""
+    _fields_ = [("n", _i), ("k", _i), ("words", _i), ("rounds", _i), ("mask_bits", _p), ("covered_in", _p), ("contact", _p),
+                ("choice", _p), ("gain", _p), ("covered_out", _p), ("gains0", _p), ("ub", _p), ("lazy", _i)]
 
 
 class GnbvEncoderParams(C.Structure):

@@ -22,6 +22,9 @@
 //   k_hit_mask<.., WIN>; every window's workgroup traces all rays and keeps only its words.  The windows partition the voxels, so the per-window counts
 //   are added with int32 atomicAdd (k_vc_zero clears cover first): integer sums, the same bits in any order.  `hits` is
 //   counted by window 0 only.
+//   MASK (gnbv_view_cover_masks): step 5 also stores (bit set & gt) as the workgroup's words of the candidate's mask row, plain
+//   16-byte stores (the workgroup owns those words: no atomics, no zeroing launch), the zero words included; the workgroup of
+//   the last window stores the row's pad words.  The bit set is cleared after every candidate, with or without `cover`.
 #include "common.h"
 #include "backproject.h"
 #include "raytrace.h"
@@ -45,6 +48,7 @@ struct VcParams {
     const uint32_t *gt, *scanned;
     int32_t *cover;
     uint32_t *seen;
+    uint32_t *mask;  // [n, k, words], read by the MASK instantiations only
 };
 
 struct CoverFrame {  // per-env constants of scanned_pts_to_idx_3D (voxel.hip load_frame)
@@ -88,7 +92,7 @@ __global__ __launch_bounds__(256) void k_vc_zero(int32_t *cover, int64_t count)
     if (t < count) cover[t] = 0;
 }
 
-template <bool WIN>
+template <bool WIN, bool MASK>
 __global__ __launch_bounds__(kMaxThreads) void k_view_cover(VcParams p)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t s_bits[];
@@ -179,8 +183,8 @@ __global__ __launch_bounds__(kMaxThreads) void k_view_cover(VcParams p)
             }
         }
         __syncthreads();  // every ray of candidate j is done: partials and bit set complete, camera slot free
-        if (!count) continue;  // accumulate only: the bit set keeps growing
-        if (tid == 0) {
+        if (!count && !MASK) continue;  // accumulate only: the bit set keeps growing
+        if (count && tid == 0) {
             int a = 0, c = 0, d = 0;
             for (int w = 0; w < nwaves; ++w) {
                 a += s_part[w][0];
@@ -199,18 +203,62 @@ __global__ __launch_bounds__(kMaxThreads) void k_view_cover(VcParams p)
         // ---- 5 / 6. flush, then clear for the next candidate (a lane clears the words it flushed: no barrier between the
         //      two; the clear is ordered in front of the next rays by the barrier at the loop's head; lane 0 reads s_part
         //      before it arrives there, the waves write it after)
-        if (p.seen != nullptr) {
+        if (MASK) {
+            // the candidate's mask row: this workgroup owns words [w0, w0 + nw) of it, every one is stored
+            uint32_t *row = p.mask + ((size_t)e * p.k + j) * p.words;
+            uint32_t *out = p.seen != nullptr ? p.seen + (size_t)e * p.words + w0 : nullptr;
+            for (int i = tid; i < nw / 4; i += nthreads) {
+                const uint4 s = s_bits4[i];
+                const uint4 t = *reinterpret_cast<const uint4 *>(gt + w0 + 4 * i);
+                const uint4 m = make_uint4(s.x & t.x, s.y & t.y, s.z & t.z, s.w & t.w);
+                *reinterpret_cast<uint4 *>(row + w0 + 4 * i) = m;
+                if (out != nullptr) {
+                    if (m.x != 0u) atomicOr(&out[4 * i + 0], m.x);
+                    if (m.y != 0u) atomicOr(&out[4 * i + 1], m.y);
+                    if (m.z != 0u) atomicOr(&out[4 * i + 2], m.z);
+                    if (m.w != 0u) atomicOr(&out[4 * i + 3], m.w);
+                }
+                s_bits4[i] = make_uint4(0u, 0u, 0u, 0u);
+            }
+            if (w0 + nw == p.vwords)  // the pad words past the voxels (words - vwords is a multiple of 4)
+                for (int i = tid; i < (p.words - p.vwords) / 4; i += nthreads)
+                    *reinterpret_cast<uint4 *>(row + p.vwords + 4 * i) = make_uint4(0u, 0u, 0u, 0u);
+        } else if (p.seen != nullptr) {
             flush(true);
         } else if (j + 1 < j1) {
             for (int i = tid; i < nw / 4; i += nthreads) s_bits4[i] = make_uint4(0u, 0u, 0u, 0u);
         }
     }
-    if (!count) flush(false);  // (the barrier that ended the last candidate completed the bit set)
+    if (!count && !MASK) flush(false);  // (the barrier that ended the last candidate completed the bit set)
 }
 
 }  // namespace
 
+template <bool WIN, bool MASK>
+static int launch_view_cover(const VcParams &p, unsigned blocks, int threads, size_t lds, hipStream_t st)
+{
+    // (per call: the attribute belongs to the current device's copy of the kernel)
+    if (lds > 64 * 1024 &&
+        hipFuncSetAttribute((const void *)k_view_cover<WIN, MASK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        return (int)hipGetLastError();
+    hipLaunchKernelGGL((k_view_cover<WIN, MASK>), dim3(blocks), dim3(threads), lds, st, p);
+    return gnbv_launch_status();
+}
+
+// gnbv_view_cover (mask_bits == NULL, with_masks false) and gnbv_view_cover_masks
+static int view_cover_impl(const GnbvMeshScene *scene, const GnbvViewCover *args, int32_t *mask_bits, bool with_masks, void *stream);
+
 GNBV_API int gnbv_view_cover(const GnbvMeshScene *scene, const GnbvViewCover *args, void *stream)
+{
+    return view_cover_impl(scene, args, nullptr, false, stream);
+}
+
+GNBV_API int gnbv_view_cover_masks(const GnbvMeshScene *scene, const GnbvViewCover *args, int32_t *mask_bits, void *stream)
+{
+    return view_cover_impl(scene, args, mask_bits, true, stream);
+}
+
+static int view_cover_impl(const GnbvMeshScene *scene, const GnbvViewCover *args, int32_t *mask_bits, bool with_masks, void *stream)
 {
     GNBV_CHECK_ARG(scene != nullptr && args != nullptr);
     const GnbvViewCover a = *args;
@@ -218,7 +266,10 @@ GNBV_API int gnbv_view_cover(const GnbvMeshScene *scene, const GnbvViewCover *ar
     GNBV_CHECK_ARG(a.n > 0 && a.n <= 65535 && sc.n == a.n && a.k >= 1 && a.g >= 2 && a.g <= kMaxGrid && a.stride >= 1);
     GNBV_CHECK_ARG(a.h > 0 && a.w > 0 && a.h <= 32768 && a.w <= 32768 && a.chunk >= 0 && a.window >= 0);
     GNBV_CHECK_ARG(a.poses != nullptr && a.range_gt != nullptr && a.voxel_size != nullptr && a.inv_intri != nullptr && a.gt_bits != nullptr);
-    GNBV_CHECK_ARG(a.cover != nullptr || a.seen_bits != nullptr);
+    if (with_masks)
+        GNBV_CHECK_ARG(mask_bits != nullptr && ((uintptr_t)mask_bits & 15) == 0);
+    else
+        GNBV_CHECK_ARG(a.cover != nullptr || a.seen_bits != nullptr);
     GNBV_CHECK_ARG(sc.cell_lo != nullptr && sc.cell_size != nullptr && sc.cell_res != nullptr && sc.cell_base != nullptr);
     GNBV_CHECK_ARG(sc.cell_start != nullptr);  // tris / tri_obj / cell_tris may be NULL when no env has a triangle
     GNBV_CHECK_ARG((((uintptr_t)a.gt_bits | (uintptr_t)a.scanned_bits | (uintptr_t)a.seen_bits) & 15) == 0);
@@ -263,6 +314,7 @@ GNBV_API int gnbv_view_cover(const GnbvMeshScene *scene, const GnbvViewCover *ar
     p.scanned = reinterpret_cast<const uint32_t *>(a.scanned_bits);
     p.cover = a.cover;
     p.seen = reinterpret_cast<uint32_t *>(a.seen_bits);
+    p.mask = reinterpret_cast<uint32_t *>(mask_bits);
     const size_t lds = (size_t)nw * sizeof(uint32_t);
     int threads = (p.tiles > 0 ? p.tiles : 1) * kWave;
     threads = threads > kMaxThreads ? kMaxThreads : threads;
@@ -272,16 +324,9 @@ GNBV_API int gnbv_view_cover(const GnbvMeshScene *scene, const GnbvViewCover *ar
             const int64_t cnt = (int64_t)a.n * a.k * 3;
             hipLaunchKernelGGL(k_vc_zero, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, a.cover, cnt);
         }
-        // (per call: the attribute belongs to the current device's copy of the kernel)
-        if (lds > 64 * 1024 &&
-            hipFuncSetAttribute((const void *)k_view_cover<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return (int)hipGetLastError();
-        hipLaunchKernelGGL(k_view_cover<true>, dim3((unsigned)blocks), dim3(threads), lds, st, p);
-    } else {
-        if (lds > 64 * 1024 &&
-            hipFuncSetAttribute((const void *)k_view_cover<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return (int)hipGetLastError();
-        hipLaunchKernelGGL(k_view_cover<false>, dim3((unsigned)blocks), dim3(threads), lds, st, p);
+        return with_masks ? launch_view_cover<true, true>(p, (unsigned)blocks, threads, lds, st)
+                          : launch_view_cover<true, false>(p, (unsigned)blocks, threads, lds, st);
     }
-    return gnbv_launch_status();
+    return with_masks ? launch_view_cover<false, true>(p, (unsigned)blocks, threads, lds, st)
+                      : launch_view_cover<false, false>(p, (unsigned)blocks, threads, lds, st);
 }

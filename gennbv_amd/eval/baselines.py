@@ -1,7 +1,8 @@
 """Baseline view planners to compare a learned policy against: a uniformly random lattice pose, the greedy
-next-best-view planner over the view gain (ops/view_gain.py, csrc/viewgain.hip; grids up to 128^3) and the one-step
+next-best-view planner over the view gain (ops/view_gain.py, csrc/viewgain.hip; grids up to 128^3), the one-step
 oracle over the view coverage (ops/view_cover.py, csrc/viewcover.hip): the candidate that really adds the most
-ground-truth voxels.
+ground-truth voxels, and the greedy set-cover planner over a fixed pool of views whose visible ground truth is cached
+as bit masks (ops/view_pool.py, csrc/covergreedy.hip).
 
 All speak the protocol `evaluate_policy_grid_obs` uses: `.policy(obs, deterministic=True) -> (actions, None, None)`,
 and `predict(obs)`; actions are int64 [N,6] on the lattice of the task (inside clip_pose_idx_low / clip_pose_idx_up).
@@ -179,6 +180,68 @@ class OracleGainPolicy:
             contact = self.env.collision_mesh.collide_candidates(poses, self.env.collision, out=self._contact)
         best = choose(cover, (1, 0), contact)
         return cand[torch.arange(n, device=cand.device), best], None, None
+
+    @property
+    def policy(self):
+        return self
+
+    def predict(self, obs, state=None, episode_start=None, deterministic: bool = True):
+        return self(obs, deterministic)[0], state
+
+
+class PoolCoverPolicy:
+    """Greedy set cover over a FIXED pool of views, the third upper baseline: `pool_size` lattice candidates per env are drawn
+    once (`LatticeCandidates(cfg, pool_size, seed, look_at_scene).sample(n)`), their visible ground truth is traced once into
+    bit masks (ops/view_pool.py ViewPool), and every decision is popcount(mask & ~scanned_bits) and an argmax over the pool --
+    no ray is traced again.  At stride 1 `last_gain[e]` is exactly the coverage_count increment the env pays for the step
+    (for envs that were not reset, as OracleGainPolicy).  Ties go to the lowest pool index; with a CollisionBody on the env (and
+    `avoid_collisions`) pool views whose pose collides are never chosen unless all do.  `last_choice` [N] is the pool index.
+    `persistent_bounds`: every candidate's last gain is kept as an upper bound for the next decision (gains only shrink
+    while the scanned set grows), so a decision evaluates only the candidates that can still win; an env whose episode has
+    just restarted (episode_length_buf <= 1 at decision time: the post-step kernel zeroes it on the done step, the next step
+    forces the init action, clears the scanned set and counts 1) gets its row set back to unknown, on the device.  The
+    actions are the same with and without.  `.plan(rounds)` is the offline greedy set-cover plan from the current scanned
+    set.  No host synchronisation inside a decision.  It needs the packed updater and a closed-loop feed with a mesh, as
+    OracleGainPolicy."""
+
+    def __init__(self, env, pool_size: int = 256, seed: int = 0, stride: int = 1, avoid_collisions: bool = True,
+                 look_at_scene: bool = True, persistent_bounds: bool = True):
+        from .. import _lib
+        from ..ops.view_pool import UNKNOWN, ViewPool
+        cfg = env.cfg
+        self.env, self.cfg, self.pool_size = env, cfg, int(pool_size)
+        self.num_envs = n = int(env.num_envs)
+        u = env.updater
+        if not getattr(u, "packed", False):
+            raise _lib.GennbvHipError("PoolCoverPolicy needs the packed updater (a binary ground truth: gt_bits / scanned_bits)")
+        mesh = getattr(env.feed, "mesh", None)
+        if mesh is None:
+            raise _lib.GennbvHipError("PoolCoverPolicy needs the scene's mesh (a closed-loop RenderFeed): env.feed has none")
+        self.cands = LatticeCandidates(cfg, pool_size, seed, look_at_scene)
+        self.pool_actions = self.cands.sample(n, env.device)
+        self.avoid_collisions = bool(avoid_collisions) and getattr(env, "collision", None) is not None
+        self.pool = ViewPool(mesh, cfg, u.range_gt, u.voxel_size_gt, u.gt_bits, self.cands.poses(self.pool_actions), stride=stride,
+                             inv_intrinsics=u.inv_intri_host, body=env.collision if self.avoid_collisions else None,
+                             collision_mesh=env.collision_mesh if self.avoid_collisions else None)
+        self.persistent_bounds = bool(persistent_bounds)
+        self._unknown = UNKNOWN
+        self._ub = torch.full((n, self.pool_size), UNKNOWN, dtype=torch.int32, device=env.device) if self.persistent_bounds else None
+        self._rows = torch.arange(n, device=env.device)
+        self.last_gain = None
+        self.last_choice = None
+
+    def __call__(self, obs, deterministic: bool = True):
+        env = self.env
+        if self._ub is not None:
+            self._ub.masked_fill_((env.episode_length_buf <= 1).unsqueeze(1), self._unknown)
+        choice, gain = self.pool.select(env.updater.scanned_bits, self._ub)
+        self.last_choice, self.last_gain = choice, gain
+        return self.pool_actions[self._rows, choice.long()], None, None
+
+    def plan(self, rounds: int, covered_bits: Optional[torch.Tensor] = None, lazy: bool = True):
+        """ViewPool.plan from covered_bits (default: the env's current scanned set) -> (choice [N,T], gain [N,T], covered);
+        the planned actions are pool_actions[e, choice[e, t]]."""
+        return self.pool.plan(rounds, self.env.updater.scanned_bits if covered_bits is None else covered_bits, lazy)
 
     @property
     def policy(self):

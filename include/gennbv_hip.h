@@ -792,6 +792,54 @@ typedef struct GnbvViewCover {
 } GnbvViewCover;
 int gnbv_view_cover(const GnbvMeshScene *scene /*[host]*/, const GnbvViewCover *args /*[host]*/, void *stream);
 
+/* ------------------------------------------------------------------------- */
+/* View pool (new entry points of ABI 5): every candidate's visible ground     */
+/* truth as a bit mask, traced once, and greedy set cover on those masks.      */
+/* ------------------------------------------------------------------------- */
+/* mask_bits[e, j, :] = S(e, j) & gt_bits[e, :], S exactly gnbv_view_cover's seen set of the same arguments; rows of
+ * words = gnbv_grid_bit_words(g).  Every word of every row is written on every call, the zero words and the pad words past the
+ * voxels included: the caller does not zero mask_bits.  The workgroup of (env, chunk[, window]) owns its window's words of its
+ * candidates' rows and stores them from the LDS bit set with 16-byte stores before it clears the set (the workgroup of the last
+ * window also stores the pad words): no atomics and no zeroing launch for the masks, so the result depends neither on `chunk` nor
+ * on `window`.  args->cover and args->seen_bits may both be NULL here; a non-NULL one is filled exactly as gnbv_view_cover fills
+ * it (popcount(mask & ~scanned) == cover[.., 0], popcount(mask) == cover[.., 1]).  Deterministic.  No host synchronisation, no
+ * allocation, no workspace.
+ * Returns hipErrorInvalidValue for a NULL or not 16-byte aligned mask_bits and for everything gnbv_view_cover refuses, except
+ * that cover and seen_bits may both be NULL. */
+int gnbv_view_cover_masks(const GnbvMeshScene *scene /*[host]*/, const GnbvViewCover *args /*[host]*/,
+                          int32_t *mask_bits /*[n, k, words]*/, void *stream);
+
+/* Greedy set cover over per-candidate bit masks (gnbv_view_cover_masks' layout, or any [n, k, words] rows).  Per env, with
+ * covered = covered_in (NULL: empty), for round t = 0 .. rounds-1:
+ *   g_j = popcount(mask[j] & ~covered);  score_j = contact[j] ? -1 : g_j;
+ *   j* = the largest score, ties to the lowest j (all candidates in contact: j* = 0);
+ *   choice[t] = j*;  gain[t] = g_j* (the true gain, also of a contact winner);  covered |= mask[j*].
+ * A candidate may win again with gain 0.  Integers with one right answer.  gains0[e, j] = g_j of round 0 for every candidate.
+ * lazy = 1 evaluates only the candidates whose upper bound can still win (gains only shrink while covered grows, so the result
+ * is the same integers as lazy = 0): per round the stale candidates are refreshed in descending (bound, -j) order, one per
+ * wave and pass, until the largest key belongs to a candidate refreshed in this round.  `ub`: the bounds are read at entry and
+ * written at exit; INT32_MAX = unknown; the caller promises ub[e, j] >= candidate j's true gain against covered_in, which holds
+ * across calls while the env's covered set only grows.  With ub == NULL the bounds are internal.  With gains0 != NULL, ub == NULL
+ * or lazy == 0, round 0 evaluates every candidate (one wave each, 16 bytes per lane).  Rounds after the first run in one
+ * workgroup per env, whose covered row lives in covered_out.  No global atomics, every output element written once per call,
+ * no host synchronisation, no allocation.  Deterministic.
+ * Returns hipErrorInvalidValue for n outside 1..65535, k or rounds outside 1..4096, words not a positive multiple of 4, lazy
+ * outside 0..1, a NULL mask_bits, choice or gain, rounds > 1 without covered_out, or a mask_bits / covered_in / covered_out
+ * that is not 16-byte aligned.  [host struct]; pointers are device. */
+typedef struct GnbvCoverGreedy {
+    int n, k, words, rounds;        /* envs, candidates per env, words per row, T >= 1 */
+    const int32_t *mask_bits;       /* [n, k, words] */
+    const int32_t *covered_in;      /* [n, words], or NULL = nothing covered */
+    const uint8_t *contact;         /* [n, k], or NULL; != 0: never chosen unless every candidate of the env is */
+    int32_t *choice, *gain;         /* [n, rounds] */
+    int32_t *covered_out;           /* [n, words] = covered_in | the chosen masks; required when rounds > 1, else may be NULL;
+                                     * may alias covered_in */
+    int32_t *gains0;                /* [n, k], or NULL: every candidate's gain against covered_in */
+    int32_t *ub;                    /* [n, k], or NULL: in/out upper bounds */
+    int lazy;                       /* 1 = lazy evaluation, 0 = every candidate in every round; the same results */
+} GnbvCoverGreedy;
+int gnbv_cover_greedy(const GnbvCoverGreedy *args /*[host]*/, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,125 @@
+"""Microbenchmark of the view pool: building the masks (gnbv_view_cover_masks) and deciding on them (gnbv_cover_greedy).
+
+    python tools/microbench_cover_greedy.py [--envs 256] [--grid 64] [--pool 256] [--repeats 7] [--iters 2] [--parts build,select,plan] [--out FILE.json]
+
+The protocol of tools/microbench_view_cover.py: device events around `iters` back-to-back calls, after warm-up, `repeats` times,
+the alternatives of one part alternated repeat by repeat in one process; reported: median / min / max us per call.  Box scenes
+(make_scenes), 240 x 320 camera, stride 1, look-at-scene lattice poses.
+
+  build    ViewPool(...) for `pool` views per env (masks, union, staging copies; 1 call per repeat), beside the same candidate
+           count through ViewCover.__call__ in batches of 64 (the trace with three integers per candidate instead of a mask row)
+  select   one decision over the pool against a mid-episode covered set (the covered set of plan(5)): exhaustive (every mask
+           read: bytes = N P vwords 4 + N vwords 4, against the 8 TB/s roof), with carried bounds (the bounds left by the
+           decision before, restored before each call), and beside them the one-step oracle's decision on the same state:
+           ViewCover (K = 32) + choose
+  plan     plan(20) from the empty set, lazy against exhaustive
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+
+from gennbv_amd.env import synthetic as S  # noqa: E402
+from gennbv_amd.env.config import TaskConfig  # noqa: E402
+from gennbv_amd.env.mesh_scene import MeshScene  # noqa: E402
+from gennbv_amd.env.state_encoding import OccupancyGridUpdater  # noqa: E402
+from gennbv_amd.eval.baselines import LatticeCandidates, choose  # noqa: E402
+from gennbv_amd.ops.view_cover import ViewCover  # noqa: E402
+from gennbv_amd.ops.view_pool import UNKNOWN, ViewPool  # noqa: E402
+from tools.microbench_view_cover import alternate, stats  # noqa: E402
+
+DEV = "cuda:0"
+HBM_BYTES_PER_S = 8e12
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=256)
+    ap.add_argument("--grid", type=int, default=64)
+    ap.add_argument("--pool", type=int, default=256)
+    ap.add_argument("--oracle-k", type=int, default=32)
+    ap.add_argument("--rounds", type=int, default=20)
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--iters", type=int, default=2)
+    ap.add_argument("--parts", default="build,select,plan")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("microbench_cover_greedy needs a GPU")
+    n, g, p, h, w = args.envs, args.grid, args.pool, 240, 320
+    parts = args.parts.split(",")
+    cfg = TaskConfig(camera_width=w, camera_height=h, grid_size=g)
+    scene = S.make_scenes(n, g, seed=1)
+    mesh = MeshScene.from_boxes(scene, device=DEV)
+    upd = OccupancyGridUpdater(n, g, h, w, S.inverse_intrinsics(h, w, cfg.horizontal_fov), scene.range_gt, scene.voxel_size, scene.grid_gt,
+                               DEV, cfg.depth_sense_dist)
+    gt = upd.gt_bits
+    lc = LatticeCandidates(cfg, p, seed=3, look_at_scene=True)
+    poses = lc.poses(lc.sample(n)).to(DEV)
+    res = {"envs": n, "grid": g, "pool": p, "h": h, "w": w}
+
+    def build():
+        return ViewPool(mesh, cfg, scene.range_gt, scene.voxel_size, gt, poses)
+
+    pool = build()
+    vwords = (((g ** 3 + 31) // 32) + 3) & ~3
+    res["mask_bytes"] = pool.masks.numel() * 4
+    if "build" in parts:
+        kb = min(64, p)
+        vc = ViewCover(mesh, cfg, scene.range_gt, scene.voxel_size, kb)
+        cols = [poses[:, j:j + kb].contiguous() for j in range(0, p - kb + 1, kb)]
+
+        def counted():
+            for c in cols:
+                vc(c, gt, None)
+        del pool
+        torch.cuda.empty_cache()
+        b, c = alternate([build, counted], 1, max(3, args.repeats // 2), warmup=1)
+        res["build"], res["view_cover_same_candidates"] = stats(b), stats(c)
+        res["build_over_view_cover"] = res["build"]["us_median"] / res["view_cover_same_candidates"]["us_median"]
+        print(json.dumps({k: res[k] for k in ("build", "view_cover_same_candidates", "build_over_view_cover")}), flush=True)
+        pool = build()
+    if "select" in parts:
+        cov4 = pool.plan(4)[2].clone()
+        cov5 = pool.plan(5)[2].clone()
+        ub0 = torch.full((n, p), UNKNOWN, dtype=torch.int32, device=DEV)
+        want = tuple(t.clone() for t in pool.select(cov5))
+        pool.select(cov4, ub0)  # the bounds a decision leaves for the next one
+        ub = ub0.clone()
+        assert all(torch.equal(x, y) for x, y in zip(pool.select(cov5, ub), want))
+        ko = args.oracle_k
+        vco = ViewCover(mesh, cfg, scene.range_gt, scene.voxel_size, ko)
+        poses_o = poses[:, :ko].contiguous()
+
+        def carried():
+            ub.copy_(ub0)
+            pool.select(cov5, ub)
+
+        ex, ca, orc = alternate([lambda: pool.select(cov5), carried, lambda: choose(vco(poses_o, gt, cov5), (1, 0))], args.iters, args.repeats)
+        res["select_exhaustive"], res["select_carried_bounds"], res["oracle_decision"] = stats(ex), stats(ca), stats(orc)
+        nbytes = n * p * vwords * 4 + n * vwords * 4
+        res["select_bytes"] = nbytes
+        res["select_fraction_of_hbm_roof"] = nbytes / (res["select_exhaustive"]["us_median"] * 1e-6) / HBM_BYTES_PER_S
+        res["oracle_over_select"] = res["oracle_decision"]["us_median"] / res["select_exhaustive"]["us_median"]
+        print(json.dumps({k: res[k] for k in ("select_exhaustive", "select_carried_bounds", "oracle_decision", "select_bytes",
+                                              "select_fraction_of_hbm_roof", "oracle_over_select")}), flush=True)
+    if "plan" in parts:
+        r = args.rounds
+        a = tuple(t.clone() for t in pool.plan(r, None, lazy=True))
+        assert all(torch.equal(x, y) for x, y in zip(a, pool.plan(r, None, lazy=False)))
+        lz, ex = alternate([lambda: pool.plan(r, None, lazy=True), lambda: pool.plan(r, None, lazy=False)], args.iters, args.repeats)
+        res["plan_lazy"], res["plan_exhaustive"], res["plan_rounds"] = stats(lz), stats(ex), r
+        print(json.dumps({k: res[k] for k in ("plan_rounds", "plan_lazy", "plan_exhaustive")}), flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
