@@ -56,6 +56,7 @@ SIGNATURES = {
     "gnbv_voxelize_surface": (_i, [_p, _p, _p, _i, _p, _p]),
     "gnbv_collide_cylinder": (_i, [_p, _p, _p, _i64, _f, _f, _i, _p, _p]),
     "gnbv_collide_cylinder_batch": (_i, [_p, _p, _p, _i, _i64, _f, _f, _i, _p, _p]),
+    "gnbv_sweep_sphere": (_i, [_p, _p, _i64, _i64, _p, _i, _i64, _f, _i, _p, _i, _p, _p]),
     "gnbv_rollout_add": (_i, [_i, _i, _p, _p, _p, _p, _i, _f, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "gnbv_input_autocorr_row_ints": (_i, []),
     "gnbv_input_autocorr": (_i, [_p, _i64, _i, _i, _p, _i64, _p]),

@@ -20,7 +20,9 @@ the GT point cloud of the evaluation env.  env/mesh_io.py reads Wavefront OBJ fi
 
 Collision termination uses the same triangles as closed solids: `objects` indexes them per (env, object id) -- the
 objects of each env, each object's AABB and triangle list, CSR, built once with torch -- and `collide` runs
-gnbv_collide_cylinder (csrc/collide.hip) for a CollisionBody (env/collision.py) at given poses.
+gnbv_collide_cylinder (csrc/collide.hip) for a CollisionBody (env/collision.py) at given poses.  `sweep` /
+`sweep_candidates` ask the same of the straight flight between two poses (gnbv_sweep_sphere, csrc/sweep.hip), through
+the cell lists alone.
 """
 from __future__ import annotations
 
@@ -171,6 +173,66 @@ class MeshScene:
         _lib.check(_lib.load().gnbv_collide_cylinder_batch(C.byref(sc), C.byref(ob), poses.data_ptr(), k, row, float(body.radius),
                                                            float(body.half_length), int(bool(body.ground)), out.data_ptr(),
                                                            _lib.stream_ptr(self.device)), "gnbv_collide_cylinder_batch")
+        return out
+
+    def sweep(self, from_poses: torch.Tensor, to_poses: torch.Tensor, body, episode_length: Optional[torch.Tensor] = None,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """gnbv_sweep_sphere on the current stream: path code [N] u8 of the straight flight from from_poses [N, >= 3] to
+        to_poses [N, >= 3] f32 (x, y, z first; unit element stride) for the sphere of radius body.path_radius: bit 3 (8) a
+        triangle comes within the radius of the segment, bit 4 (16) the swept sphere reaches z <= 0 (body.ground); 0 = free.
+        episode_length [N] int64: envs with episode_length <= 1 get 0 (their pose was set, not flown to).  Equal to
+        sweep_candidates(...)[:, 0], bit for bit.  On the GPU only."""
+        if self.device.type != "cuda":
+            raise _lib.GennbvHipError("MeshScene.sweep runs on the GPU only (no CPU fallback): build the MeshScene on a cuda device")
+        n = self.num_envs
+        _lib.require_cuda(from_poses, to_poses, episode_length, out)
+        assert to_poses.dtype == torch.float32 and to_poses.dim() == 2 and to_poses.shape[0] == n and to_poses.shape[1] >= 3 and to_poses.stride(1) == 1
+        if out is None:
+            out = torch.empty(n, dtype=torch.uint8, device=self.device)
+        assert out.dtype == torch.uint8 and out.shape == (n,) and out.is_contiguous()
+        self.sweep_candidates(from_poses, to_poses.unsqueeze(1), body, episode_length, out.unsqueeze(1))
+        return out
+
+    def sweep_candidates(self, from_poses: torch.Tensor, to_poses: torch.Tensor, body, episode_length: Optional[torch.Tensor] = None,
+                         out: Optional[torch.Tensor] = None, accumulate: bool = False) -> torch.Tensor:
+        """gnbv_sweep_sphere on the current stream: path code [N,K] u8 of the flights to to_poses [N, K, >= 3] f32 (unit element
+        stride, rows (e, j) evenly spaced) from from_poses [N, >= 3] (one start per env, broadcast over K) or [N, K, >= 3], one
+        launch.  `accumulate`: OR the codes into `out` (e.g. what collide_candidates has just stored there) instead of
+        storing them.  See `sweep` for the code, the radius and episode_length."""
+        if self.device.type != "cuda":
+            raise _lib.GennbvHipError("MeshScene.sweep_candidates runs on the GPU only (no CPU fallback): build the MeshScene on a "
+                                      "cuda device")
+        n = self.num_envs
+        _lib.require_cuda(from_poses, to_poses, episode_length, out)
+        assert to_poses.dtype == torch.float32 and to_poses.dim() == 3 and to_poses.shape[0] == n and to_poses.shape[2] >= 3 and to_poses.stride(2) == 1
+        k = int(to_poses.shape[1])
+        assert from_poses.dtype == torch.float32 and from_poses.dim() in (2, 3) and from_poses.shape[0] == n and from_poses.shape[-1] >= 3
+        assert from_poses.stride(-1) == 1 and (from_poses.dim() == 2 or from_poses.shape[1] == k)
+
+        def rows(t, broadcast):  # (tensor, its strides of dim 0 and 1 in floats); a dimension of size 1 may carry any stride
+            def bad(t):
+                return (t.shape[0] > 1 and t.stride(0) < 3) or (t.dim() == 3 and t.shape[1] > 1 and t.stride(1) < 3 and
+                                                               not (broadcast and t.stride(1) == 0))
+            if bad(t):
+                t = t.contiguous()
+            s1 = int(t.stride(1)) if t.dim() == 3 and t.shape[1] > 1 else 0
+            return t, max(int(t.stride(0)), 3), s1
+        if k > 1 and n > 1 and to_poses.stride(0) != k * to_poses.stride(1):
+            to_poses = to_poses.contiguous()
+        to_poses, t0, t1 = rows(to_poses, False)
+        row = t1 if k > 1 else t0
+        from_poses, f0, f1 = rows(from_poses, True)
+        if episode_length is not None:
+            assert episode_length.dtype == torch.int64 and episode_length.shape == (n,) and episode_length.is_contiguous()
+        if out is None:
+            assert not accumulate, "accumulate needs the buffer to OR into"
+            out = torch.empty(n, k, dtype=torch.uint8, device=self.device)
+        assert out.dtype == torch.uint8 and out.shape == (n, k) and out.is_contiguous()
+        sc = self.c_struct()
+        _lib.check(_lib.load().gnbv_sweep_sphere(C.byref(sc), from_poses.data_ptr(), f0, f1, to_poses.data_ptr(), k, row,
+                                                 float(body.path_radius), int(bool(body.ground)), _lib.ptr(episode_length),
+                                                 int(bool(accumulate)), out.data_ptr(), _lib.stream_ptr(self.device)),
+                   "gnbv_sweep_sphere")
         return out
 
     # ------------------------------------------------------------------

@@ -23,7 +23,10 @@ buffer hand its own storage to the env (no assemble + copy pass).
 termination: every step and reset tests the body at the step's poses against the
 mesh's solids (MeshScene.collide) into `collision_buf` [N] u8, and an env with
 contact resets with the termination reward (gnbv_env_post_step_contacts).  The
-mesh is `collision_mesh`, by default the RenderFeed's own.
+mesh is `collision_mesh`, by default the RenderFeed's own.  With `collision.sweep`
+the straight flight from the previous pose to the step's pose is tested too
+(MeshScene.sweep, csrc/sweep.hip): its path bits are ORed into `collision_buf`,
+except on the first step of an episode, whose pose is set, not flown to.
 """
 from __future__ import annotations
 
@@ -126,6 +129,8 @@ class ReplayFeedEnv:
             mesh.objects()  # the per-object index, built once
             self.collision_mesh = mesh
             self.collision_buf = torch.zeros(n, dtype=torch.uint8, device=self.device)
+        self._sweep = collision is not None and bool(getattr(collision, "sweep", False))
+        self._prev_poses = None  # the poses before the step's head overwrites them (collision.sweep only)
         self.grid_size = cfg.grid_size
         self.max_episode_length = int(cfg.max_episode_length if max_episode_length is None else max_episode_length)
         self.max_episode_length_s = cfg.episode_length_s
@@ -245,12 +250,16 @@ class ReplayFeedEnv:
         # step(): clip, forced init action, poses; episode_length_buf += 1
         self._post.episode_length_buf = self.episode_length_buf.data_ptr()  # the algorithm may have replaced the tensor
         rgb_off = cfg.state_dim + (0 if compact else cfg.grid_dim)
+        if self._sweep:
+            if self._prev_poses is None:
+                self._prev_poses = torch.empty_like(self.poses)
+            self._prev_poses.copy_(self.poses)
         if closed_loop:
             # closed loop (RenderFeed): the frame is rendered from the poses this step computes, so the fused
             # gnbv_env_observe (poses and the rgba read in one launch) cannot be used
             self._pre_step(actions_in, st)
             if self.collision is not None:  # step order: pre-step -> collide -> render -> ... -> post-step with contacts
-                self.collision_mesh.collide(self.poses, self.collision, out=self.collision_buf)
+                self._collide_step()
             depth_raw, seg_raw, rgba, c2w = self.feed.render(self.poses)
             self._observe_slices(obs, stride, self._rgba_or_zero(rgba), rgb_off, st)
         elif self.fused_observe and getattr(lib, "gnbv_env_observe", None) is not None:
@@ -263,7 +272,7 @@ class ReplayFeedEnv:
         else:
             self._observe_three_launches(actions_in, obs, stride, self._rgba_or_zero(rgba), rgb_off, st)
         if self.collision is not None and not closed_loop:
-            self.collision_mesh.collide(self.poses, self.collision, out=self.collision_buf)
+            self._collide_step()
         # obs["grid"]: tri-class grid straight into the observation rows
         if compact:
             self.updater.update(depth_raw, seg_raw, c2w, self.poses, reset_mask=self.reset_mask, tri_i8_out=grid_i8_out, fp32_out=False)
@@ -279,6 +288,14 @@ class ReplayFeedEnv:
         else:
             _lib.check(lib.gnbv_env_post_step(C.byref(self._post), st), "gnbv_env_post_step")
         return obs
+
+    def _collide_step(self):
+        """collision_buf = the body at the step's poses, and with `collision.sweep` | the flight from the previous poses to
+        them (episode_length_buf <= 1 after the step's head: the first pose of an episode, not flown to)."""
+        self.collision_mesh.collide(self.poses, self.collision, out=self.collision_buf)
+        if self._sweep:
+            self.collision_mesh.sweep_candidates(self._prev_poses, self.poses.unsqueeze(1), self.collision, self.episode_length_buf,
+                                                 out=self.collision_buf.unsqueeze(1), accumulate=True)
 
     def _rgba_or_zero(self, rgba):
         if rgba is None:

@@ -63,6 +63,11 @@ class RandomLatticePolicy:
         return self(obs, deterministic)[0], state
 
 
+def _sweeps(env) -> bool:
+    """The env's CollisionBody also tests the flight between poses (CollisionBody.sweep)."""
+    return bool(getattr(getattr(env, "collision", None), "sweep", False))
+
+
 def choose(gain: torch.Tensor, weights: Sequence[int], contact: Optional[torch.Tensor] = None) -> torch.Tensor:
     """gain [N,K,3] int -> index [N] of the candidate with the largest w0 * unknown + w1 * unknown_hit (int64); candidates
     with contact[N,K] != 0 score -1; ties go to the lowest candidate index."""
@@ -78,7 +83,9 @@ def choose(gain: torch.Tensor, weights: Sequence[int], contact: Optional[torch.T
 class GreedyGainPolicy:
     """Greedy next-best view: K random lattice candidates per env and step, the one with the largest
     w0 * unknown + w1 * unknown_hit of the view gain against the observation's grid wins; with a CollisionBody on the
-    env (and `avoid_collisions`) candidates whose pose collides are never chosen unless all do.  No host
+    env (and `avoid_collisions`) candidates whose pose collides are never chosen unless all do; where that body has `sweep`,
+    a candidate whose straight flight from `env.poses` is blocked (MeshScene.sweep_candidates, accumulated into the same
+    contact buffer) counts exactly like one in contact -- that needs a collision mesh with `sweep_candidates`.  No host
     synchronisation inside a decision.  `gain_backend(tri [N,G^3], poses [N,K,6]) -> gain [N,K,3]` replaces the kernel in
     tests only: the product path has no CPU fallback."""
 
@@ -89,6 +96,10 @@ class GreedyGainPolicy:
         self.num_envs = int(env.num_envs)
         self.cands = LatticeCandidates(cfg, k, seed, look_at_scene)
         self.avoid_collisions = bool(avoid_collisions) and getattr(env, "collision", None) is not None
+        self.sweep = self.avoid_collisions and _sweeps(env)
+        if self.sweep and not (hasattr(env.collision_mesh, "sweep_candidates") and hasattr(env.collision_mesh, "collide_candidates")):
+            from .. import _lib
+            raise _lib.GennbvHipError("GreedyGainPolicy: CollisionBody.sweep needs a collision mesh with sweep_candidates")
         if gain_backend is None:
             from ..ops.view_gain import make_view_gain
             u = env.updater
@@ -112,6 +123,8 @@ class GreedyGainPolicy:
                 if self._contact is None:
                     self._contact = torch.zeros(n, k, dtype=torch.uint8, device=obs.device)
                 contact = mesh.collide_candidates(poses, self.env.collision, out=self._contact)
+                if self.sweep:  # | the flight from the current pose, into the same buffer
+                    mesh.sweep_candidates(self.env.poses, poses, self.env.collision, out=self._contact, accumulate=True)
             else:
                 if self._contact is None:
                     self._contact = torch.zeros(k, n, dtype=torch.uint8, device=obs.device)
@@ -135,7 +148,8 @@ class OracleGainPolicy:
     (ops/view_cover.py) of the env's own scene (`env.feed.mesh`), ground truth and scanned set (`env.updater.gt_bits`,
     `.scanned_bits`), i.e. at stride 1 exactly the coverage_count increment the env pays for the step.  It reads the scene
     geometry and the ground truth, which no deployable planner has.  Ties go to the lowest candidate index; with a
-    CollisionBody on the env (and `avoid_collisions`) candidates whose pose collides are never chosen unless all do.
+    CollisionBody on the env (and `avoid_collisions`) candidates whose pose collides are never chosen unless all do, and
+    where that body has `sweep` neither are candidates whose straight flight from `env.poses` is blocked.
     `last_cover` [N,K,3] keeps the last decision's integers.  No host synchronisation inside a decision.  It needs the
     packed updater (a binary ground truth) and a closed-loop feed with a mesh; anything else is refused.
     `cover_backend(poses [N,K,6], gt_bits, scanned_bits) -> cover [N,K,3]` replaces the kernel in tests only: the product
@@ -152,6 +166,7 @@ class OracleGainPolicy:
         self.num_envs = int(env.num_envs)
         self.cands = LatticeCandidates(cfg, k, seed, look_at_scene)
         self.avoid_collisions = bool(avoid_collisions) and getattr(env, "collision", None) is not None
+        self.sweep = self.avoid_collisions and _sweeps(env)
         u = env.updater
         if not getattr(u, "packed", False):
             raise _lib.GennbvHipError("OracleGainPolicy needs the packed updater (a binary ground truth: gt_bits / scanned_bits)")
@@ -178,6 +193,8 @@ class OracleGainPolicy:
             if self._contact is None:
                 self._contact = torch.zeros(n, k, dtype=torch.uint8, device=obs.device)
             contact = self.env.collision_mesh.collide_candidates(poses, self.env.collision, out=self._contact)
+            if self.sweep:
+                self.env.collision_mesh.sweep_candidates(self.env.poses, poses, self.env.collision, out=self._contact, accumulate=True)
         best = choose(cover, (1, 0), contact)
         return cand[torch.arange(n, device=cand.device), best], None, None
 
@@ -195,13 +212,17 @@ class PoolCoverPolicy:
     bit masks (ops/view_pool.py ViewPool), and every decision is popcount(mask & ~scanned_bits) and an argmax over the pool --
     no ray is traced again.  At stride 1 `last_gain[e]` is exactly the coverage_count increment the env pays for the step
     (for envs that were not reset, as OracleGainPolicy).  Ties go to the lowest pool index; with a CollisionBody on the env (and
-    `avoid_collisions`) pool views whose pose collides are never chosen unless all do.  `last_choice` [N] is the pool index.
+    `avoid_collisions`) pool views whose pose collides are never chosen unless all do; where that body has `sweep`, every
+    decision also ORs the flight from `env.poses` to each pool pose into a copy of the pool's static contact (one copy, one
+    sweep launch) and hands it to the selection -- the carried bounds stay valid, a bound does not depend on contact.
+    `last_choice` [N] is the pool index.
     `persistent_bounds`: every candidate's last gain is kept as an upper bound for the next decision (gains only shrink
     while the scanned set grows), so a decision evaluates only the candidates that can still win; an env whose episode has
     just restarted (episode_length_buf <= 1 at decision time: the post-step kernel zeroes it on the done step, the next step
     forces the init action, clears the scanned set and counts 1) gets its row set back to unknown, on the device.  The
     actions are the same with and without.  `.plan(rounds)` is the offline greedy set-cover plan from the current scanned
-    set.  No host synchronisation inside a decision.  It needs the packed updater and a closed-loop feed with a mesh, as
+    set; it keeps the static contact (an offline plan has no "current pose" per round, so no flight is tested).  No host
+    synchronisation inside a decision.  It needs the packed updater and a closed-loop feed with a mesh, as
     OracleGainPolicy."""
 
     def __init__(self, env, pool_size: int = 256, seed: int = 0, stride: int = 1, avoid_collisions: bool = True,
@@ -223,6 +244,8 @@ class PoolCoverPolicy:
         self.pool = ViewPool(mesh, cfg, u.range_gt, u.voxel_size_gt, u.gt_bits, self.cands.poses(self.pool_actions), stride=stride,
                              inv_intrinsics=u.inv_intri_host, body=env.collision if self.avoid_collisions else None,
                              collision_mesh=env.collision_mesh if self.avoid_collisions else None)
+        self.sweep = self.avoid_collisions and _sweeps(env)
+        self._contact = torch.empty_like(self.pool.contact) if self.sweep else None
         self.persistent_bounds = bool(persistent_bounds)
         self._unknown = UNKNOWN
         self._ub = torch.full((n, self.pool_size), UNKNOWN, dtype=torch.int32, device=env.device) if self.persistent_bounds else None
@@ -234,13 +257,17 @@ class PoolCoverPolicy:
         env = self.env
         if self._ub is not None:
             self._ub.masked_fill_((env.episode_length_buf <= 1).unsqueeze(1), self._unknown)
-        choice, gain = self.pool.select(env.updater.scanned_bits, self._ub)
+        contact = None
+        if self.sweep:  # the static contact | the flight from the current pose to each pool pose
+            contact = self._contact.copy_(self.pool.contact)
+            env.collision_mesh.sweep_candidates(env.poses, self.pool.poses, env.collision, out=contact, accumulate=True)
+        choice, gain = self.pool.select(env.updater.scanned_bits, self._ub, contact)
         self.last_choice, self.last_gain = choice, gain
         return self.pool_actions[self._rows, choice.long()], None, None
 
     def plan(self, rounds: int, covered_bits: Optional[torch.Tensor] = None, lazy: bool = True):
         """ViewPool.plan from covered_bits (default: the env's current scanned set) -> (choice [N,T], gain [N,T], covered);
-        the planned actions are pool_actions[e, choice[e, t]]."""
+        the planned actions are pool_actions[e, choice[e, t]].  The plan keeps the static contact: no flight is tested."""
         return self.pool.plan(rounds, self.env.updater.scanned_bits if covered_bits is None else covered_bits, lazy)
 
     @property

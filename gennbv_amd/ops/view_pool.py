@@ -109,31 +109,39 @@ class ViewPool:
                                       f"got {covered_bits.dtype} {tuple(covered_bits.shape)}")
         return covered_bits
 
-    def _launch(self, rounds, covered_in, choice, gain, covered_out, gains0, ub, lazy):
+    def _launch(self, rounds, covered_in, choice, gain, covered_out, gains0, ub, lazy, contact=None):
         c = self._cg
+        c.contact = _lib.ptr(self.contact if contact is None else contact)
         c.rounds, c.covered_in, c.choice, c.gain = int(rounds), _lib.ptr(covered_in), choice.data_ptr(), gain.data_ptr()
         c.covered_out, c.gains0, c.ub, c.lazy = _lib.ptr(covered_out), _lib.ptr(gains0), _lib.ptr(ub), int(bool(lazy))
         _lib.check(self.lib.gnbv_cover_greedy(C.byref(c), _lib.stream_ptr(self.device)), "gnbv_cover_greedy")
 
-    def select(self, covered_bits: Optional[torch.Tensor], ub: Optional[torch.Tensor] = None):
+    def select(self, covered_bits: Optional[torch.Tensor], ub: Optional[torch.Tensor] = None, contact: Optional[torch.Tensor] = None):
         """One round against covered_bits [N, words] (None = nothing covered) -> (choice [N], gain [N]) int32.  `ub` [N,P]
         int32: upper bounds carried from call to call (GnbvCoverGreedy.ub: read, used for lazy evaluation, rewritten; UNKNOWN
         says nothing; valid while each env's covered set only grows -- reset an env's row to UNKNOWN when it shrinks).  Without
-        `ub` every candidate is evaluated."""
+        `ub` every candidate is evaluated.  `contact` [N,P] u8 replaces the pool's static contact for this call only (e.g.
+        the static contact | the flight from the current pose); a bound does not depend on contact -- the kernel keeps a
+        contact candidate's bound as it is, still >= its gain -- so `ub` stays valid while the contact set changes."""
         cov = self._covered(covered_bits)
+        if contact is not None:
+            _lib.require_cuda(contact)
+            if contact.dtype != torch.uint8 or contact.shape != (self.num_envs, self.pool_size) or not contact.is_contiguous():
+                raise _lib.GennbvHipError(f"ViewPool: contact must be contiguous uint8 [{self.num_envs}, {self.pool_size}]")
         if ub is not None:
             _lib.require_cuda(ub)
             if ub.dtype != torch.int32 or ub.shape != (self.num_envs, self.pool_size) or not ub.is_contiguous():
                 raise _lib.GennbvHipError(f"ViewPool: ub must be contiguous int32 [{self.num_envs}, {self.pool_size}]")
-            self._launch(1, cov, self._choice1, self._gain1, None, None, ub, True)
+            self._launch(1, cov, self._choice1, self._gain1, None, None, ub, True, contact)
         else:
-            self._launch(1, cov, self._choice1, self._gain1, None, self._gains, None, False)
+            self._launch(1, cov, self._choice1, self._gain1, None, self._gains, None, False, contact)
         return self._choice1[:, 0], self._gain1[:, 0]
 
     def plan(self, rounds: int, covered_bits: Optional[torch.Tensor] = None, lazy: bool = True):
         """Greedy set cover: `rounds` views from the pool, starting from covered_bits (None = nothing covered; not modified)
         -> (choice [N,T], gain [N,T], covered [N, words] = covered_bits | the chosen masks).  `lazy` changes the work, not the
-        result."""
+        result.  The plan keeps the pool's static contact (poses that collide): an offline plan has no "current pose" per
+        round, so no flight is tested."""
         rounds = int(rounds)
         if not 1 <= rounds <= 4096:
             raise _lib.GennbvHipError(f"ViewPool.plan: rounds in 1..4096, got {rounds}")

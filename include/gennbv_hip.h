@@ -249,6 +249,29 @@ int gnbv_collide_cylinder_batch(const GnbvMeshScene *scene /*[host]*/, const Gnb
                                 int k, int64_t poses_row_stride /*floats*/, float radius, float half_length, int ground,
                                 uint8_t *contact_out /*[N,K]*/, void *stream);
 
+/* Swept flight path (a new entry point of ABI 5): does the drone, flown straight from one pose to the next, meet the scene?
+ * Item (e, j) is the segment a -> b, a = the xyz of `from` (e, j), b = the xyz of `to` (e, j), fp32 taken to fp64; the swept solid
+ * is the sphere of radius R = (double)radius moved along it (a capsule).  The body turns in flight, so the
+ * orientation-independent solid is the sphere that bounds the cylinder, R = sqrt(radius^2 + half_length^2) of
+ * gnbv_collide_cylinder's body: conservative, it never passes a path the cylinder could not fly.  The code of item (e, j) is
+ *   8  (PATH):        some closed triangle T of env e has dist(segment, T) <= R (a degenerate triangle counts as its segment or
+ *                     point; a zero-length segment is the sphere test), OR
+ *   16 (PATH_GROUND): ground != 0 and min(a_z, b_z) - R <= 0.
+ * The bits coexist with gnbv_collide_cylinder's 1, 2 and 4 in one byte.  An item with a non-finite endpoint gets 0.  There is
+ * no "inside" bit: a path whose start is free cannot enter a closed solid without coming within R of one of its triangles;
+ * whether the start is free is gnbv_collide_cylinder's question.
+ * to [N, K, >= 3] with the stride between consecutive (e, j) rows in floats (>= 3); from: row (e, j) at
+ * from + e * from_env_stride + j * from_item_stride floats, from_env_stride >= 3, from_item_stride >= 3 or 0 = one start per env,
+ * broadcast over K.  episode_length [N] int64 or NULL: where episode_length[e] <= 1 the code of every item of env e is 0 -- the
+ * first pose of an episode is set, not flown to (the tensor gnbv_env_pre_step counts).  accumulate = 0 stores the code,
+ * 1 ORs it into contact_out[e, j] (the item's own wave reads and writes its own byte: no atomics), e.g. onto what
+ * gnbv_collide_cylinder_batch has just stored.  Deterministic; no host synchronisation, no allocation, no workspace.
+ * k >= 1, N * k <= 2^31 - 1, radius > 0 finite, accumulate 0 or 1, else hipErrorInvalidValue. */
+int gnbv_sweep_sphere(const GnbvMeshScene *scene /*[host]*/, const float *from, int64_t from_env_stride /*floats*/,
+                      int64_t from_item_stride /*floats, 0 = broadcast*/, const float *to, int k, int64_t to_row_stride /*floats*/,
+                      float radius, int ground, const int64_t *episode_length /*[N] or NULL*/, int accumulate,
+                      uint8_t *contact_out /*[N,K]*/, void *stream);
+
 /* compute_reward (env_train_base.py:377-398), _reward_* / check_termination /
  * reset_idx (env_train_gennbv.py:377-457,535-556), update_extra_episode_info
  * (env_train_base.py:629-639). All pointers device, arrays [N] unless noted. [host struct] */
