@@ -245,9 +245,16 @@ __global__ __launch_bounds__(kPostThreads) void k_env_post_step(GnbvEnvPost a, c
         __syncthreads();
         const int tile_total = s_wave[kPostThreads / kWave];
         if (flag) {
-            const int64_t pos = a.ring_state[0] + base_count + s_wave[wv] + incl - 1;
-            a.ring_reward[pos % a.ring_len] = cur_sum;
-            a.ring_length[pos % a.ring_len] = cur_len;
+            // One writer per slot: only the last ring_len finished envs of the tile store (rank r with r + ring_len >= tile_total).  They
+            // hold at most ring_len consecutive positions, hence distinct slots; every store dropped is one a later env of this tile
+            // would overwrite (the deque keeps the highest env index), and between those waves there is no order.  A later tile
+            // overwrites an earlier one behind the loop's closing barrier.  At most ring_len finishes in the tile: every env stores.
+            const int r = s_wave[wv] + incl - 1;
+            if ((int64_t)r + a.ring_len >= tile_total) {
+                const int64_t pos = a.ring_state[0] + base_count + r;
+                a.ring_reward[pos % a.ring_len] = cur_sum;
+                a.ring_length[pos % a.ring_len] = cur_len;
+            }
             atomicOr(&s_any, 1);
         }
         base_count += tile_total;

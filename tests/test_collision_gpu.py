@@ -10,6 +10,7 @@ import torch
 from gennbv_amd.env import synthetic as S
 from gennbv_amd.env.config import TaskConfig
 from tests.collision_oracle import GROUND, INSIDE, SURFACE, CollisionOracle, hand_cases
+from tests.envstep_util import PostState as _PostState, contact_oracle_cls as _contact_oracle_cls
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -213,98 +214,6 @@ def test_env_counts(n):
 # ---------------------------------------------------------------------------
 # post-step with contacts
 # ---------------------------------------------------------------------------
-class _PostState:
-    """The device state of gnbv_env_post_step, random but consistent."""
-    NAMES = ("coverage_count", "num_valid", "prev_ratio", "episode_length_buf", "rewards", "dones", "reset_mask", "step_time_out",
-             "extras_time_outs", "coverage_ratio", "episode_sums", "cur_reward_sum", "cur_episode_length", "ring_reward", "ring_length",
-             "ring_state", "episode_info", "episode_state")
-
-    def __init__(self, n, cfg, max_len, seed):
-        g = torch.Generator().manual_seed(seed)
-        z = lambda *s, dt=torch.float32: torch.zeros(*s, dtype=dt, device=DEV)  # noqa: E731
-        self.n, self.cfg, self.max_len = n, cfg, max_len
-        self.coverage_count = z(n, dt=torch.int32)
-        self.num_valid = (200 + torch.randint(0, 100, (n,), generator=g)).float().to(DEV)
-        self.prev_ratio, self.episode_length_buf = z(n), torch.randint(0, max_len, (n,), generator=g).to(DEV)
-        self.rewards, self.dones, self.reset_mask = z(n), z(n, dt=torch.uint8), z(n, dt=torch.uint8)
-        self.step_time_out, self.extras_time_outs, self.coverage_ratio = z(n, dt=torch.uint8), z(n, dt=torch.uint8), z(n)
-        self.episode_sums, self.cur_reward_sum, self.cur_episode_length = z(3, n), z(n), z(n)
-        self.ring_reward, self.ring_length, self.ring_state = z(100), z(100), z(1, dt=torch.int64)
-        self.episode_info, self.episode_state = z(6, dt=torch.float64), z(4, dt=torch.float64)
-
-    def clone(self):
-        c = _PostState.__new__(_PostState)
-        c.n, c.cfg, c.max_len = self.n, self.cfg, self.max_len
-        for k in self.NAMES:
-            setattr(c, k, getattr(self, k).clone())
-        return c
-
-    def struct(self):
-        from gennbv_amd import _lib
-        cfg, p = self.cfg, _lib.GnbvEnvPost()
-        p.n, p.only_positive, p.max_episode_length = self.n, int(cfg.only_positive_rewards), self.max_len
-        p.scale_cov = float(f32(cfg.scale_surface_coverage * cfg.dt))
-        p.scale_short = float(f32(cfg.scale_short_path * cfg.dt))
-        p.scale_term = float(f32(cfg.scale_termination * cfg.dt))
-        p.coverage_threshold = float(f32(cfg.coverage_threshold))
-        p.coverage_count, p.num_valid_voxel_gt = self.coverage_count.data_ptr(), self.num_valid.data_ptr()
-        p.prev_ratio, p.episode_length_buf = self.prev_ratio.data_ptr(), self.episode_length_buf.data_ptr()
-        p.rewards, p.dones, p.reset_mask = self.rewards.data_ptr(), self.dones.data_ptr(), self.reset_mask.data_ptr()
-        p.step_time_out, p.extras_time_outs = self.step_time_out.data_ptr(), self.extras_time_outs.data_ptr()
-        p.coverage_ratio, p.episode_sums = self.coverage_ratio.data_ptr(), self.episode_sums.data_ptr()
-        p.cur_reward_sum, p.cur_episode_length = self.cur_reward_sum.data_ptr(), self.cur_episode_length.data_ptr()
-        p.ring_reward, p.ring_length, p.ring_state, p.ring_len = (self.ring_reward.data_ptr(), self.ring_length.data_ptr(),
-                                                                  self.ring_state.data_ptr(), 100)
-        p.episode_info, p.episode_state = self.episode_info.data_ptr(), self.episode_state.data_ptr()
-        p.max_episode_length_s = float(f32(cfg.episode_length_s))
-        return p
-
-    def advance(self, g):
-        """What the step does before the post-step: coverage grows (from 0 after a reset), the step is counted."""
-        grow = torch.randint(0, 40, (self.n,), generator=g).to(DEV).int()
-        self.coverage_count.copy_(torch.where(self.reset_mask.bool(), grow, self.coverage_count + grow))
-        self.coverage_count.copy_(torch.minimum(self.coverage_count, self.num_valid.int()))
-        self.episode_length_buf += 1
-
-    def snapshot(self):
-        return [getattr(self, k).cpu().numpy().tobytes() for k in self.NAMES]
-
-
-def _contact_oracle_cls():
-    from oracle.env_oracle import OracleEnv
-
-    class ContactOracleEnv(OracleEnv):
-        """oracle/env_oracle.OracleEnv with check_termination's collision_buf ORed into the resets (env_train_gennbv.py:445-457):
-        `contact` [n] u8 for the next step, or -- with `collider` = (CollisionOracle, r, h, ground) -- the oracle's collisions at
-        the oracle's own poses."""
-        contact = None
-        collider = None
-
-        def _observe(self, depth_raw, seg_raw, rgba, c2w, poses):
-            if self.collider is not None:
-                o, r, h, ground = self.collider
-                self.contact = o.codes(np.arange(self.n), poses, float(f32(r)), float(f32(h)), ground)
-            return super()._observe(depth_raw, seg_raw, rgba, c2w, poses)
-
-        def _reward_done(self, cov):
-            n = self.n
-            ratio = (cov.astype(f32) / self.num_valid).astype(f32)
-            rew = np.zeros(n, f32)
-            rew = (rew + ((ratio - self.prev_ratio).astype(f32) * self.s_cov).astype(f32)).astype(f32)
-            extra = np.clip(self.episode_length_buf - 30, 0, 2)
-            rew = (rew + ((-extra).astype(f32) * self.s_short).astype(f32)).astype(f32)
-            if self.cfg.only_positive_rewards:
-                rew = np.where(rew < 0, f32(0), rew).astype(f32)
-            collided = np.zeros(n, bool) if self.contact is None else np.asarray(self.contact) != 0
-            time_out = self.episode_length_buf >= self.max_episode_length
-            reset = collided | time_out | (ratio > f32(self.cfg.coverage_threshold))
-            self.time_out = time_out
-            self.term = ((reset & ~time_out).astype(f32) * self.s_term).astype(f32)  # the termination reward of this step
-            rew = (rew + self.term).astype(f32)
-            return rew, reset, time_out, ratio
-    return ContactOracleEnv
-
-
 def test_post_step_contacts_null_and_zero_equal_the_plain_kernel_and_random_contacts_equal_the_oracle():
     from gennbv_amd import _lib
     lib = _lib.load()

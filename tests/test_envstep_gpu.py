@@ -121,6 +121,47 @@ def test_replay_env_writes_into_caller_rows_and_tracks_episodes():
     assert int(env.ring_state.item()) == len(rew_host)
 
 
+def test_replay_env_episode_ring_when_more_envs_finish_at_once_than_it_holds():
+    """130 envs time out on the same step, twice: the 100-deep ring keeps the 100 highest env indices of the last mass reset
+    (deque(maxlen=100) extended in env order), whatever order the kernel's waves store in."""
+    from collections import deque
+    from gennbv_amd.env.replay_feed import ReplayFeed, ReplayFeedEnv
+    n, h, w, g, L = 130, 48, 64, 16, 3
+    cfg = TaskConfig(camera_width=w, camera_height=h, grid_size=g)
+    scene = S.make_scenes(n, g, seed=5)
+    feed = ReplayFeed.synthetic(scene, cfg, 3, seed=5)
+    feed = ReplayFeed(feed.depth_raw.to(DEV), feed.seg_raw.to(DEV), feed.rgba.to(DEV), feed.c2w.to(DEV))
+    env = ReplayFeedEnv(cfg, scene, feed, DEV, max_episode_length=L)
+    assert env.ring_len == 100
+    env.reset()
+    g_ = torch.Generator().manual_seed(0)
+    rew_host, len_host = deque(maxlen=100), deque(maxlen=100)
+    cur_r, cur_l = env.rew_buf.cpu().numpy().copy(), np.ones(n, np.float32)  # (reset() has run one update_extra_episode_info)
+    finished, mass = 0, 0
+    for t in range(6):
+        obs, rew, done, info = env.step(S.sample_actions(n, cfg, g_).to(DEV))
+        r, d = rew.cpu().numpy(), done.cpu().numpy()
+        assert d.all() or not d.any(), f"step {t}: the envs finish together"
+        if d.any():
+            assert info["time_outs"].cpu().numpy().all()
+        mass += int(d.all())
+        cur_r += r; cur_l += 1
+        for e in range(n):
+            if d[e]:
+                rew_host.append(cur_r[e]); len_host.append(cur_l[e]); cur_r[e] = 0; cur_l[e] = 0
+                finished += 1
+        if finished:
+            ei = env.episode_info()
+            np.testing.assert_allclose(ei["episode_reward"], np.mean(np.array(rew_host, np.float64)), rtol=1e-6, err_msg=f"step {t}")
+            np.testing.assert_allclose(ei["episode_length"], np.mean(np.array(len_host, np.float64)), rtol=1e-6, err_msg=f"step {t}")
+        assert int(env.ring_state.item()) == finished
+    assert mass == 2 and finished == 2 * n
+    # entry p of the ring sits at p % 100: the slots hold envs 30 .. 129 of the second mass reset
+    pos = np.arange(finished - 100, finished)
+    assert np.array_equal(env.ring_reward.cpu().numpy()[pos % 100], np.array(rew_host, np.float32))
+    assert np.array_equal(env.ring_length.cpu().numpy()[pos % 100], np.array(len_host, np.float32))
+
+
 @pytest.mark.parametrize("depth_dtype", ["f32", "f16"])
 def test_env_over_a_recorded_feed_file(tmp_path, depth_dtype):
     """an env fed from the on-disk container (env/feed_file.py) steps exactly like one fed from the
