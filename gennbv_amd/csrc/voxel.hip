@@ -435,7 +435,7 @@ __global__ __launch_bounds__(kRayThreads) void k_raycast(
 }
 
 // ===========================================================================
-// fused path, launches 1 + 2 (grids whose bitmask fits a workgroup's LDS next to 31 other waves: G <= 104)
+// fused path, launches 1 + 2 (grids whose bitmask, word list and pixel queue fit a workgroup's 160 KiB of LDS: G <= 93, see list_lds)
 //
 // k_hit_list: N x chunks workgroups of 1024 threads.  A workgroup streams its share of the env's depth + seg pixels
 // (two tiles of 4096 pixels in flight: the next tile's 16-byte requests are issued before the current tile is
@@ -2266,6 +2266,14 @@ static int launch_masks(const float *depth_raw, const float *seg_raw, const floa
     return gnbv_launch_status();
 }
 
+// k_hit_mask / k_hit_list / k_hit_atomic fetch the camera rows with 16-byte requests when four consecutive pixels share an image row
+// (w % 4 == 0; rows of h * w floats then keep the base pointer's alignment): the base pointers must be 16-byte aligned there.
+static inline bool camera_rows_aligned(const float *depth_raw, const float *seg_raw, int h, int w)
+{
+    if ((w & 3) != 0 || (int64_t)h * w >= (1 << 23)) return true;  // (the scalar pixel loops)
+    return (((uintptr_t)depth_raw | (uintptr_t)seg_raw) & 15) == 0;
+}
+
 static inline int grid_update_blocks(int64_t items, int n)
 {
     int bx = (int)((items + kGridThreads - 1) / kGridThreads);
@@ -2286,6 +2294,7 @@ GNBV_API int gnbv_update_occ_grid(const float *depth_raw, const float *seg_raw, 
     const int64_t g3 = (int64_t)g * g * g;
     GNBV_CHECK_ARG(g3 < (1ll << 31) && tri_row_stride >= g3 && (int64_t)h * w < (1ll << 31));
     GNBV_CHECK_ARG(workspace_bytes >= gnbv_voxel_workspace_bytes(n, g) && ((uintptr_t)workspace & 255) == 0);
+    GNBV_CHECK_ARG(camera_rows_aligned(depth_raw, seg_raw, h, w));
     hipStream_t st = gnbv_stream(stream);
     VoxelWorkspace ws = carve(workspace, workspace_bytes, n, g, h, w);
     int err = launch_masks(depth_raw, seg_raw, c2w, inv_intri, poses_xyz, poses_row_stride, range_gt, voxel_size, n, h, w, g,
@@ -2379,6 +2388,7 @@ GNBV_API int gnbv_update_occ_grid_packed(const float *depth_raw, const float *se
     const int64_t g3 = (int64_t)g * g * g;
     GNBV_CHECK_ARG(g3 < (1ll << 31) && tri_row_stride >= g3 && (int64_t)h * w < (1ll << 31));
     GNBV_CHECK_ARG(workspace_bytes >= gnbv_voxel_workspace_bytes(n, g) && ((uintptr_t)workspace & 255) == 0);
+    GNBV_CHECK_ARG(camera_rows_aligned(depth_raw, seg_raw, h, w));
     hipStream_t st = gnbv_stream(stream);
     VoxelWorkspace ws = carve(workspace, workspace_bytes, n, g, h, w);
     return update_packed_range(depth_raw, seg_raw, c2w, inv_intri, poses_xyz, poses_row_stride, range_gt, voxel_size, gt_bits, reset_mask, 0,
@@ -2422,6 +2432,8 @@ GNBV_API int gnbv_update_occ_grid_coded(const float *depth_raw, const float *seg
     const int64_t g3 = (int64_t)g * g * g;
     GNBV_CHECK_ARG(g3 < (1ll << 31) && (tri_out == nullptr || tri_row_stride >= g3) && (int64_t)h * w < (1ll << 31));
     GNBV_CHECK_ARG(workspace_bytes >= gnbv_voxel_workspace_bytes(n, g) && ((uintptr_t)workspace & 255) == 0);
+    GNBV_CHECK_ARG(camera_rows_aligned(depth_raw, seg_raw, h, w));
+    GNBV_CHECK_ARG(tri_i8 == nullptr || tri_i8_row_stride >= g3);  // (before any launch: a refused call leaves the workspace alone)
     hipStream_t st = gnbv_stream(stream);
     VoxelWorkspace ws = carve(workspace, workspace_bytes, n, g, h, w);
     const bool clean = (workspace_flags & GNBV_VOXEL_WS_CLEAN) != 0;
@@ -2430,7 +2442,6 @@ GNBV_API int gnbv_update_occ_grid_coded(const float *depth_raw, const float *seg
                            depth_sense_dist, coverage_count, ws, st, clean, &lists);
     if (err) return err;
     const int leave_clean = (clean && lists) ? 1 : 0;  // (the two-launch mask kernels zero what they need themselves)
-    GNBV_CHECK_ARG(tri_i8 == nullptr || tri_i8_row_stride >= g3);
     const bool vec4 = (g3 % 4 == 0) && (tri_out == nullptr || ((tri_row_stride % 4 == 0) && (((uintptr_t)tri_out & 15) == 0))) &&
                       (((uintptr_t)prob_code & 3) == 0) && (tri_i8 == nullptr || ((((uintptr_t)tri_i8 | (uintptr_t)tri_i8_row_stride) & 3) == 0));
     const bool vec16 = tri_out == nullptr && (g3 % 16 == 0) && (((uintptr_t)prob_code & 15) == 0) &&

@@ -78,7 +78,13 @@ int gnbv_grid_tri_cls(const float *grid_prob, int64_t count, float threshold_occ
 /*   One call = one environment step for all N envs, three launches:           */
 /*     hit-mask scatter (LDS-staged bitmask) -> ray cast (LDS path bitmask)     */
 /*     -> streaming grid update.                                                */
-/*   depth_raw / seg_raw are the RAW camera tensors (A1 is fused).              */
+/*   depth_raw / seg_raw are the RAW camera tensors (A1 is fused).  When        */
+/*   w % 4 == 0 (and h*w < 2^23) the kernels fetch four pixels of a row per     */
+/*   16-byte request: both pointers must then be 16-byte aligned, a call with   */
+/*   another pointer is refused (all three entry points; no other argument is   */
+/*   fetched wider than its element unless the call has checked its alignment). */
+/*   A refused call (non-zero return for an argument) launches nothing and      */
+/*   leaves the workspace as it was.                                            */
 /*   reset_mask [N] u8 or NULL: env rows whose prob/scanned grids are treated   */
 /*   as zero before the update (reset_idx :416-420 folded into the next step).  */
 /*   tri_out: row e starts at tri_out + e*tri_row_stride (floats) so the        */
@@ -91,7 +97,8 @@ int gnbv_grid_tri_cls(const float *grid_prob, int64_t count, float threshold_occ
 size_t gnbv_voxel_workspace_bytes(int n, int g);
 /* The same two bitmask arrays + per-env ray lists (one int32 per distinct hit voxel and image chunk, capacity h*w per
  * env): with a workspace of at least this size the update runs the hit-list + load-balanced ray-cast launches
- * (csrc/voxel.hip: k_hit_list, k_ray_list; grids whose bitmask fits no workgroup's LDS -- G > 104 -- k_hit_atomic, k_ray_slab); with
+ * (csrc/voxel.hip: k_hit_list, k_ray_list; grids whose hit mask, word list and pixel queue do not fit a workgroup's 160 KiB of LDS
+ * together -- G > 93 -- k_hit_atomic, k_ray_slab); with
  * the smaller mask-only workspace it falls back to k_hit_mask + k_raycast.
  * Same results either way. */
 size_t gnbv_voxel_workspace_bytes_hw(int n, int g, int h, int w);
