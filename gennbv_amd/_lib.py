@@ -57,6 +57,10 @@ SIGNATURES = {
     "gnbv_collide_cylinder": (_i, [_p, _p, _p, _i64, _f, _f, _i, _p, _p]),
     "gnbv_collide_cylinder_batch": (_i, [_p, _p, _p, _i, _i64, _f, _f, _i, _p, _p]),
     "gnbv_sweep_sphere": (_i, [_p, _p, _i64, _i64, _p, _i, _i64, _f, _i, _p, _i, _p, _p]),
+    "gnbv_flight_lds_max_nodes": (_i, []),
+    "gnbv_flight_field": (_i, [_p, _i, _i, _i, _i, _p, _p, _i64, _p, _p, _p, _p, _i, _p]),
+    "gnbv_flight_query": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _i, _i64, _p, _p]),
+    "gnbv_flight_path": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _i64, _p, _i, _p, _p]),
     "gnbv_rollout_add": (_i, [_i, _i, _p, _p, _p, _p, _i, _f, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "gnbv_input_autocorr_row_ints": (_i, []),
     "gnbv_input_autocorr": (_i, [_p, _i64, _i, _i, _p, _i64, _p]),

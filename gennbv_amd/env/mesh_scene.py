@@ -235,6 +235,40 @@ class MeshScene:
                    "gnbv_sweep_sphere")
         return out
 
+    def flight_blocked(self, lattice, body, chunk: int = 1 << 18) -> torch.Tensor:
+        """The free set of the flight search (env/flight.py FlightLattice, csrc/flight.hip): int32 [N, ceil(M / 32)], bit c of
+        env e set iff the sphere of radius rho = (body.path_radius + |h| / 2) (1 + 2^-20) at node c is NOT free -- some closed
+        triangle of env e lies within rho of the node, or the node lies inside a closed object, or (body.ground) z - rho <= 0.
+        Padding bits are set.
+
+        The inflation by |h| / 2 (h = the node spacing per axis) is the whole soundness argument of a lattice route: every point
+        of an edge between two 26-adjacent nodes is within |h| / 2 of one of them, and every lattice pose is within |h| / 2 of its
+        nearest node, so the sphere of radius path_radius flown pose -> nearest node -> free neighbours -> nearest node -> pose
+        never leaves the inflated spheres of free nodes.  Conservative: gaps narrower than 2 rho are closed; no route passes that
+        the swept sphere could not fly.  (1 + 2^-20 covers the rounding of rho and of the node positions to fp32.)
+
+        Built once per scene set, in chunks of `chunk` (env, node) items, from the predicates that exist: the zero-length
+        flight of sweep_candidates with sweep_radius = rho (PATH / PATH_GROUND), and the SURFACE / INSIDE bits of
+        collide_candidates for the body at the node.  On the GPU only."""
+        import dataclasses
+
+        from .flight import pack_bits
+        if self.device.type != "cuda":
+            raise _lib.GennbvHipError("MeshScene.flight_blocked runs on the GPU only (no CPU fallback): build the MeshScene on a cuda device")
+        n, m = self.num_envs, int(lattice.num_nodes)
+        ball = dataclasses.replace(body, sweep=True, sweep_radius=lattice.inflated_radius(body))
+        here = dataclasses.replace(body, ground=False)
+        nodes = torch.zeros(m, 6, dtype=torch.float32, device=self.device)
+        nodes[:, :3] = torch.as_tensor(lattice.node_positions(), device=self.device).to(torch.float32)
+        blocked = torch.empty(n, m, dtype=torch.bool, device=self.device)
+        step = max(1, int(chunk) // n)
+        for c0 in range(0, m, step):
+            rows = nodes[c0:c0 + step].unsqueeze(0).expand(n, -1, -1).contiguous()
+            path = self.sweep_candidates(rows, rows, ball)
+            pose = self.collide_candidates(rows, here)
+            blocked[:, c0:c0 + step] = ((path & 24) | (pose & 3)) != 0
+        return pack_bits(blocked, lattice.words)
+
     # ------------------------------------------------------------------
     @staticmethod
     def from_boxes(scene: S.Scene, device=None) -> "MeshScene":

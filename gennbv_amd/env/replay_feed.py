@@ -27,6 +27,14 @@ mesh is `collision_mesh`, by default the RenderFeed's own.  With `collision.swee
 the straight flight from the previous pose to the step's pose is tested too
 (MeshScene.sweep, csrc/sweep.hip): its path bits are ORed into `collision_buf`,
 except on the first step of an episode, whose pose is set, not flown to.
+
+`flight=FlightField(...)` (ops/flight_field.py; needs `collision.sweep`) lets the drone fly round what blocks the straight
+line: a step whose straight flight is blocked but whose detour over the flight lattice from the previous pose is finite has
+its PATH / PATH_GROUND bits cleared before the post-step kernel (pose bits are untouched), and `flight_length` [N] f32 counts
+the metres flown in the episode: the straight distance where the straight flight was free, the detour length otherwise
+(nothing for a flight with no route: it ends the episode), reset to 0 by the step that sets an episode's first pose -- so
+after the step that ends an episode it still holds that episode's length.  The field is computed once per step from the
+poses the env has just arrived at and kept in `env.flight`: the next step's check and the planners' queries both read it.
 """
 from __future__ import annotations
 
@@ -104,7 +112,7 @@ class ReplayFeedEnv:
 
     def __init__(self, cfg: TaskConfig, scene: S.Scene, feed, device="cuda:0",
                  max_episode_length: Optional[int] = None, inv_intrinsics: Optional[torch.Tensor] = None,
-                 collision=None, collision_mesh=None):
+                 collision=None, collision_mesh=None, flight=None):
         self.lib = _lib.load()
         self.cfg = cfg
         self.device = torch.device(device)
@@ -131,6 +139,15 @@ class ReplayFeedEnv:
             self.collision_buf = torch.zeros(n, dtype=torch.uint8, device=self.device)
         self._sweep = collision is not None and bool(getattr(collision, "sweep", False))
         self._prev_poses = None  # the poses before the step's head overwrites them (collision.sweep only)
+        # detours round a blocked straight flight (module docstring): None keeps every launch of the env as it was
+        if flight is not None:
+            if not self._sweep:
+                raise ValueError("flight needs collision=CollisionBody(sweep=True): without the swept path there is nothing to fly round")
+            if flight.num_envs != n:
+                raise ValueError(f"flight must hold {n} envs, got {flight.num_envs}")
+        self.flight = flight
+        self.flight_length = torch.zeros(n, dtype=torch.float32, device=self.device) if flight is not None else None
+        self.path_code = torch.zeros(n, dtype=torch.uint8, device=self.device) if flight is not None else None
         self.grid_size = cfg.grid_size
         self.max_episode_length = int(cfg.max_episode_length if max_episode_length is None else max_episode_length)
         self.max_episode_length_s = cfg.episode_length_s
@@ -293,9 +310,27 @@ class ReplayFeedEnv:
         """collision_buf = the body at the step's poses, and with `collision.sweep` | the flight from the previous poses to
         them (episode_length_buf <= 1 after the step's head: the first pose of an episode, not flown to)."""
         self.collision_mesh.collide(self.poses, self.collision, out=self.collision_buf)
-        if self._sweep:
+        if self.flight is not None:
+            self._fly_step()
+        elif self._sweep:
             self.collision_mesh.sweep_candidates(self._prev_poses, self.poses.unsqueeze(1), self.collision, self.episode_length_buf,
                                                  out=self.collision_buf.unsqueeze(1), accumulate=True)
+
+    def _fly_step(self):
+        """The sweep of _collide_step with detours: the path bits of a blocked straight flight are dropped where `flight` (the
+        field from the previous poses) holds a finite route to the step's poses; flight_length follows; then the one field
+        launch of the step, from the poses just arrived at."""
+        fl, poses, prev = self.flight, self.poses, self._prev_poses
+        code = self.collision_mesh.sweep_candidates(prev, poses.unsqueeze(1), self.collision, self.episode_length_buf,
+                                                    out=self.path_code.unsqueeze(1))[:, 0]
+        detour = fl.cost(poses.unsqueeze(1))[:, 0]
+        blocked, routed = code != 0, torch.isfinite(detour)
+        self.collision_buf |= torch.where(blocked & routed, torch.zeros_like(code), code)
+        straight = (poses[:, :3] - prev[:, :3]).norm(dim=-1)
+        flown = torch.where(blocked, torch.where(routed, detour, torch.zeros_like(detour)), straight)
+        first = self.episode_length_buf <= 1  # after the step's head: the pose was set, not flown to
+        self.flight_length.copy_(torch.where(first, torch.zeros_like(flown), self.flight_length + flown))
+        fl.update(poses)
 
     def _rgba_or_zero(self, rgba):
         if rgba is None:

@@ -68,6 +68,24 @@ def _sweeps(env) -> bool:
     return bool(getattr(getattr(env, "collision", None), "sweep", False))
 
 
+def candidate_contact(env, poses: torch.Tensor, out: torch.Tensor, sweep: bool, static: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The planners' "contact | sweep" block: out [N,K] u8 = the body at poses [N,K,6] (collide_candidates; or a copy of
+    `static`, a contact computed before) and, with `sweep`, | the path code of the straight flight from env.poses to each pose.
+    Where the env flies detours (`env.flight`, ops/flight_field.py) a candidate is refused for its path only if its straight
+    flight is blocked AND no route over the flight lattice reaches it: the path bits of a candidate with a finite detour cost
+    are dropped.  Without `env.flight` the launches are the ones the planners always made."""
+    mesh, body = env.collision_mesh, env.collision
+    contact = mesh.collide_candidates(poses, body, out=out) if static is None else out.copy_(static)
+    if sweep:
+        flight = getattr(env, "flight", None)
+        if flight is None:
+            mesh.sweep_candidates(env.poses, poses, body, out=contact, accumulate=True)
+        else:
+            path = mesh.sweep_candidates(env.poses, poses, body)
+            contact |= torch.where(flight.reachable(poses), torch.zeros_like(path), path)
+    return contact
+
+
 def choose(gain: torch.Tensor, weights: Sequence[int], contact: Optional[torch.Tensor] = None) -> torch.Tensor:
     """gain [N,K,3] int -> index [N] of the candidate with the largest w0 * unknown + w1 * unknown_hit (int64); candidates
     with contact[N,K] != 0 score -1; ties go to the lowest candidate index."""
@@ -85,7 +103,8 @@ class GreedyGainPolicy:
     w0 * unknown + w1 * unknown_hit of the view gain against the observation's grid wins; with a CollisionBody on the
     env (and `avoid_collisions`) candidates whose pose collides are never chosen unless all do; where that body has `sweep`,
     a candidate whose straight flight from `env.poses` is blocked (MeshScene.sweep_candidates, accumulated into the same
-    contact buffer) counts exactly like one in contact -- that needs a collision mesh with `sweep_candidates`.  No host
+    contact buffer) counts exactly like one in contact -- that needs a collision mesh with `sweep_candidates`; where the env also
+    flies detours (`env.flight`) only a candidate that no route reaches is refused for its path (`candidate_contact`).  No host
     synchronisation inside a decision.  `gain_backend(tri [N,G^3], poses [N,K,6]) -> gain [N,K,3]` replaces the kernel in
     tests only: the product path has no CPU fallback."""
 
@@ -122,9 +141,7 @@ class GreedyGainPolicy:
             if hasattr(mesh, "collide_candidates"):  # all N x K poses in one launch
                 if self._contact is None:
                     self._contact = torch.zeros(n, k, dtype=torch.uint8, device=obs.device)
-                contact = mesh.collide_candidates(poses, self.env.collision, out=self._contact)
-                if self.sweep:  # | the flight from the current pose, into the same buffer
-                    mesh.sweep_candidates(self.env.poses, poses, self.env.collision, out=self._contact, accumulate=True)
+                contact = candidate_contact(self.env, poses, self._contact, self.sweep)  # | the flight from the current pose
             else:
                 if self._contact is None:
                     self._contact = torch.zeros(k, n, dtype=torch.uint8, device=obs.device)
@@ -149,7 +166,8 @@ class OracleGainPolicy:
     `.scanned_bits`), i.e. at stride 1 exactly the coverage_count increment the env pays for the step.  It reads the scene
     geometry and the ground truth, which no deployable planner has.  Ties go to the lowest candidate index; with a
     CollisionBody on the env (and `avoid_collisions`) candidates whose pose collides are never chosen unless all do, and
-    where that body has `sweep` neither are candidates whose straight flight from `env.poses` is blocked.
+    where that body has `sweep` neither are candidates whose straight flight from `env.poses` is blocked (with `env.flight`:
+    blocked and reached by no route, `candidate_contact`).
     `last_cover` [N,K,3] keeps the last decision's integers.  No host synchronisation inside a decision.  It needs the
     packed updater (a binary ground truth) and a closed-loop feed with a mesh; anything else is refused.
     `cover_backend(poses [N,K,6], gt_bits, scanned_bits) -> cover [N,K,3]` replaces the kernel in tests only: the product
@@ -192,9 +210,7 @@ class OracleGainPolicy:
         if self.avoid_collisions:
             if self._contact is None:
                 self._contact = torch.zeros(n, k, dtype=torch.uint8, device=obs.device)
-            contact = self.env.collision_mesh.collide_candidates(poses, self.env.collision, out=self._contact)
-            if self.sweep:
-                self.env.collision_mesh.sweep_candidates(self.env.poses, poses, self.env.collision, out=self._contact, accumulate=True)
+            contact = candidate_contact(self.env, poses, self._contact, self.sweep)
         best = choose(cover, (1, 0), contact)
         return cand[torch.arange(n, device=cand.device), best], None, None
 
@@ -214,7 +230,8 @@ class PoolCoverPolicy:
     (for envs that were not reset, as OracleGainPolicy).  Ties go to the lowest pool index; with a CollisionBody on the env (and
     `avoid_collisions`) pool views whose pose collides are never chosen unless all do; where that body has `sweep`, every
     decision also ORs the flight from `env.poses` to each pool pose into a copy of the pool's static contact (one copy, one
-    sweep launch) and hands it to the selection -- the carried bounds stay valid, a bound does not depend on contact.
+    sweep launch; with `env.flight` only for pool views no route reaches, `candidate_contact`) and hands it to the selection --
+    the carried bounds stay valid, a bound does not depend on contact.
     `last_choice` [N] is the pool index.
     `persistent_bounds`: every candidate's last gain is kept as an upper bound for the next decision (gains only shrink
     while the scanned set grows), so a decision evaluates only the candidates that can still win; an env whose episode has
@@ -259,8 +276,7 @@ class PoolCoverPolicy:
             self._ub.masked_fill_((env.episode_length_buf <= 1).unsqueeze(1), self._unknown)
         contact = None
         if self.sweep:  # the static contact | the flight from the current pose to each pool pose
-            contact = self._contact.copy_(self.pool.contact)
-            env.collision_mesh.sweep_candidates(env.poses, self.pool.poses, env.collision, out=contact, accumulate=True)
+            contact = candidate_contact(env, self.pool.poses, self._contact, True, static=self.pool.contact)
         choice, gain = self.pool.select(env.updater.scanned_bits, self._ub, contact)
         self.last_choice, self.last_gain = choice, gain
         return self.pool_actions[self._rows, choice.long()], None, None

@@ -1,0 +1,170 @@
+"""FlightField: the shortest collision-free route over the flight lattice, per env (csrc/flight.hip).
+
+    field = FlightField(mesh, FlightLattice(cfg, stride=2), body)
+    field.update(poses)            # one launch: the distance in mm from each env's pose to every lattice node
+    field.cost(targets)            # f32 [N,K] metres (inf: no route), field.cost_mm(targets) the raw u32 of the nodes
+    field.path(targets)            # the waypoints of one route per env
+
+It owns the blocked bits (MeshScene.flight_blocked: built once from the mesh) and the field [N, M] u32.  A route goes
+pose -> its nearest node -> free 26-neighbours -> the target's nearest node -> target; `cost` is the integer lattice distance
+in metres plus the two stub legs pose <-> node.  Every leg is flyable by the sphere of radius body.path_radius (env/flight.py
+has the argument).  `mode`: 0 auto, 1 the field resident in LDS (refused where it does not fit), 2 the field in global memory.
+The sweep count of the field kernel has a hard cap; an env that hit it is reported lazily, by `check()` (one read-back) and
+by `path()`, the way ScanAccumulator reports its flags.  GPU only.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional, Tuple
+
+import numpy as np
+import torch
+
+from .. import _lib
+from ..env.flight import INF_MM
+
+
+class FlightField:
+    def __init__(self, mesh, lattice, body, mode: int = 0, blocked: Optional[torch.Tensor] = None):
+        if mesh.device.type != "cuda":
+            raise _lib.GennbvHipError("FlightField runs on the GPU only (no CPU fallback): build the MeshScene on a cuda device")
+        if int(mode) not in (0, 1, 2):
+            raise ValueError(f"FlightField: mode must be 0, 1 or 2, got {mode}")
+        self.lib = _lib.load()
+        self.mesh, self.lattice, self.body, self.mode = mesh, lattice, body, int(mode)
+        self.device = mesh.device
+        self.num_envs = n = int(mesh.num_envs)
+        m = int(lattice.num_nodes)
+        if self.mode == 1 and m > int(self.lib.gnbv_flight_lds_max_nodes()):
+            raise _lib.GennbvHipError(f"FlightField: a field of {m} nodes does not fit LDS (mode 1)")
+        self.blocked = mesh.flight_blocked(lattice, body) if blocked is None else blocked
+        assert self.blocked.dtype == torch.int32 and self.blocked.shape == (n, lattice.words) and self.blocked.is_contiguous()
+        _lib.require_cuda(self.blocked)
+        self.field = torch.full((n, m), -1, dtype=torch.int32, device=self.device)  # u32 bits; all INF_MM until update()
+        self.status = torch.zeros(n, dtype=torch.int32, device=self.device)
+        self.source = torch.full((n, 3), float("nan"), dtype=torch.float32, device=self.device)  # the poses of the last update
+        self._cost = (C.c_uint32 * 8)(*[int(c) for c in lattice.cost])
+        self._lo = (C.c_double * 3)(*[float(v) for v in lattice.lo])
+        self._h = (C.c_double * 3)(*[float(v) for v in lattice.h])
+        self.launches = 0  # field launches so far
+
+    # ------------------------------------------------------------------
+    def update(self, poses: torch.Tensor) -> "FlightField":
+        """gnbv_flight_field on the current stream from poses [N, >= 3] f32 (unit element stride)."""
+        n = self.num_envs
+        _lib.require_cuda(poses)
+        assert poses.dtype == torch.float32 and poses.dim() == 2 and poses.shape[0] == n and poses.shape[1] >= 3 and poses.stride(1) == 1
+        nx, ny, nz = self.lattice.dims
+        self.source.copy_(poses[:, :3])
+        _lib.check(self.lib.gnbv_flight_field(self.blocked.data_ptr(), n, nx, ny, nz, self._cost, poses.data_ptr(), max(int(poses.stride(0)), 3),
+                                              self._lo, self._h, self.field.data_ptr(), self.status.data_ptr(), self.mode,
+                                              _lib.stream_ptr(self.device)), "gnbv_flight_field")
+        self.launches += 1
+        return self
+
+    def check(self):
+        """Raise if the field kernel's sweep cap ended an env's relaxation (one device -> host copy)."""
+        bad = torch.nonzero(self.status).flatten().tolist()
+        if bad:
+            raise _lib.GennbvHipError(f"FlightField: the relaxation of envs {bad[:8]} hit the sweep cap; their fields are not settled")
+
+    def _targets(self, targets: torch.Tensor):
+        n = self.num_envs
+        _lib.require_cuda(targets)
+        assert targets.dtype == torch.float32 and targets.dim() == 3 and targets.shape[0] == n and targets.shape[2] >= 3 and targets.stride(2) == 1
+        k = int(targets.shape[1])
+        if k > 1 and n > 1 and targets.stride(0) != k * targets.stride(1):
+            targets = targets.contiguous()
+        row = int(targets.stride(1)) if k > 1 else int(targets.stride(0))
+        if row < 3:  # a dimension of size 1 may carry any stride
+            targets, row = targets.contiguous(), int(targets.shape[2])
+        return targets, k, row
+
+    def cost_mm(self, targets: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """gnbv_flight_query: int32 [N,K] holding the u32 field value (mm) at the nearest node of targets [N, K, >= 3] f32;
+        -1 (0xFFFFFFFF) = blocked, unreachable or no node."""
+        targets, k, row = self._targets(targets)
+        n = self.num_envs
+        if out is None:
+            out = torch.empty(n, k, dtype=torch.int32, device=self.device)
+        assert out.dtype == torch.int32 and out.shape == (n, k) and out.is_contiguous()
+        nx, ny, nz = self.lattice.dims
+        _lib.check(self.lib.gnbv_flight_query(self.field.data_ptr(), n, nx, ny, nz, self._lo, self._h, targets.data_ptr(), k, row,
+                                              out.data_ptr(), _lib.stream_ptr(self.device)), "gnbv_flight_query")
+        return out
+
+    def cost(self, targets: torch.Tensor) -> torch.Tensor:
+        """f32 [N,K]: the length in metres of the route from the poses of the last update() to targets [N, K, >= 3] -- the stub
+        from the pose to its node, the lattice distance, the stub from the target's node to the target -- or inf."""
+        mm = self.cost_mm(targets)
+        lat = self.lattice
+        t = targets[..., :3].to(torch.float64)
+        s = self.source.to(torch.float64)
+        stub = (t - lat.nearest_positions(t)).norm(dim=-1) + (s - lat.nearest_positions(s)).norm(dim=-1)[:, None]
+        metres = (mm.to(torch.float64) * 1e-3 + stub).to(torch.float32)
+        return torch.where(mm == -1, torch.full_like(metres, float("inf")), metres)
+
+    def reachable(self, targets: torch.Tensor) -> torch.Tensor:
+        """bool [N,K]: a route exists from the poses of the last update() to each target."""
+        return self.cost_mm(targets) != -1
+
+    def path(self, targets: torch.Tensor, max_len: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """gnbv_flight_path for one target per env, targets [N, >= 3] f32 -> (waypoints f32 [N, L, 3], length int32 [N]): the
+        route from the pose of the last update() to the target, both end poses included (length = nodes + 2), rows past the
+        length NaN; length 0 and all NaN where there is no route.  Synchronises with the host (the length decides the shape);
+        not for the hot path.  Raises where an env's field is not settled."""
+        n = self.num_envs
+        _lib.require_cuda(targets)
+        assert targets.dtype == torch.float32 and targets.dim() == 2 and targets.shape[0] == n and targets.shape[1] >= 3 and targets.stride(1) == 1
+        self.check()
+        nodes, count = self.path_nodes(targets, max_len)
+        longest = max(int(count.max()), 0)
+        pos = torch.as_tensor(self.lattice.node_positions(), device=self.device).to(torch.float32)
+        way = torch.full((n, longest + 2, 3), float("nan"), dtype=torch.float32, device=self.device)
+        if longest:
+            j = torch.arange(longest, device=self.device)[None]
+            valid = j < count[:, None]
+            back = (count[:, None].long() - 1 - j).clamp(min=0)  # nodes run target -> source: waypoint 1 + j is node count - 1 - j
+            ids = nodes[:, :longest].long().gather(1, back).clamp(min=0)
+            way[:, 1:1 + longest] = torch.where(valid[..., None], pos[ids], way[:, 1:1 + longest])
+        ok = count > 0
+        way[:, 0] = torch.where(ok[:, None], self.source, way[:, 0])
+        rows = torch.nonzero(ok).flatten()
+        way[rows, 1 + count[rows].long()] = targets[rows, :3]
+        return way, torch.where(ok, count + 2, torch.zeros_like(count))
+
+    def path_into(self, targets: torch.Tensor, nodes_out: torch.Tensor, len_out: torch.Tensor):
+        """One gnbv_flight_path launch into the caller's buffers: nodes_out int32 [N, L], len_out int32 [N] (0 no route, -needed where
+        L is too short).  No host synchronisation."""
+        n = self.num_envs
+        nx, ny, nz = self.lattice.dims
+        _lib.require_cuda(targets, nodes_out, len_out)
+        assert targets.dtype == torch.float32 and targets.dim() == 2 and targets.shape[0] == n and targets.shape[1] >= 3 and targets.stride(1) == 1
+        assert nodes_out.dtype == torch.int32 and nodes_out.dim() == 2 and nodes_out.shape[0] == n and nodes_out.is_contiguous()
+        assert len_out.dtype == torch.int32 and len_out.shape == (n,) and len_out.is_contiguous()
+        _lib.check(self.lib.gnbv_flight_path(self.field.data_ptr(), n, nx, ny, nz, self._cost, self._lo, self._h, targets.data_ptr(),
+                                             max(int(targets.stride(0)), 3), nodes_out.data_ptr(), int(nodes_out.shape[1]), len_out.data_ptr(),
+                                             _lib.stream_ptr(self.device)), "gnbv_flight_path")
+
+    def path_nodes(self, targets: torch.Tensor, max_len: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The raw walk: (nodes int32 [N, L] from the target's node back to the source, count int32 [N]; 0 = no route).  Runs the
+        kernel again with a longer buffer where the first was too short (a host read-back of the counts)."""
+        n = self.num_envs
+        nx, ny, nz = self.lattice.dims
+        length = int(max_len) if max_len is not None else max(2 * (nx + ny + nz), 8)
+        while True:
+            nodes = torch.full((n, length), -1, dtype=torch.int32, device=self.device)
+            count = torch.zeros(n, dtype=torch.int32, device=self.device)
+            self.path_into(targets, nodes, count)
+            need = -int(count.min())
+            if need <= 0:
+                return nodes, count
+            length = need
+
+
+def field_u32(t: torch.Tensor) -> np.ndarray:
+    """An int32 tensor of u32 bits (field, cost_mm) as a numpy uint32 array on the host."""
+    return np.ascontiguousarray(t.detach().cpu().numpy()).view(np.uint32)
+
+
+__all__ = ["FlightField", "INF_MM", "field_u32"]

@@ -279,6 +279,43 @@ int gnbv_sweep_sphere(const GnbvMeshScene *scene /*[host]*/, const float *from, 
                       float radius, int ground, const int64_t *episode_length /*[N] or NULL*/, int accumulate,
                       uint8_t *contact_out /*[N,K]*/, void *stream);
 
+/* Collision-free flight between views (new entry points of ABI 5): the shortest 26-connected route over the flight lattice.
+ * The lattice has nx * ny * nz = M nodes (each axis 1..1024), node (i, j, k) at lo + h * (i, j, k), flat id c = (k ny + j) nx + i,
+ * the same for every env (gennbv_amd/env/flight.py).  blocked [N, ceil(M / 32)] u32: bit c & 31 of word c >> 5 of env e is set
+ * where node c is not free in env e (MeshScene.flight_blocked; padding bits are not read).  Two free nodes that differ by at
+ * most one step on every axis are joined by an edge of cost[|dx| | |dy| << 1 | |dz| << 2] millimetres ([host], 8 u32, every
+ * entry the lattice can use > 0, M * max cost < 2^32 - 2): all distances are integer sums, so the result is exact and does not
+ * depend on the order of evaluation.  The nearest node of a pose is, per axis, clamp(floor((p - lo) / h + 0.5), 0, n - 1) in
+ * fp64 (0 on an axis with one node); a pose with a non-finite x, y or z has no node.  lo, h [host] 3 doubles, finite, h > 0 on
+ * every axis with more than one node.  No allocation, no host synchronisation; bad arguments return hipErrorInvalidValue. */
+
+/* The most nodes whose field fits the LDS of one CU (mode 1 of gnbv_flight_field): (160 KiB - 16) / 4 = 40956. */
+int gnbv_flight_lds_max_nodes(void);
+/* field_out[e, c] = the length in mm of the shortest route from the nearest node of poses[e] (row stride in floats, >= 3) to
+ * node c through free nodes; the source holds 0; blocked and unreachable nodes hold 0xFFFFFFFF, and so does every node of an env
+ * whose source node is blocked or absent.  One workgroup per env relaxes the table in place until a sweep changes nothing.
+ * mode: 0 auto (1 where M <= gnbv_flight_lds_max_nodes(), else 2), 1 the table resident in LDS (hipErrorInvalidValue where it does
+ * not fit), 2 the table in field_out itself; the result is the same.  status_out[e] = 0, or 1 where the sweep count reached its
+ * hard cap M before the table settled (it cannot: Bellman-Ford needs fewer than M sweeps; the cap bounds the loop whatever
+ * happens, and the field of such an env is not to be used). */
+int gnbv_flight_field(const uint32_t *blocked /*[N,ceil(M/32)]*/, int n, int nx, int ny, int nz, const uint32_t *cost /*[host] 8*/,
+                      const float *poses, int64_t poses_row_stride /*floats*/, const double *lo /*[host] 3*/,
+                      const double *h /*[host] 3*/, uint32_t *field_out /*[N,M]*/, int32_t *status_out /*[N]*/, int mode, void *stream);
+/* cost_mm_out[e, j] = field[e, nearest node of targets (e, j)], 0xFFFFFFFF for a target without a node.  targets [N, K, >= 3] with
+ * the stride between consecutive (e, j) rows in floats (>= 3); k >= 1, N * k <= 2^31 - 1. */
+int gnbv_flight_query(const uint32_t *field /*[N,M]*/, int n, int nx, int ny, int nz, const double *lo /*[host] 3*/,
+                      const double *h /*[host] 3*/, const float *targets, int k, int64_t targets_row_stride /*floats*/,
+                      uint32_t *cost_mm_out /*[N,K]*/, void *stream);
+/* The route of one target per env (targets [N, >= 3], row stride in floats), as node ids from the target's nearest node back
+ * to the source: from each node the walk takes the first neighbour, in the fixed order dz, dy, dx in (-1, 0, 1) with dx
+ * fastest, with field[neighbour] + cost == field[node].  len_out[e] = the number of nodes (1 when target and source share a
+ * node), 0 for an unreachable target, and -needed where the route has more than max_len nodes (the first max_len are
+ * written).  nodes_out [N, max_len], max_len >= 1. */
+int gnbv_flight_path(const uint32_t *field /*[N,M]*/, int n, int nx, int ny, int nz, const uint32_t *cost /*[host] 8*/,
+                     const double *lo /*[host] 3*/, const double *h /*[host] 3*/, const float *targets,
+                     int64_t targets_row_stride /*floats*/, int32_t *nodes_out /*[N,max_len]*/, int max_len, int32_t *len_out /*[N]*/,
+                     void *stream);
+
 /* compute_reward (env_train_base.py:377-398), _reward_* / check_termination /
  * reset_idx (env_train_gennbv.py:377-457,535-556), update_extra_episode_info
  * (env_train_base.py:629-639). All pointers device, arrays [N] unless noted. [host struct] */
