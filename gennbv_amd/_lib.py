@@ -109,6 +109,7 @@ SIGNATURES = {
     "gnbv_view_cover": (_i, [_p, _p, _p]),
     "gnbv_view_cover_masks": (_i, [_p, _p, _p, _p]),
     "gnbv_cover_greedy": (_i, [_p, _p]),
+    "gnbv_tour_route": (_i, [_p, _p]),
     "gnbv_gae_sb3": (_i, [_p, _p, _p, _p, _p, _i, _i, _d, _d, _p, _p, _p]),
     "gnbv_gae_rsl": (_i, [_p, _p, _p, _p, _i, _i, _d, _d, _p, _p, _p]),
 }
@@ -171,6 +172,12 @@ class GnbvCoverGreedy(C.Structure):
     """include/gennbv_hip.h: GnbvCoverGreedy"""
     _fields_ = [("n", _i), ("k", _i), ("words", _i), ("rounds", _i), ("mask_bits", _p), ("covered_in", _p), ("contact", _p),
                 ("choice", _p), ("gain", _p), ("covered_out", _p), ("gains0", _p), ("ub", _p), ("lazy", _i)]
+
+
+class GnbvTourRoute(C.Structure):
+    """include/gennbv_hip.h: GnbvTourRoute"""
+    _fields_ = [("n", _i), ("p", _i), ("dist_mm", _p), ("count", _p), ("max_moves", _i), ("order", _p), ("routed", _p),
+                ("length_mm", _p), ("status", _p)]
 
 
 class GnbvEncoderParams(C.Structure):

@@ -2,13 +2,15 @@
 next-best-view planner over the view gain (ops/view_gain.py, csrc/viewgain.hip; grids up to 128^3), the one-step
 oracle over the view coverage (ops/view_cover.py, csrc/viewcover.hip): the candidate that really adds the most
 ground-truth voxels, and the greedy set-cover planner over a fixed pool of views whose visible ground truth is cached
-as bit masks (ops/view_pool.py, csrc/covergreedy.hip).
+as bit masks (ops/view_pool.py, csrc/covergreedy.hip) -- online, or as the plan-then-fly baseline: the set-cover plan ordered
+into a short flight tour (ops/tour.py, csrc/tour.hip) and flown by TourPolicy.
 
 All speak the protocol `evaluate_policy_grid_obs` uses: `.policy(obs, deterministic=True) -> (actions, None, None)`,
 and `predict(obs)`; actions are int64 [N,6] on the lattice of the task (inside clip_pose_idx_low / clip_pose_idx_up).
 """
 from __future__ import annotations
 
+from dataclasses import dataclass
 from typing import Callable, Optional, Sequence
 
 import torch
@@ -238,7 +240,8 @@ class PoolCoverPolicy:
     just restarted (episode_length_buf <= 1 at decision time: the post-step kernel zeroes it on the done step, the next step
     forces the init action, clears the scanned set and counts 1) gets its row set back to unknown, on the device.  The
     actions are the same with and without.  `.plan(rounds)` is the offline greedy set-cover plan from the current scanned
-    set; it keeps the static contact (an offline plan has no "current pose" per round, so no flight is tested).  No host
+    set; it keeps the static contact (an offline plan has no "current pose" per round, so no flight is tested).
+    `.plan_route(rounds)` is that plan ordered into a short flight tour (RoutePlan; TourPolicy flies it).  No host
     synchronisation inside a decision.  It needs the packed updater and a closed-loop feed with a mesh, as
     OracleGainPolicy."""
 
@@ -285,6 +288,104 @@ class PoolCoverPolicy:
         """ViewPool.plan from covered_bits (default: the env's current scanned set) -> (choice [N,T], gain [N,T], covered);
         the planned actions are pool_actions[e, choice[e, t]].  The plan keeps the static contact: no flight is tested."""
         return self.pool.plan(rounds, self.env.updater.scanned_bits if covered_bits is None else covered_bits, lazy)
+
+    def plan_route(self, rounds: int, start: Optional[torch.Tensor] = None, covered_bits: Optional[torch.Tensor] = None) -> "RoutePlan":
+        """Plan, then route: `plan(rounds, covered_bits)`, keep the rounds with gain > 0 whose view is not in static contact (a
+        repeat has gain 0, so the kept views are distinct), and order them into a short open flight tour from `start` [N, >= 3]
+        (default: env.poses).  The legs come from `env.flight.pairwise_mm` (shortest collision-free routes, mm) where the env has
+        a flight field, from `euclid_mm` (straight flights) otherwise; the order from `route_tour` (nearest neighbour + 2-opt,
+        csrc/tour.hip).  A kept view that no route reaches from the start is left out of the tour.  No host synchronisation."""
+        from .. import _lib
+        from ..ops.tour import MAX_POINTS, euclid_mm, route_tour
+        rounds = int(rounds)
+        if not 1 <= rounds <= MAX_POINTS - 1:
+            raise _lib.GennbvHipError(f"PoolCoverPolicy.plan_route: rounds in 1..{MAX_POINTS - 1} (the start and the views are {MAX_POINTS} "
+                                      f"points at most), got {rounds}")
+        env, n, dev = self.env, self.num_envs, self.env.device
+        choice, gain, _ = self.plan(rounds, covered_bits)
+        choice64 = choice.long()
+        keep = gain > 0
+        if self.pool.contact is not None:
+            keep &= self.pool.contact.gather(1, choice64) == 0
+        # the kept rounds to the front, in plan order: a stable sort on a 0 / 1 key
+        front = torch.sort((~keep).to(torch.uint8), dim=1, stable=True)[1]
+        views = choice64.gather(1, front)  # [N, T] pool indices; the first `kept` are the kept views
+        count = (keep.sum(dim=1) + 1).to(torch.int32)
+        start = env.poses if start is None else start
+        if start.dim() != 2 or start.shape[0] != n or start.shape[1] < 3:
+            raise _lib.GennbvHipError(f"PoolCoverPolicy.plan_route: start must be [{n}, >= 3], got {tuple(start.shape)}")
+        points = torch.empty(n, rounds + 1, 3, dtype=torch.float32, device=dev)
+        points[:, 0] = start[:, :3]
+        points[:, 1:] = self.pool.poses[..., :3].gather(1, views[..., None].expand(-1, -1, 3))
+        flight = getattr(env, "flight", None)
+        dist = flight.pairwise_mm(points, count) if flight is not None else euclid_mm(points, count)
+        res = route_tour(dist, count)
+        # the routed views in flight order; the tail repeats the last one; the init action where nothing is routed
+        routed = res.routed.long()
+        slot = torch.minimum(torch.arange(1, rounds + 1, device=dev)[None], (routed - 1)[:, None])
+        point = res.order.long().gather(1, slot)
+        view = views.gather(1, (point - 1).clamp(min=0))
+        actions = self.pool_actions.gather(1, view[..., None].expand(-1, -1, 6))
+        init = torch.tensor(self.cfg.init_action, dtype=torch.int64, device=dev)
+        actions = torch.where((routed > 1)[:, None, None], actions, init.expand_as(actions))
+        # the same views in the plan's own order: the route points in ascending index (the compaction kept the plan order)
+        p = rounds + 1
+        ranks = torch.arange(p, device=dev)[None]
+        member = torch.zeros(n, p, dtype=torch.bool, device=dev).scatter_(1, res.order.long(), ranks < routed[:, None])
+        seq = torch.sort((~member).to(torch.uint8), dim=1, stable=True)[1]
+        legs = (dist.long() & 0xFFFFFFFF).flatten(1).gather(1, seq[:, :-1] * p + seq[:, 1:])
+        flown = ranks[:, :-1] < (routed - 1)[:, None]
+        missing = (flown & (legs == 0xFFFFFFFF)).any(dim=1)
+        plan_len = torch.where(missing, torch.full_like(routed, -1), torch.where(flown, legs, torch.zeros_like(legs)).sum(dim=1))
+        plan_view = views.gather(1, (seq.gather(1, slot) - 1).clamp(min=0))
+        plan_actions = self.pool_actions.gather(1, plan_view[..., None].expand(-1, -1, 6))
+        plan_actions = torch.where((routed > 1)[:, None, None], plan_actions, init.expand_as(plan_actions))
+        return RoutePlan(actions=actions, views=(routed - 1).to(torch.int32), length_mm=res.length_mm.clone(), plan_length_mm=plan_len,
+                         status=res.status.clone(), choice=choice.clone(), gain=gain.clone(), plan_actions=plan_actions)
+
+    @property
+    def policy(self):
+        return self
+
+    def predict(self, obs, state=None, episode_start=None, deterministic: bool = True):
+        return self(obs, deterministic)[0], state
+
+
+@dataclass
+class RoutePlan:
+    """PoolCoverPolicy.plan_route's result (tensors on the env's device)."""
+    actions: torch.Tensor         # int64 [N, T, 6]: the routed views' pool actions in flight order; the tail repeats the last routed
+    #                               view; cfg.init_action where nothing is routed
+    views: torch.Tensor           # int32 [N]: routed views (the start not counted)
+    length_mm: torch.Tensor       # int64 [N]: the length of the tour, start -> views in flight order
+    plan_length_mm: torch.Tensor  # int64 [N]: the same views flown in the plan's gain order, from the same matrix; -1: a missing leg
+    status: torch.Tensor          # int32 [N]: gnbv_tour_route's status bits
+    choice: torch.Tensor          # int32 [N, T]: the plan's pool indices, in gain order
+    gain: torch.Tensor            # int32 [N, T]: the plan's gains
+    plan_actions: torch.Tensor    # int64 [N, T, 6]: the routed views in the plan's gain order (what plan_length_mm measures), same tail
+
+
+class TourPolicy:
+    """Plan-then-fly: the greedy set-cover plan of `pool_policy` (a PoolCoverPolicy on `env`) over `rounds` views, ordered into a
+    short flight tour and flown view by view -- the classic offline coverage-planning baseline ("how many metres for this
+    coverage, for a planner that knows the scene?", against `env.flight_length`).  The plan is computed once, at construction,
+    from an empty covered set and the task's init pose (`poses_from_actions(cfg.init_action)`): scene, pool, init pose and empty
+    scanned set are the same at every episode start, so one plan serves every episode.  A decision for an env with
+    episode_length_buf == t >= 1 is `last_plan.actions[e, min(t, rounds) - 1]`: view t of the tour, the last view once the tour
+    is flown; at t == 0 the env has just finished and the next step forces the init action whatever is chosen.  One gather per
+    decision, no host synchronisation."""
+
+    def __init__(self, env, pool_policy: PoolCoverPolicy, rounds: int):
+        self.env, self.cfg, self.pool_policy, self.rounds = env, env.cfg, pool_policy, int(rounds)
+        self.num_envs = n = int(env.num_envs)
+        init = torch.tensor(self.cfg.init_action, dtype=torch.int64, device=env.device).repeat(n, 1)
+        start = S.poses_from_actions(init, self.cfg).float()
+        self.last_plan = pool_policy.plan_route(self.rounds, start=start, covered_bits=torch.zeros_like(env.updater.scanned_bits))
+        self._rows = torch.arange(n, device=env.device)
+
+    def __call__(self, obs, deterministic: bool = True):
+        slot = (self.env.episode_length_buf.clamp(min=1, max=self.rounds) - 1)
+        return self.last_plan.actions[self._rows, slot], None, None
 
     @property
     def policy(self):

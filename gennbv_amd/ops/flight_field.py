@@ -4,6 +4,7 @@
     field.update(poses)            # one launch: the distance in mm from each env's pose to every lattice node
     field.cost(targets)            # f32 [N,K] metres (inf: no route), field.cost_mm(targets) the raw u32 of the nodes
     field.path(targets)            # the waypoints of one route per env
+    field.pairwise_mm(points)      # int32 [N,P,P] u32 mm between every two of P points (a private field: update() state untouched)
 
 It owns the blocked bits (MeshScene.flight_blocked: built once from the mesh) and the field [N, M] u32.  A route goes
 pose -> its nearest node -> free 26-neighbours -> the target's nearest node -> target; `cost` is the integer lattice distance
@@ -47,6 +48,8 @@ class FlightField:
         self._lo = (C.c_double * 3)(*[float(v) for v in lattice.lo])
         self._h = (C.c_double * 3)(*[float(v) for v in lattice.h])
         self.launches = 0  # field launches so far
+        # pairwise_mm: its private field (shares `blocked`), its sticky device flags (1 sweep cap, 2 a sum too wide), its buffers per P
+        self._pair, self._pair_status, self._pair_rows, self._pair_out = None, None, {}, {}
 
     # ------------------------------------------------------------------
     def update(self, poses: torch.Tensor) -> "FlightField":
@@ -63,10 +66,71 @@ class FlightField:
         return self
 
     def check(self):
-        """Raise if the field kernel's sweep cap ended an env's relaxation (one device -> host copy)."""
+        """Raise if the field kernel's sweep cap ended an env's relaxation (one device -> host copy), here or in a field of
+        pairwise_mm, or if a pairwise_mm sum did not fit."""
         bad = torch.nonzero(self.status).flatten().tolist()
         if bad:
             raise _lib.GennbvHipError(f"FlightField: the relaxation of envs {bad[:8]} hit the sweep cap; their fields are not settled")
+        if self._pair_status is not None:
+            st = self._pair_status.tolist()
+            capped, wide = [e for e, s in enumerate(st) if s & 1], [e for e, s in enumerate(st) if s & 2]
+            if capped:
+                raise _lib.GennbvHipError(f"FlightField.pairwise_mm: the relaxation of envs {capped[:8]} hit the sweep cap")
+            if wide:
+                raise _lib.GennbvHipError(f"FlightField.pairwise_mm: a route of envs {wide[:8]} with its stubs does not fit 32 bits of "
+                                          "millimetres (entries set to 0xFFFFFFFF)")
+
+    def pairwise_mm(self, points: torch.Tensor, count: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """int32 [N,P,P] of u32 bits: the length in mm of the shortest route between every two of points [N, P, >= 3] f32.
+        Inside count[e] (int32 [N], 1..P; None: P):  out[e,a,a] = 0;  out[e,a,b] = field_mm(node(a) -> node(b)) + stub(a) + stub(b),
+        stub(p) = rint(1000 * ||p - its nearest node||) in fp64, summed in 64 bits; 0xFFFFFFFF where no route exists (either node
+        blocked, absent or cut off).  A point without a node (a non-finite coordinate) holds 0xFFFFFFFF in its whole row and
+        column, the diagonal included.  Rows and columns at or above count[e] hold 0xFFFFFFFF.  Symmetric: the lattice is
+        undirected and the distances exact integers.
+        P field launches from points[:, s], each followed by one query of all P points, on a private field that shares
+        `blocked`: `field`, `source`, `status` and `launches` of this object are not touched.  A sweep cap in one of those
+        fields, or a sum that does not stay below 0xFFFFFFFE (the entry is then 0xFFFFFFFF), is kept in a device flag and raised
+        by the next check().  The result buffer is reused per P.  No host synchronisation."""
+        n = self.num_envs
+        _lib.require_cuda(points, count)
+        if points.dtype != torch.float32 or points.dim() != 3 or points.shape[0] != n or points.shape[2] < 3 or points.shape[1] < 1:
+            raise _lib.GennbvHipError(f"FlightField.pairwise_mm: points must be float32 [{n}, P, >= 3], got {points.dtype} {tuple(points.shape)}")
+        p = int(points.shape[1])
+        if count is not None and (count.dtype != torch.int32 or count.shape != (n,)):
+            raise _lib.GennbvHipError(f"FlightField.pairwise_mm: count must be int32 [{n}], got {count.dtype} {tuple(count.shape)}")
+        if self._pair is None:
+            self._pair = FlightField(self.mesh, self.lattice, self.body, mode=self.mode, blocked=self.blocked)
+            self._pair_status = torch.zeros(n, dtype=torch.int32, device=self.device)
+        scratch = self._pair
+        if p not in self._pair_rows:
+            self._pair_rows[p] = torch.empty(p, n, p, dtype=torch.int32, device=self.device)
+        rows = self._pair_rows[p]
+        pts = points if points.stride(2) == 1 else points.contiguous()
+        for s in range(p):
+            scratch.update(pts[:, s])
+            scratch.cost_mm(pts, out=rows[s])
+            self._pair_status |= scratch.status
+        lat = self.lattice
+        q = pts[..., :3].to(torch.float64)
+        d = q - lat.nearest_positions(q)
+        stub = torch.round(1000.0 * torch.sqrt(d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1] + d[..., 2] * d[..., 2]))  # NaN: no node
+        has_node = torch.isfinite(stub)
+        stub = torch.where(has_node, stub, torch.zeros_like(stub)).clamp(max=float(2 ** 40)).to(torch.int64)
+        mm = rows.permute(1, 0, 2).to(torch.int64) & 0xFFFFFFFF
+        routed = mm != INF_MM
+        total = mm + stub[:, :, None] + stub[:, None, :]
+        fits = total < INF_MM - 1
+        self._pair_status |= (routed & ~fits).flatten(1).any(dim=1).to(torch.int32) * 2
+        eye = torch.eye(p, dtype=torch.bool, device=self.device)[None]
+        total = torch.where(eye & has_node[:, :, None], torch.zeros_like(total), torch.where(routed & fits, total, torch.full_like(total, INF_MM)))
+        if count is not None:
+            inside = torch.arange(p, device=self.device)[None] < count[:, None]
+            total = torch.where(inside[:, :, None] & inside[:, None, :], total, torch.full_like(total, INF_MM))
+        out = self._pair_out.get(p)
+        if out is None:
+            out = self._pair_out[p] = torch.empty(n, p, p, dtype=torch.int32, device=self.device)
+        out.copy_(torch.where(total >= 2 ** 31, total - 2 ** 32, total))
+        return out
 
     def _targets(self, targets: torch.Tensor):
         n = self.num_envs

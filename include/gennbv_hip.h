@@ -907,6 +907,47 @@ typedef struct GnbvCoverGreedy {
 } GnbvCoverGreedy;
 int gnbv_cover_greedy(const GnbvCoverGreedy *args /*[host]*/, void *stream);
 
+/* ------------------------------------------------------------------------- */
+/* Plan-then-fly (a new entry point of ABI 5): order a set of points into a    */
+/* short open flight tour from a matrix of integer leg lengths.                */
+/* ------------------------------------------------------------------------- */
+/* Per env, D = dist_mm[e] ([p, p] u32 millimetres, 0xFFFFFFFF = no route; read as given, D[a][b] is the entry of row a, the
+ * matrix is assumed symmetric and never checked), c = count[e] (NULL: p):
+ *   route set   = {0} and every j in 1 .. c-1 with D[0][j] != 0xFFFFFFFF.  routed = R = its size.  Point 0 is the fixed start,
+ *                 the path is open (no return to the start).  Every other index of 0 .. p-1 (j >= c included) goes to
+ *                 order[R ..] in ascending order.
+ *   construction: t[0] = 0; then R - 1 times the unvisited route point j with the smallest D[t[last]][j] is appended, ties to the
+ *                 lowest j.
+ *   improvement : best-improvement 2-opt.  A round looks at every 1 <= i < j <= R-1 with, in signed 64 bits,
+ *                   delta = D[t[i-1]][t[j]] - D[t[i-1]][t[i]] + (j+1 < R ? D[t[i]][t[j+1]] - D[t[j]][t[j+1]] : 0)
+ *                 and takes the most negative delta, ties to the lowest i, then the lowest j.  No delta below 0: done.  Else, if
+ *                 max_moves moves have been made already, status bit 2 is set and the loop stops; else t[i .. j] is reversed
+ *                 (one move) and the next round starts.  On a symmetric D every move shortens an integer length, so the loop
+ *                 ends; max_moves bounds it whatever D holds.
+ *   order[0 .. R-1] = t;  length_mm = the sum of D[t[q]][t[q+1]], q = 0 .. R-2, in 64 bits.
+ *   status bit 1: some entry the rule reads between two route points was 0xFFFFFFFF -- D[t[last]][j] of every unvisited route
+ *                 point j in every construction step, the two or four entries of every pair of every 2-opt round (the round
+ *                 that finds nothing and the round that meets the cap included), or a leg of the final route.  Such an entry is
+ *                 used as the plain number 4294967295, so the result stays defined.  (On a symmetric D: exactly when two route
+ *                 points have no route between them.)
+ *   status bit 2: the max_moves cap, as above.
+ *   status bit 4: c outside 1 .. p.  The env gets order = 0 .. p-1, routed = 1, length_mm = 0, and no other bit.
+ * One workgroup per env, D and the tour in LDS.  Integers with one right answer.  No global atomics, every output element
+ * written once per call, no host synchronisation, no allocation.  Deterministic.
+ * Returns hipErrorInvalidValue for a NULL struct, n outside 1..65535, p outside 1..128, max_moves < 0, or a NULL dist_mm, order,
+ * routed, length_mm or status.  [host struct]; pointers are device. */
+typedef struct GnbvTourRoute {
+    int n, p;                 /* envs 1..65535, points per env 1..128 */
+    const uint32_t *dist_mm;  /* [n,p,p], 0xFFFFFFFF = no route; read as given, assumed symmetric */
+    const int32_t *count;     /* [n] or NULL (= p) */
+    int max_moves;            /* >= 0 */
+    int32_t *order;           /* [n,p] */
+    int32_t *routed;          /* [n] */
+    int64_t *length_mm;       /* [n] */
+    int32_t *status;          /* [n] */
+} GnbvTourRoute;
+int gnbv_tour_route(const GnbvTourRoute *args /*[host]*/, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
