@@ -1,0 +1,257 @@
+// flightmap.hip -- the free set of the flight lattice from the map the agent has scanned so far (gnbv_flight_blocked_tri).
+//
+// flight.hip routes over blocked bits; MeshScene.flight_blocked takes them from the ground-truth mesh.  This file takes them from
+// an env's own tri-class grid (< 0 free, 0 unknown, > 0 occupied: gnbv_view_gain's signs), once per env step: node c of env e is
+// blocked iff the closed ball of radius rho round the node touches an occupied voxel (or, by flag, an unknown one, the outside of
+// the grid, the ground).  The predicate is exact -- fp64, one fixed operation order, no FMA (include/gennbv_hip.h states it; the
+// library is built with -ffp-contract=off) -- so tests compare every u32 of the output with a numpy restatement.
+//
+//   k_flight_blocked_tri<kLds, kF32>   workgroup (env, chunk of nodes), 512 lanes; a wave owns 64 consecutive nodes at a time and
+//     stores their ballot as two whole words of blocked_out: one writer per word, no atomics.  Nodes at or past M (padding) count
+//     as blocked.  Per node: the per-axis voxel window [i0, i1] of the ball (clamped to the grid in fp64 before conversion, so every
+//     loop below runs at most G times whatever the device arrays hold), then x, y, z over the window with gx^2 and gx^2 + gy^2
+//     hoisted; a partial sum already above rho^2 skips the rest (adding a square >= 0 never lowers a rounded sum).  The walk ends at
+//     the first touched blocking voxel.
+//     kLds (mode 1): the workgroup first packs "this voxel blocks" into one bit per voxel in LDS (64 voxels per wave ballot,
+//       coalesced reads of either grid form; G^3 / 8 bytes, 32 KiB at 64^3) and a node reads the z-run of a (x, y) column as whole
+//       words: a word with no blocking bit inside the window costs no arithmetic.  Lanes of a wave are x-neighbours, their words lie
+//       G^2 / 32 apart -- at G = 64 all on one bank -- so word w is kept at w ^ ((w >> shift) & 31), shift ~ log2(G^2 / 32), >= 5: a
+//       permutation inside each aligned group of 32 words that spreads x-neighbours over the banks.
+//     !kLds (mode 2): the same decisions with the voxels read from global memory, for grids whose bits do not fit (up to 128^3).
+//     kF32: the grid is the fp32 slice of an observation row, else int8 rows.
+#include <algorithm>
+#include <cmath>
+
+#include "common.h"
+#include "../../include/gennbv_hip.h"
+
+namespace {
+
+constexpr int kMapLanes = 512;
+constexpr int kMapWaves = kMapLanes / kWave;
+constexpr int kMapLdsBytes = 160 * 1024;
+constexpr int kMapMaxGrid = 128;
+
+// LDS of mode 1: one bit per voxel in whole 64-voxel ballots, rounded up to a group of 32 words (the swizzle stays inside a group)
+constexpr size_t map_lds_bytes(int g)
+{
+    const size_t words = 2 * (((size_t)g * g * g + 63) / 64);
+    return 4 * ((words + 31) / 32 * 32);
+}
+
+constexpr int map_lds_max_grid()
+{
+    int g = 1;
+    while (g < kMapMaxGrid && map_lds_bytes(g + 1) <= (size_t)kMapLdsBytes) ++g;
+    return g;
+}
+
+struct MapArgs {
+    int g, nx, ny, nz, m, words;
+    int chunks, chunk_waves;  // workgroups per env; 64-node groups per workgroup
+    int shift;                // the LDS swizzle
+    int unknown_blocks, outside_blocks, ground;
+    double lo[3], h[3], rho, rho2;
+};
+
+template <bool kF32>
+__device__ __forceinline__ bool voxel_blocks(const void *__restrict__ tri, int idx, bool unknown_blocks)
+{
+    if (kF32) {
+        const float t = static_cast<const float *>(tri)[idx];
+        return t > 0.0f || (unknown_blocks && t == 0.0f);
+    }
+    const int t = static_cast<const int8_t *>(tri)[idx];
+    return t > 0 || (unknown_blocks && t == 0);
+}
+
+__device__ __forceinline__ int map_swizzle(int w, int shift) { return w ^ ((w >> shift) & 31); }
+
+// the squared gap on one axis between node coordinate p and voxel i = [o + i v, o + (i + 1) v]
+__device__ __forceinline__ double gap2(double o, double v, int i, double p)
+{
+    const double below = o + (double)i * v - p;
+    const double above = p - (o + (double)(i + 1) * v);
+    const double gap = fmax(fmax(below, 0.0), above);
+    return gap * gap;
+}
+
+template <bool kLds, bool kF32>
+__device__ __forceinline__ bool node_blocked(const MapArgs &a, int c, const double *o, const double *v, const void *__restrict__ tri,
+                                             const uint32_t *bits)
+{
+    const int g = a.g;
+    const int idx[3] = {c % a.nx, (c / a.nx) % a.ny, c / (a.nx * a.ny)};
+    const double top = (double)(g - 1);
+    double p[3];
+    int i0[3], i1[3];
+    bool outside = false, empty = false;
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax) {
+        p[ax] = a.lo[ax] + a.h[ax] * (double)idx[ax];
+        const double pm = p[ax] - a.rho, pp = p[ax] + a.rho;
+        const double f0 = floor((pm - o[ax]) / v[ax]), f1 = floor((pp - o[ax]) / v[ax]);
+        empty = empty || f1 < 0.0 || f0 > top;
+        i0[ax] = (int)fmin(fmax(f0, 0.0), top);  // (a NaN clamps to 0: the loops stay inside the grid)
+        i1[ax] = (int)fmin(fmax(f1, 0.0), top);
+        outside = outside || pm < o[ax] || pp > o[ax] + (double)g * v[ax];
+    }
+    if (a.outside_blocks && outside) return true;
+    if (a.ground && p[2] - a.rho <= 0.0) return true;
+    if (empty) return false;
+    const bool unk = a.unknown_blocks != 0;
+    for (int x = i0[0]; x <= i1[0]; ++x) {
+        const double gx2 = gap2(o[0], v[0], x, p[0]);
+        if (gx2 > a.rho2) continue;
+        for (int y = i0[1]; y <= i1[1]; ++y) {
+            const double s = gx2 + gap2(o[1], v[1], y, p[1]);
+            if (s > a.rho2) continue;
+            const int base = (x * g + y) * g;
+            if (kLds) {
+                const int b0 = base + i0[2], b1 = base + i1[2];
+                for (int w = b0 >> 5; w <= (b1 >> 5); ++w) {
+                    const int first = max(b0, w << 5), last = min(b1, (w << 5) + 31);
+                    const uint32_t span = (0xFFFFFFFFu >> (31 - (last - first))) << (first & 31);
+                    const uint32_t word = bits[map_swizzle(w, a.shift)] & span;
+                    if (word == 0u) continue;
+                    for (int b = first; b <= last; ++b) {
+                        if (((word >> (b & 31)) & 1u) == 0u) continue;
+                        if (s + gap2(o[2], v[2], b - base, p[2]) <= a.rho2) return true;
+                    }
+                }
+            } else {
+                for (int z = i0[2]; z <= i1[2]; ++z) {
+                    if (!voxel_blocks<kF32>(tri, base + z, unk)) continue;
+                    if (s + gap2(o[2], v[2], z, p[2]) <= a.rho2) return true;
+                }
+            }
+        }
+    }
+    return false;
+}
+
+template <bool kLds, bool kF32>
+__global__ __launch_bounds__(kMapLanes) void k_flight_blocked_tri(const void *__restrict__ tri_base, int64_t row_bytes,
+                                                                  const float *__restrict__ range_gt, const float *__restrict__ voxel_size,
+                                                                  MapArgs a, uint32_t *__restrict__ blocked_out)
+{
+    extern __shared__ __attribute__((aligned(16))) char map_lds[];
+    uint32_t *bits = reinterpret_cast<uint32_t *>(map_lds);
+    const int e = blockIdx.x / a.chunks, chunk = blockIdx.x - e * a.chunks;
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    const void *tri = static_cast<const char *>(tri_base) + (size_t)e * row_bytes;
+
+    if (kLds) {
+        const int g3 = a.g * a.g * a.g, groups = (g3 + kWave - 1) / kWave;
+        const bool unk = a.unknown_blocks != 0;
+        for (int q = wave; q < groups; q += kMapWaves) {  // (q is the same in every lane of a wave: the ballot is whole)
+            const int vox = q * kWave + lane;
+            const bool b = vox < g3 && voxel_blocks<kF32>(tri, vox, unk);
+            const unsigned long long mask = __ballot(b);
+            if (lane == 0) {
+                bits[map_swizzle(2 * q, a.shift)] = (uint32_t)mask;
+                bits[map_swizzle(2 * q + 1, a.shift)] = (uint32_t)(mask >> 32);
+            }
+        }
+        __syncthreads();
+    }
+
+    // the voxel frame of gnbv_pose_to_idx: the subtraction in fp32
+    double o[3], v[3];
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax) {
+        const float vf = voxel_size[e * 3 + ax];
+        o[ax] = (double)__fsub_rn(range_gt[e * 6 + 2 * ax + 1], __fmul_rn(0.5f, vf));
+        v[ax] = (double)vf;
+    }
+
+    uint32_t *out = blocked_out + (size_t)e * a.words;
+    for (int t = wave; t < a.chunk_waves; t += kMapWaves) {
+        const int c0 = (chunk * a.chunk_waves + t) * kWave, c = c0 + lane;
+        bool blocked = true;  // padding
+        if (c < a.m) blocked = node_blocked<kLds, kF32>(a, c, o, v, tri, bits);
+        const unsigned long long mask = __ballot(blocked);
+        const int w = c0 >> 5;
+        if (lane == 0 && w < a.words) out[w] = (uint32_t)mask;
+        if (lane == 0 && w + 1 < a.words) out[w + 1] = (uint32_t)(mask >> 32);
+    }
+}
+
+template <bool kLds, bool kF32>
+int launch_map(const void *tri, int64_t row_bytes, const float *range_gt, const float *voxel_size, const MapArgs &a, int n, size_t lds,
+               uint32_t *blocked_out, hipStream_t stream)
+{
+    if (kLds && lds > 64 * 1024) {  // what a launch may ask for without the attribute
+        static bool raised = false;
+        if (!raised) {
+            const hipError_t err = hipFuncSetAttribute((const void *)k_flight_blocked_tri<kLds, kF32>,
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, kMapLdsBytes);
+            if (err != hipSuccess) return (int)err;
+            raised = true;
+        }
+    }
+    hipLaunchKernelGGL((k_flight_blocked_tri<kLds, kF32>), dim3((unsigned)(n * a.chunks)), dim3(kMapLanes), lds, stream, tri, row_bytes,
+                       range_gt, voxel_size, a, blocked_out);
+    return gnbv_launch_status();
+}
+
+}  // namespace
+
+GNBV_API int gnbv_flightmap_lds_max_grid(void) { return map_lds_max_grid(); }
+
+GNBV_API int gnbv_flight_blocked_tri(const int8_t *tri_i8, int64_t tri_i8_row_stride, const float *tri_f32, int64_t tri_f32_row_stride,
+                                     int g, const float *range_gt, const float *voxel_size, int n, int nx, int ny, int nz, const double *lo,
+                                     const double *h, double rho, int unknown_blocks, int outside_blocks, int ground,
+                                     uint32_t *blocked_out, int mode, void *stream)
+{
+    GNBV_CHECK_ARG((tri_i8 != nullptr) != (tri_f32 != nullptr));
+    GNBV_CHECK_ARG(range_gt != nullptr && voxel_size != nullptr && blocked_out != nullptr && lo != nullptr && h != nullptr);
+    GNBV_CHECK_ARG(n >= 1 && g >= 1 && g <= kMapMaxGrid && mode >= 0 && mode <= 2);
+    GNBV_CHECK_ARG(std::isfinite(rho) && rho > 0.0);
+    const int64_t g3 = (int64_t)g * g * g;
+    const bool f32 = tri_f32 != nullptr;
+    GNBV_CHECK_ARG((f32 ? tri_f32_row_stride : tri_i8_row_stride) >= g3);
+    MapArgs a;
+    const int dims[3] = {nx, ny, nz};
+    for (int ax = 0; ax < 3; ++ax) {
+        GNBV_CHECK_ARG(dims[ax] >= 1 && dims[ax] <= 1024 && std::isfinite(lo[ax]) && std::isfinite(h[ax]));
+        GNBV_CHECK_ARG(dims[ax] == 1 || h[ax] > 0.0);
+        a.lo[ax] = lo[ax];
+        a.h[ax] = h[ax];
+    }
+    const int64_t m = (int64_t)nx * ny * nz;
+    const bool fits = g <= map_lds_max_grid();
+    GNBV_CHECK_ARG(mode != 1 || fits);
+    const bool lds = mode == 1 || (mode == 0 && fits);
+    a.g = g;
+    a.nx = nx;
+    a.ny = ny;
+    a.nz = nz;
+    a.m = (int)m;
+    a.words = (int)((m + 31) / 32);
+    // 64-node groups per workgroup: one per wave where the grid is read in place; with the bits in LDS every workgroup pays for
+    // packing the whole grid, so an env gets only as many workgroups as it takes to reach about two per CU over all envs
+    const int64_t groups = (m + kWave - 1) / kWave;
+    int64_t chunks = (groups + kMapWaves - 1) / kMapWaves;
+    if (lds) chunks = std::min<int64_t>(chunks, std::max<int64_t>(1, (512 + n - 1) / n));
+    a.chunk_waves = (int)((groups + chunks - 1) / chunks);
+    a.chunks = (int)((groups + a.chunk_waves - 1) / a.chunk_waves);
+    GNBV_CHECK_ARG((int64_t)n * a.chunks <= 0x7fffffff);
+    a.shift = 5;
+    while (a.shift < 20 && (2 << a.shift) * 3 <= (g * g / 32) * 4) ++a.shift;  // ~ round(log2(G^2 / 32))
+    a.unknown_blocks = unknown_blocks != 0;
+    a.outside_blocks = outside_blocks != 0;
+    a.ground = ground != 0;
+    a.rho = rho;
+    a.rho2 = rho * rho;
+    const void *tri = f32 ? static_cast<const void *>(tri_f32) : static_cast<const void *>(tri_i8);
+    const int64_t row_bytes = f32 ? 4 * tri_f32_row_stride : tri_i8_row_stride;
+    const hipStream_t s = gnbv_stream(stream);
+    if (lds) {
+        const size_t bytes = map_lds_bytes(g);
+        return f32 ? launch_map<true, true>(tri, row_bytes, range_gt, voxel_size, a, n, bytes, blocked_out, s)
+                   : launch_map<true, false>(tri, row_bytes, range_gt, voxel_size, a, n, bytes, blocked_out, s);
+    }
+    return f32 ? launch_map<false, true>(tri, row_bytes, range_gt, voxel_size, a, n, 0, blocked_out, s)
+               : launch_map<false, false>(tri, row_bytes, range_gt, voxel_size, a, n, 0, blocked_out, s);
+}

@@ -35,6 +35,15 @@ the metres flown in the episode: the straight distance where the straight flight
 (nothing for a flight with no route: it ends the episode), reset to 0 by the step that sets an episode's first pose -- so
 after the step that ends an episode it still holds that episode's length.  The field is computed once per step from the
 poses the env has just arrived at and kept in `env.flight`: the next step's check and the planners' queries both read it.
+
+`flight=BeliefFlightField(...)` (a field whose `belief` is true) is the pilot that knows only its own map: the drone flies the
+route that the field -- computed last step from the map scanned so far -- holds to the step's pose, and the true mesh judges
+what was flown.  One path launch (buffer length max(2 (nx + ny + nz), 8); a route that does not fit counts as none and is
+counted in `route_overflow`); where a route exists its legs previous pose -> nodes -> new pose, otherwise the straight flight,
+go through ONE sweep_candidates call and their codes are ORed into `path_code` and, in full, into `collision_buf`: nothing is
+dropped.  `flight_length` adds the route's length where there is one and the straight distance otherwise.  After the voxel
+update the field is refreshed from the tri-class grid the step has just written (grid_i8_out where given, else the observation's
+grid slice) and updated from the poses arrived at.
 """
 from __future__ import annotations
 
@@ -148,6 +157,19 @@ class ReplayFeedEnv:
         self.flight = flight
         self.flight_length = torch.zeros(n, dtype=torch.float32, device=self.device) if flight is not None else None
         self.path_code = torch.zeros(n, dtype=torch.uint8, device=self.device) if flight is not None else None
+        self._belief = flight is not None and bool(getattr(flight, "belief", False))
+        self.route_overflow = self.routed = None
+        if self._belief:
+            if int(flight.grid_size) != int(cfg.grid_size):
+                raise ValueError(f"flight is built for a {flight.grid_size}^3 grid, the env's is {cfg.grid_size}^3")
+            nx, ny, nz = flight.lattice.dims
+            self._route_len = length = max(2 * (nx + ny + nz), 8)
+            self._route_nodes = torch.full((n, length), -1, dtype=torch.int32, device=self.device)
+            self._route_count = torch.zeros(n, dtype=torch.int32, device=self.device)
+            self._route_codes = torch.zeros(n, length + 1, dtype=torch.uint8, device=self.device)
+            self._node_pos = torch.as_tensor(flight.lattice.node_positions(), device=self.device).to(torch.float32)
+            self.route_overflow = torch.zeros((), dtype=torch.int64, device=self.device)  # routes longer than the buffer, so far
+            self.routed = torch.zeros(n, dtype=torch.bool, device=self.device)  # the last step flew a route of the field
         self.grid_size = cfg.grid_size
         self.max_episode_length = int(cfg.max_episode_length if max_episode_length is None else max_episode_length)
         self.max_episode_length_s = cfg.episode_length_s
@@ -297,6 +319,10 @@ class ReplayFeedEnv:
             self.updater.update(depth_raw, seg_raw, c2w, self.poses, reset_mask=self.reset_mask,
                                 tri_out=obs[:, cfg.state_dim:], tri_row_stride=stride,
                                 tri_i8_out=grid_i8_out if self.updater.coded else None)
+        if self._belief:  # what the pilot knows next step: the map just written, from the poses just arrived at
+            wrote_i8 = grid_i8_out is not None and (compact or self.updater.coded)
+            self.flight.refresh(grid_i8_out if wrote_i8 else obs[:, cfg.state_dim:cfg.state_dim + cfg.grid_dim])
+            self.flight.update(self.poses)
         # rewards / termination / reset bookkeeping
         self._ep_step += 1
         self._post.episode_info = self.episode_info_hist[self._ep_step % self._ep_hist].data_ptr()
@@ -310,7 +336,9 @@ class ReplayFeedEnv:
         """collision_buf = the body at the step's poses, and with `collision.sweep` | the flight from the previous poses to
         them (episode_length_buf <= 1 after the step's head: the first pose of an episode, not flown to)."""
         self.collision_mesh.collide(self.poses, self.collision, out=self.collision_buf)
-        if self.flight is not None:
+        if self._belief:
+            self._fly_belief_step()
+        elif self.flight is not None:
             self._fly_step()
         elif self._sweep:
             self.collision_mesh.sweep_candidates(self._prev_poses, self.poses.unsqueeze(1), self.collision, self.episode_length_buf,
@@ -331,6 +359,38 @@ class ReplayFeedEnv:
         first = self.episode_length_buf <= 1  # after the step's head: the pose was set, not flown to
         self.flight_length.copy_(torch.where(first, torch.zeros_like(flown), self.flight_length + flown))
         fl.update(poses)
+
+    def _fly_belief_step(self):
+        """The sweep of _collide_step for a pilot that plans on its own map (module docstring): `flight` still holds the field
+        from the previous poses over the previous map.  Waypoints: previous pose, the route's nodes, new pose; an env without a
+        route has the one leg previous pose -> new pose, the straight flight.  The truth judges every leg."""
+        fl, poses, prev = self.flight, self.poses, self._prev_poses
+        n, length = self.num_envs, self._route_len
+        nodes, count = self._route_nodes, self._route_count
+        fl.path_into(poses, nodes, count)
+        self.route_overflow += (count < 0).sum()
+        routed = count > 0
+        cnt = count.clamp(min=0).long()
+        j = torch.arange(length, device=self.device)[None]
+        back = (cnt[:, None] - 1 - j).clamp(min=0)  # nodes run target -> source: waypoint 1 + j is node count - 1 - j
+        ids = nodes.long().gather(1, back).clamp(min=0)
+        new = poses[:, None, :3]
+        way = torch.empty(n, length + 2, 3, dtype=torch.float32, device=self.device)
+        way[:, 0] = prev[:, :3]
+        way[:, 1:length + 1] = torch.where((j < cnt[:, None])[..., None], self._node_pos[ids], new)  # past the route: the new pose
+        way[:, length + 1] = poses[:, :3]
+        codes = self.collision_mesh.sweep_candidates(way[:, :-1].contiguous(), way[:, 1:].contiguous(), self.collision,
+                                                     self.episode_length_buf, out=self._route_codes)
+        legs = torch.arange(length + 1, device=self.device)[None] <= cnt[:, None]  # count + 1 legs; 1 without a route
+        codes = torch.where(legs, codes, torch.zeros_like(codes))
+        code = ((codes & 8) != 0).any(dim=1).to(torch.uint8) * 8 | ((codes & 16) != 0).any(dim=1).to(torch.uint8) * 16
+        self.path_code.copy_(code)
+        self.collision_buf |= code
+        straight = (poses[:, :3] - prev[:, :3]).norm(dim=-1)
+        flown = torch.where(routed, fl.cost(poses.unsqueeze(1))[:, 0], straight)
+        first = self.episode_length_buf <= 1  # after the step's head: the pose was set, not flown to
+        self.flight_length.copy_(torch.where(first, torch.zeros_like(flown), self.flight_length + flown))
+        self.routed.copy_(routed & ~first)
 
     def _rgba_or_zero(self, rgba):
         if rgba is None:

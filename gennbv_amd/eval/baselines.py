@@ -143,7 +143,7 @@ class GreedyGainPolicy:
             if hasattr(mesh, "collide_candidates"):  # all N x K poses in one launch
                 if self._contact is None:
                     self._contact = torch.zeros(n, k, dtype=torch.uint8, device=obs.device)
-                contact = candidate_contact(self.env, poses, self._contact, self.sweep)  # | the flight from the current pose
+                contact = self.contact(poses)  # | the flight from the current pose
             else:
                 if self._contact is None:
                     self._contact = torch.zeros(k, n, dtype=torch.uint8, device=obs.device)
@@ -153,12 +153,46 @@ class GreedyGainPolicy:
         best = choose(gain, self.weights, contact)
         return cand[torch.arange(n, device=cand.device), best], None, None
 
+    def contact(self, poses: torch.Tensor) -> torch.Tensor:
+        """u8 [N,K] into `self._contact`: non-zero where candidate poses [N,K,6] is refused (the hook MapGreedyPolicy replaces)."""
+        return candidate_contact(self.env, poses, self._contact, self.sweep)
+
     @property
     def policy(self):
         return self
 
     def predict(self, obs, state=None, episode_start=None, deterministic: bool = True):
         return self(obs, deterministic)[0], state
+
+
+class MapGreedyPolicy(GreedyGainPolicy):
+    """GreedyGainPolicy for a pilot that knows only its own map: a candidate is refused iff the env's BeliefFlightField
+    (ops/flight_field.py) holds no route to it -- contact = ~env.flight.reachable(poses) and nothing else.  The collision mesh is
+    never consulted: not for the candidate's pose, not for the flight to it.  What the drone then really meets is the env's
+    business (ReplayFeedEnv flies the field's route and lets the true mesh judge it)."""
+
+    def __init__(self, env, k: int = 32, weights=(1, 4), seed: int = 0, stride: int = 4, look_at_scene: bool = False,
+                 gain_backend: Optional[Callable] = None):
+        if not getattr(getattr(env, "flight", None), "belief", False):
+            from .. import _lib
+            raise _lib.GennbvHipError("MapGreedyPolicy needs an env whose flight is a BeliefFlightField")
+        super().__init__(env, k=k, weights=weights, seed=seed, stride=stride, avoid_collisions=False, look_at_scene=look_at_scene,
+                         gain_backend=gain_backend)
+        self.avoid_collisions = True  # by the map: `contact` below; `sweep` stays off, no mesh predicate is launched
+
+    def __call__(self, obs, deterministic: bool = True):
+        cfg, n = self.cfg, self.num_envs
+        cand = self.cands.sample(n, obs.device)
+        poses = self.cands.poses(cand)
+        gain = self.gain_backend(obs[:, cfg.state_dim:cfg.state_dim + cfg.grid_dim], poses)
+        self.last_gain = gain
+        if self._contact is None:
+            self._contact = torch.zeros(n, self.k, dtype=torch.uint8, device=obs.device)
+        best = choose(gain, self.weights, self.contact(poses))
+        return cand[torch.arange(n, device=cand.device), best], None, None
+
+    def contact(self, poses: torch.Tensor) -> torch.Tensor:
+        return self._contact.copy_(~self.env.flight.reachable(poses))
 
 
 class OracleGainPolicy:

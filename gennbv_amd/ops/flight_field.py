@@ -12,6 +12,9 @@ in metres plus the two stub legs pose <-> node.  Every leg is flyable by the sph
 has the argument).  `mode`: 0 auto, 1 the field resident in LDS (refused where it does not fit), 2 the field in global memory.
 The sweep count of the field kernel has a hard cap; an env that hit it is reported lazily, by `check()` (one read-back) and
 by `path()`, the way ScanAccumulator reports its flags.  GPU only.
+
+BeliefFlightField is the same field over the agent's own map: its blocked bits are recomputed every step from the tri-class
+grid (csrc/flightmap.hip) and no mesh is consulted.
 """
 from __future__ import annotations
 
@@ -226,9 +229,95 @@ class FlightField:
             length = need
 
 
+class BeliefFlightField(FlightField):
+    """The flight field over the map the agent has scanned so far: the blocked bits come from each env's tri-class grid
+    (gnbv_flight_blocked_tri, csrc/flightmap.hip), not from a mesh -- the pilot that knows only what it has seen.
+
+        field = BeliefFlightField(num_envs, lattice, body, range_gt, voxel_size, grid_size)
+        field.refresh(tri)     # one launch: the grid (int8 rows, or the fp32 grid slice of observation rows) -> blocked_map
+        field.update(poses)    # blocked = blocked_map with each env's own node cleared, then the field launch
+
+    A node is blocked where the ball of radius rho = lattice.inflated_radius(body) + margin touches an occupied voxel
+    (`unknown="blocked"`: or an unknown one, the conservative pilot; the default "free" is the optimistic one), with
+    `outside="blocked"` where it leaves the grid (range_gt bounds every solid of a scene by grid_spec's construction, hence the
+    default "free"), and with body.ground where it reaches z <= 0.  The drone is at its own nearest node, so update() calls
+    that node flyable whatever the map says; `blocked_map` stays the pure kernel output.  `map_mode`: 0 auto, 1 the grid's
+    bits packed into LDS (refused where they do not fit), 2 the grid read from global memory.  GPU only."""
+    belief = True
+
+    def __init__(self, num_envs: int, lattice, body, range_gt: torch.Tensor, voxel_size: torch.Tensor, grid_size: int,
+                 unknown: str = "free", outside: str = "free", margin: float = 0.0, mode: int = 0, map_mode: int = 0, device="cuda:0"):
+        import types
+        device = torch.device(device)
+        for name, val in (("unknown", unknown), ("outside", outside)):
+            if val not in ("free", "blocked"):
+                raise ValueError(f"BeliefFlightField: {name} must be 'free' or 'blocked', got {val!r}")
+        if int(map_mode) not in (0, 1, 2):
+            raise ValueError(f"BeliefFlightField: map_mode must be 0, 1 or 2, got {map_mode}")
+        n, g = int(num_envs), int(grid_size)
+        if not 1 <= g <= 128:
+            raise ValueError(f"BeliefFlightField: grid_size must be in 1..128, got {grid_size}")
+        if device.type != "cuda":
+            raise _lib.GennbvHipError("BeliefFlightField runs on the GPU only (no CPU fallback)")
+        lib = _lib.load()
+        if int(map_mode) == 1 and g > int(lib.gnbv_flightmap_lds_max_grid()):
+            raise _lib.GennbvHipError(f"BeliefFlightField: the bits of a {g}^3 grid do not fit LDS (map_mode 1)")
+        self.rho = float(lattice.inflated_radius(body)) + float(margin)
+        if not (np.isfinite(self.rho) and self.rho > 0.0):
+            raise ValueError(f"BeliefFlightField: the inflated radius plus margin must be finite and > 0, got {self.rho}")
+        self.grid_size, self.map_mode = g, int(map_mode)
+        self.unknown_blocks, self.outside_blocks = unknown == "blocked", outside == "blocked"
+        self.range_gt = range_gt.to(device, torch.float32).contiguous()
+        self.voxel_size = voxel_size.to(device, torch.float32).contiguous()
+        assert self.range_gt.shape == (n, 6) and self.voxel_size.shape == (n, 3)
+        blocked = torch.full((n, lattice.words), -1, dtype=torch.int32, device=device)  # all blocked until the first refresh
+        super().__init__(types.SimpleNamespace(device=device, num_envs=n), lattice, body, mode=mode, blocked=blocked)
+        self.blocked_map = torch.full_like(self.blocked, -1)
+        self.refreshes = 0  # map launches so far
+
+    def refresh(self, tri: torch.Tensor) -> "BeliefFlightField":
+        """gnbv_flight_blocked_tri on the current stream into `blocked_map`: tri [N, >= G^3] int8 or float32, unit element
+        stride, any row stride (e.g. obs[:, state_dim:state_dim + grid_dim])."""
+        n, g3 = self.num_envs, self.grid_size ** 3
+        _lib.require_cuda(tri)
+        if tri.dtype not in (torch.int8, torch.float32) or tri.dim() != 2 or tri.shape[0] != n or tri.shape[1] < g3 or tri.stride(1) != 1:
+            raise _lib.GennbvHipError(f"BeliefFlightField.refresh: tri must be int8 or float32 [{n}, >= {g3}] with unit element stride, "
+                                      f"got {tri.dtype} {tuple(tri.shape)} strides {tuple(tri.stride())}")
+        row = int(tri.stride(0)) if n > 1 else max(int(tri.stride(0)), g3)
+        i8 = tri.dtype == torch.int8
+        nx, ny, nz = self.lattice.dims
+        _lib.check(self.lib.gnbv_flight_blocked_tri(tri.data_ptr() if i8 else None, row if i8 else 0, None if i8 else tri.data_ptr(),
+                                                    0 if i8 else row, self.grid_size, self.range_gt.data_ptr(), self.voxel_size.data_ptr(),
+                                                    n, nx, ny, nz, self._lo, self._h, self.rho, int(self.unknown_blocks),
+                                                    int(self.outside_blocks), int(bool(self.body.ground)), self.blocked_map.data_ptr(),
+                                                    self.map_mode, _lib.stream_ptr(self.device)), "gnbv_flight_blocked_tri")
+        self.refreshes += 1
+        return self
+
+    def update(self, poses: torch.Tensor) -> "BeliefFlightField":
+        """blocked = blocked_map with the bit of each env's own nearest node cleared (the drone is there; an env with a
+        non-finite pose is left alone), then FlightField.update."""
+        _lib.require_cuda(poses)
+        lat = self.lattice
+        near = lat.nearest_positions(poses[:, :3])  # NaN rows where there is no node
+        has = torch.isfinite(near).all(-1)
+        lo = torch.as_tensor(lat.lo, device=self.device)
+        h = torch.as_tensor(lat.h, device=self.device)
+        idx = torch.round((torch.where(has[:, None], near, lo.expand_as(near)) - lo) / torch.where(h > 0, h, torch.ones_like(h))).to(torch.int64)
+        nx, ny, _ = lat.dims
+        node = (idx[:, 2] * ny + idx[:, 1]) * nx + idx[:, 0]
+        bit = torch.ones_like(node) << (node & 31)
+        bit = torch.where(bit >= 2 ** 31, bit - 2 ** 32, bit).to(torch.int32)  # bit 31 as an int32
+        clear = torch.where(has, ~bit, torch.full_like(bit, -1))
+        self.blocked.copy_(self.blocked_map)
+        rows = torch.arange(self.num_envs, device=self.device)
+        self.blocked[rows, node >> 5] &= clear
+        return super().update(poses)
+
+
 def field_u32(t: torch.Tensor) -> np.ndarray:
     """An int32 tensor of u32 bits (field, cost_mm) as a numpy uint32 array on the host."""
     return np.ascontiguousarray(t.detach().cpu().numpy()).view(np.uint32)
 
 
-__all__ = ["FlightField", "INF_MM", "field_u32"]
+__all__ = ["FlightField", "BeliefFlightField", "INF_MM", "field_u32"]

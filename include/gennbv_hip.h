@@ -316,6 +316,34 @@ int gnbv_flight_path(const uint32_t *field /*[N,M]*/, int n, int nx, int ny, int
                      int64_t targets_row_stride /*floats*/, int32_t *nodes_out /*[N,max_len]*/, int max_len, int32_t *len_out /*[N]*/,
                      void *stream);
 
+/* The free set of the flight lattice from the scanned map (an additive entry point of ABI 5; csrc/flightmap.hip): the blocked bits
+ * gnbv_flight_field reads, from each env's tri-class grid instead of the ground-truth mesh.  tri [G,G,G] per env in C order x, y, z
+ * with gnbv_view_gain's signs: < 0 free, 0 unknown, > 0 occupied.  Exactly one of the two forms: tri_i8 (int8 rows, row stride in
+ * bytes) or tri_f32 (fp32 rows, row stride in floats: the grid slice of a flat observation row); the other NULL.  range_gt [N,6],
+ * voxel_size [N,3] device arrays; the lattice as above (lo, h [host] 3 doubles); rho [host] the radius of the ball round a node.
+ * The predicate, in fp64, in this operation order, without FMA:
+ *   voxel frame (gnbv_pose_to_idx): v_a = (double)voxel_size[a], o_a = (double)fp32(range_gt[2a+1] - fp32(0.5f * voxel_size[a]));
+ *     voxel i of axis a spans [o_a + i v_a, o_a + (i + 1) v_a]; node c sits at p_a = lo_a + h_a * idx_a.
+ *   window per axis: i0_a = floor(((p_a - rho) - o_a) / v_a), i1_a = floor(((p_a + rho) - o_a) / v_a), both clamped in fp64 to
+ *     [0, G - 1] before conversion; the window is empty if i1_a < 0 or i0_a > G - 1 (before clamping) on any axis.
+ *   a voxel of the window is touched iff (gx^2 + gy^2) + gz^2 <= rho * rho,
+ *     g_a = max(max((o_a + i v_a) - p_a, 0), p_a - (o_a + (i + 1) v_a)).
+ *   the node touches the outside iff on any axis p_a - rho < o_a or p_a + rho > o_a + (double)G * v_a.
+ * Bit c of env e is set iff a touched voxel is occupied, or unknown_blocks and a touched voxel is unknown, or outside_blocks and
+ * the node touches the outside, or ground and p_z - rho <= 0.  blocked_out [N, ceil(M / 32)], every word written, padding bits set.
+ * mode: 0 auto (1 where G <= gnbv_flightmap_lds_max_grid(), else 2), 1 one bit per voxel packed into LDS first
+ * (hipErrorInvalidValue where G^3 / 8 bytes do not fit), 2 the grid read from global memory; the result is the same.  One launch,
+ * one writer per output word, no atomics, no allocation, no host synchronisation; every loop is bounded by G whatever the device
+ * arrays hold.  hipErrorInvalidValue before any launch for: both or neither grid form, a NULL required pointer, n < 1, G outside
+ * 1..128, a row stride below G^3, rho not finite or <= 0, a lattice axis outside 1..1024 or lo / h not finite (h > 0 where the
+ * axis has more than one node), a mode outside 0..2. */
+int gnbv_flightmap_lds_max_grid(void); /* the largest G of mode 1: 109 */
+int gnbv_flight_blocked_tri(const int8_t *tri_i8 /*[N, >= G^3] or NULL*/, int64_t tri_i8_row_stride /*bytes*/,
+                            const float *tri_f32 /*[N, >= G^3] or NULL*/, int64_t tri_f32_row_stride /*floats*/, int g,
+                            const float *range_gt /*[N,6]*/, const float *voxel_size /*[N,3]*/, int n, int nx, int ny, int nz,
+                            const double *lo /*[host] 3*/, const double *h /*[host] 3*/, double rho, int unknown_blocks,
+                            int outside_blocks, int ground, uint32_t *blocked_out /*[N,ceil(M/32)]*/, int mode, void *stream);
+
 /* compute_reward (env_train_base.py:377-398), _reward_* / check_termination /
  * reset_idx (env_train_gennbv.py:377-457,535-556), update_extra_episode_info
  * (env_train_base.py:629-639). All pointers device, arrays [N] unless noted. [host struct] */

@@ -1,0 +1,119 @@
+"""Closed-loop table of DESIGN.md "Flying on the scanned map": the greedy planner with the privileged flight field beside the
+pilot that knows only its own map.
+
+    python tools/closed_loop_belief.py [--envs 16] [--grid 20] [--steps 20] [--k 32] [--seeds 1] [--stride 2] [--out FILE.json]
+
+The set-up of tools/closed_loop_flight.py (box scenes, 60 x 80 camera, CollisionBody(sweep=True), episodes of at most `steps`
+steps, each env's first episode).  Rows:
+
+  greedy / privileged        GreedyGainPolicy, flight=FlightField(mesh): contacts and routes from the ground-truth mesh
+  map-greedy / optimistic    MapGreedyPolicy, flight=BeliefFlightField(unknown="free"): routes through what it has not seen
+  map-greedy / conservative  MapGreedyPolicy, flight=BeliefFlightField(unknown="blocked"): routes through seen free space only
+
+Columns: final coverage, episode length, metres flown (env.flight_length at the step that ends the episode), the share of
+flown steps that followed a route of the field (the others flew straight), the share of episodes ended by a path collision
+and by a pose collision, and for the belief rows the share of decisions in which every candidate was unreachable.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+
+from gennbv_amd.env import synthetic as S  # noqa: E402
+from gennbv_amd.env.collision import PATH, PATH_GROUND, CollisionBody  # noqa: E402
+from gennbv_amd.env.config import TaskConfig  # noqa: E402
+from gennbv_amd.env.flight import FlightLattice  # noqa: E402
+from gennbv_amd.env.mesh_scene import MeshScene  # noqa: E402
+from gennbv_amd.env.render_feed import RenderFeed  # noqa: E402
+from gennbv_amd.env.replay_feed import ReplayFeedEnv  # noqa: E402
+from gennbv_amd.eval.baselines import GreedyGainPolicy, MapGreedyPolicy  # noqa: E402
+from gennbv_amd.ops.flight_field import BeliefFlightField, FlightField  # noqa: E402
+
+DEV = "cuda:0"
+
+
+def run(policy, env, steps):
+    n = env.num_envs
+    belief = bool(getattr(env.flight, "belief", False))
+    obs = env.reset()
+    alive = torch.ones(n, dtype=torch.bool, device=DEV)
+    final, length, flown, routed, moved, stuck, decisions = (torch.zeros(n, device=DEV) for _ in range(7))
+    code = torch.zeros(n, dtype=torch.uint8, device=DEV)
+    for t in range(steps):
+        act = policy(obs)[0]
+        if belief:
+            stuck += (alive & (policy._contact != 0).all(dim=1)).float()
+        decisions += alive.float()
+        obs, _, done, _ = env.step(act)
+        moved += alive.float()  # reset() set the first pose: every step of an env's first episode is flown
+        if belief:
+            routed += (alive & env.routed).float()
+        else:  # the privileged env flies straight where it can and the field's detour where it must
+            routed += (alive & (env.path_code != 0) & ((env.collision_buf & (PATH | PATH_GROUND)) == 0)).float()
+        flown = torch.where(alive, env.flight_length, flown)
+        ends = alive & done
+        final = torch.where(ends, env.coverage_ratio, final)
+        length = torch.where(ends, torch.full_like(length, t + 1), length)
+        code = torch.where(ends, env.collision_buf, code)
+        alive &= ~done
+        if not bool(alive.any()):
+            break
+    assert not bool(alive.any()), "max_episode_length must end every episode"
+    env.flight.check()
+    pose_hit = (code & 7) != 0
+    path_hit = (code & (PATH | PATH_GROUND)) != 0
+    out = {"final_coverage": float(final.mean()), "mean_length": float(length.mean()), "mean_flown_m": float(flown.mean()),
+           "routed_share": float(routed.sum() / moved.sum().clamp(min=1.0)), "ended_by_path_collision": float(path_hit.float().mean()),
+           "ended_by_pose_collision": float(pose_hit.float().mean())}
+    if belief:
+        out["all_candidates_unreachable_share"] = float(stuck.sum() / decisions.sum().clamp(min=1.0))
+        out["route_overflows"] = int(env.route_overflow)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=16)
+    ap.add_argument("--grid", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--k", type=int, default=32)
+    ap.add_argument("--seeds", default="1")
+    ap.add_argument("--stride", type=int, default=2)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("closed_loop_belief needs a GPU")
+    n, g = args.envs, args.grid
+    cfg = TaskConfig(camera_width=80, camera_height=60, grid_size=g)
+    scene = S.make_scenes(n, g, seed=1)
+    mesh = MeshScene.from_boxes(scene, device=DEV)
+    body = CollisionBody(sweep=True)
+    lattice = FlightLattice(cfg, stride=args.stride)
+    blocked = mesh.flight_blocked(lattice, body)  # once per scene set
+    res = {"envs": n, "grid": g, "steps": args.steps, "k": args.k, "stride": args.stride, "rows": []}
+    for seed in (int(s) for s in args.seeds.split(",")):
+        for name in ("greedy / privileged", "map-greedy / optimistic", "map-greedy / conservative"):
+            if name.startswith("greedy"):
+                flight = FlightField(mesh, lattice, body, blocked=blocked)
+            else:
+                flight = BeliefFlightField(n, lattice, body, scene.range_gt, scene.voxel_size, g,
+                                           unknown="free" if name.endswith("optimistic") else "blocked", device=DEV)
+            env = ReplayFeedEnv(cfg, scene, RenderFeed(mesh, cfg), DEV, max_episode_length=args.steps, collision=body, flight=flight)
+            pol = (GreedyGainPolicy if name.startswith("greedy") else MapGreedyPolicy)(env, k=args.k, weights=(1, 4), seed=seed)
+            row = {"seed": seed, "row": name}
+            row.update(run(pol, env, args.steps))
+            print(json.dumps(row), flush=True)
+            res["rows"].append(row)
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
