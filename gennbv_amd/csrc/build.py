@@ -18,7 +18,8 @@ OUT = os.path.join(PKG, "libgennbv_hip.so")
 SOURCES = ["voxel.hip", "gae.hip", "envstep.hip", "encoder.hip", "linear.hip", "head.hip", "chamfer.hip", "ppo.hip", "render.hip",
            "voxelize.hip", "collide.hip", "sweep.hip", "flight.hip", "flightmap.hip", "scan.hip", "viewgain.hip", "viewcover.hip", "covergreedy.hip",
            "tour.hip"]
-HEADERS = ["common.h", "conv_split.h", "conv_splitx.h", "backproject.h", "raytrace.h", os.path.join("..", "..", "include", "gennbv_hip.h")]
+HEADERS = ["common.h", "conv_split.h", "conv_splitx.h", "backproject.h", "raytrace.h", "scene_cells.h", "voxel_frame.h",
+           os.path.join("..", "..", "include", "gennbv_hip.h")]
 ARCH = "gfx950"
 
 

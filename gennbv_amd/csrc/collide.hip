@@ -12,9 +12,8 @@
 //
 //   k_collide_cylinder   one wave per env, kWavesPerBlock envs per workgroup:
 //     1. (S) candidates: the body's AABB (half-extents e_k = r sqrt(1 - a_k^2) + h |a_k|, grown) -> the range of cells it
-//        overlaps, clamped to the env's grid (the cell lists are a conservative superset).  Up to 64 cells at a time: lane j
-//        reads cell j's list bounds, one wave scan makes the lists one flat range the lanes stride over.  A triangle listed
-//        in several cells is tested more than once: the results are ORed;
+//        overlaps, clamped to the env's grid, and the wave's walk over those cells' triangle lists (scene_cells.h cell_range,
+//        wave_any_listed_tri);
 //     2. (S) exact test, fp64, per triangle: P = triangle n slab |(x - c).a| <= h meets the infinite cylinder iff the axis
 //        line pierces P or P's boundary comes within r of the axis.  That boundary is the three edges clipped to the slab
 //        and the triangle's chords on the two cap planes; the piercing test is the axis segment against the triangle
@@ -27,22 +26,13 @@
 #include <cmath>
 
 #include "common.h"
+#include "scene_cells.h"
 #include "../../include/gennbv_hip.h"
 
 namespace {
 
 constexpr int kWavesPerBlock = 4;
 constexpr double kPi = 3.14159265358979323846;
-
-struct V3 {
-    double x, y, z;
-};
-__device__ __forceinline__ V3 v3(double x, double y, double z) { return V3{x, y, z}; }
-__device__ __forceinline__ V3 operator-(V3 a, V3 b) { return v3(a.x - b.x, a.y - b.y, a.z - b.z); }
-__device__ __forceinline__ V3 operator+(V3 a, V3 b) { return v3(a.x + b.x, a.y + b.y, a.z + b.z); }
-__device__ __forceinline__ V3 operator*(V3 a, double s) { return v3(a.x * s, a.y * s, a.z * s); }
-__device__ __forceinline__ double dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ V3 cross(V3 a, V3 b) { return v3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
 
 // squared distance between the axis line (through the origin, unit direction a) and the segment p + u d, u in [u0, u1]
 __device__ __forceinline__ double seg_axis_dist2(V3 p, V3 d, V3 a, double u0, double u1)
@@ -134,13 +124,6 @@ __device__ __forceinline__ double solid_angle(const float *q, V3 c)
     return 2.0 * atan2(num, den);
 }
 
-__device__ __forceinline__ double wave_sum_xor(double v)
-{
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) v += __shfl_xor(v, d, kWave);  // butterfly: every lane ends with the same bits
-    return v;
-}
-
 // the contact code of env e's scene at pose p (one wave; the same value in every lane)
 __device__ __forceinline__ uint8_t collide_code(const GnbvMeshScene &sc, const GnbvMeshObjects &ob, int e, const float *__restrict__ p,
                                                 float radius, float half_length, int ground)
@@ -157,67 +140,17 @@ __device__ __forceinline__ uint8_t collide_code(const GnbvMeshScene &sc, const G
     const bool finite = isfinite(c.x) && isfinite(c.y) && isfinite(c.z) && isfinite(a.x) && isfinite(a.y) && isfinite(a.z);
 
     // ---- (S): candidates from the cells the body's AABB overlaps
-    bool hit = false;
-    const int rx = sc.cell_res[e * 3 + 0], ry = sc.cell_res[e * 3 + 1], rz = sc.cell_res[e * 3 + 2];
-    if (finite && rx > 0) {
+    bool s_hit = false;
+    if (finite) {
         const double grow = 1e-12 * (fmax(fabs(c.x), fmax(fabs(c.y), fabs(c.z))) + r + h);  // rounding of a and of e_k
         const double blo[3] = {c.x - ex - grow, c.y - ey - grow, c.z - ez - grow};
         const double bhi[3] = {c.x + ex + grow, c.y + ey + grow, c.z + ez + grow};
-        const int res[3] = {rx, ry, rz};
-        int c0[3], c1[3];
-        bool any = true;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            // (a 1e-6-cell margin: a point on a cell boundary may count in either neighbour)
-            const double clo = (double)sc.cell_lo[e * 3 + k], csz = (double)sc.cell_size[e * 3 + k];
-            const double f0 = floor((blo[k] - clo) / csz - 1e-6), f1 = floor((bhi[k] - clo) / csz + 1e-6);
-            any = any && f1 >= 0.0 && f0 <= (double)(res[k] - 1);
-            c0[k] = (int)fmin(fmax(f0, 0.0), (double)(res[k] - 1));
-            c1[k] = (int)fmax(fmin(f1, (double)(res[k] - 1)), 0.0);
-        }
-        if (any) {
-            const int nx = c1[0] - c0[0] + 1, ny = c1[1] - c0[1] + 1, nz = c1[2] - c0[2] + 1;
-            const int ncell = nx * ny * nz;
-            const int base = sc.cell_base[e];
-            for (int j0 = 0; j0 < ncell; j0 += kWave) {  // wave-uniform trip counts: every lane reaches every shuffle
-                const int j = j0 + lane;
-                int start = 0, cnt = 0;
-                if (j < ncell) {
-                    const int kx = c0[0] + j % nx, ky = c0[1] + (j / nx) % ny, kz = c0[2] + j / (nx * ny);
-                    const int cell = base + kx + rx * (ky + ry * kz);
-                    start = sc.cell_start[cell];
-                    cnt = sc.cell_start[cell + 1] - start;
-                }
-                const int incl = wave_inclusive_scan(cnt);
-                const int off = start - (incl - cnt);  // entry of flat index i in this lane's cell = off + i
-                const int total = __shfl(incl, kWave - 1, kWave);
-                for (int i0 = 0; i0 < total; i0 += kWave) {
-                    const int i = i0 + lane;
-                    // the lane whose cell holds flat entry i: the number of lanes with incl <= i (6 fixed steps)
-                    int pos = 0;
-#pragma unroll
-                    for (int s = kWave / 2; s > 0; s >>= 1)
-                        if (__shfl(incl, pos + s - 1, kWave) <= i) pos += s;
-                    const int k = __shfl(off, pos, kWave) + i;
-                    if (i < total && !hit) {
-                        const int t = sc.cell_tris[k];
-                        const float *q = sc.tris + (size_t)t * 9;
-                        bool near = true;
-#pragma unroll
-                        for (int d = 0; d < 3; ++d) {
-                            const double tmin = fmin(fmin((double)q[d], (double)q[3 + d]), (double)q[6 + d]);
-                            const double tmax = fmax(fmax((double)q[d], (double)q[3 + d]), (double)q[6 + d]);
-                            near = near && tmax >= blo[d] && tmin <= bhi[d];
-                        }
-                        hit = near && tri_cylinder(q, c, a, r2, h);
-                    }
-                    if (__any(hit)) break;
-                }
-                if (__any(hit)) break;
-            }
-        }
+        const EnvCells cells = load_env_cells(sc, e);
+        CellRange range;
+        if (cell_range(cells, blo, bhi, range))
+            s_hit = wave_any_listed_tri(sc, cells, range, no_cells(),
+                                        [&](const float *q) { return tri_aabb_meets(q, blo, bhi) && tri_cylinder(q, c, a, r2, h); });
     }
-    const bool s_hit = __any(hit);
 
     // ---- (I): the centre inside an object's solid (only without (S))
     bool inside = false;
@@ -238,7 +171,7 @@ __device__ __forceinline__ uint8_t collide_code(const GnbvMeshScene &sc, const G
                 const int t0 = ob.obj_tri_start[obj], t1 = ob.obj_tri_start[obj + 1];
                 double sum = 0.0;
                 for (int t = t0 + lane; t < t1; t += kWave) sum += solid_angle(sc.tris + (size_t)ob.obj_tris[t] * 9, c);
-                const double w = wave_sum_xor(sum) / (4.0 * kPi);
+                const double w = wave_sum_all(sum) / (4.0 * kPi);
                 inside = fabs(w) >= 0.5;
             }
         }
@@ -281,11 +214,9 @@ static bool collide_args_ok(const GnbvMeshScene *scene, const GnbvMeshObjects *o
     if (scene == nullptr || objects == nullptr || poses == nullptr || contact_out == nullptr) return false;
     const GnbvMeshScene &sc = *scene;
     const GnbvMeshObjects &ob = *objects;
-    return sc.n > 0 && ob.n == sc.n && ob.num_objects >= 0 && poses_row_stride >= 6 && std::isfinite(radius) && radius > 0.0f &&
-           std::isfinite(half_length) && half_length >= 0.0f && sc.cell_lo != nullptr && sc.cell_size != nullptr &&
-           sc.cell_res != nullptr && sc.cell_base != nullptr && sc.cell_start != nullptr && ob.env_obj_start != nullptr &&
-           ob.obj_tri_start != nullptr &&
-           // tris / cell_tris / obj_aabb / obj_tris may be NULL when no env has a triangle
+    return scene_ok(sc) && ob.n == sc.n && ob.num_objects >= 0 && poses_row_stride >= 6 && std::isfinite(radius) && radius > 0.0f &&
+           std::isfinite(half_length) && half_length >= 0.0f && ob.env_obj_start != nullptr && ob.obj_tri_start != nullptr &&
+           // obj_aabb / obj_tris (and the scene's tris) may be NULL when no env has an object
            (ob.num_objects == 0 || (ob.obj_aabb != nullptr && ob.obj_tris != nullptr && sc.tris != nullptr));
 }
 

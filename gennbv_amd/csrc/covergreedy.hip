@@ -57,16 +57,6 @@ __device__ __forceinline__ int wave_gain(const uint32_t *m, const uint32_t *c, i
     return __shfl(wave_reduce_sum(s), 0, kWave);
 }
 
-__device__ __forceinline__ long long wave_reduce_max(long long v)
-{
-#pragma unroll
-    for (int d = kWave / 2; d > 0; d >>= 1) {
-        const long long o = __shfl_xor(v, d, kWave);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
 __global__ __launch_bounds__(kCgGainWaves * kWave) void k_cg_gains(CgParams p)
 {
     // XCD-aware block -> (env, group of candidates): all workgroups of an env run on one XCD (viewcover.hip k_view_cover)
@@ -138,8 +128,8 @@ __global__ __launch_bounds__(kCgMaxWaves * kWave) void k_cg_rounds(CgParams p)
                 if (s_at[j] == now) kf = key > kf ? key : kf;
                 else ks = key > ks ? key : ks;
             }
-            kf = wave_reduce_max(kf);
-            ks = wave_reduce_max(ks);
+            kf = wave_max_all(kf);
+            ks = wave_max_all(ks);
             if (lane == 0) {
                 s_fresh[wave] = kf;
                 s_stale[wave] = ks;

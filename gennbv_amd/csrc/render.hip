@@ -17,6 +17,7 @@
 // axes and the ray's dominant-axis permutation are selects, not arrays, so nothing is runtime-indexed per lane.
 #include "common.h"
 #include "raytrace.h"
+#include "scene_cells.h"
 #include "../../include/gennbv_hip.h"
 
 namespace {
@@ -77,9 +78,7 @@ GNBV_API int gnbv_render_depth(const GnbvMeshScene *scene, const float *poses, i
     GNBV_CHECK_ARG(scene != nullptr && inv_intri != nullptr && poses != nullptr && c2w_out != nullptr);
     GNBV_CHECK_ARG(depth_raw != nullptr && seg_raw != nullptr);
     const GnbvMeshScene sc = *scene;
-    GNBV_CHECK_ARG(sc.n > 0 && sc.n <= 65535 && h > 0 && w > 0 && poses_row_stride >= 6);
-    GNBV_CHECK_ARG(sc.cell_lo != nullptr && sc.cell_size != nullptr && sc.cell_res != nullptr && sc.cell_base != nullptr);
-    GNBV_CHECK_ARG(sc.cell_start != nullptr);  // tris / tri_obj / cell_tris may be NULL when no env has a triangle
+    GNBV_CHECK_ARG(scene_ok(sc) && sc.n <= 65535 && h > 0 && w > 0 && poses_row_stride >= 6);
     GNBV_CHECK_ARG(rgba == nullptr || ((uintptr_t)rgba & 3) == 0);
     hipStream_t st = gnbv_stream(stream);
     k_render_camera<<<(sc.n + 63) / 64, 64, 0, st>>>(poses, poses_row_stride, sc.n, c2w_out);

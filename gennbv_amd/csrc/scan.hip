@@ -517,8 +517,6 @@ struct ScoreLayout {
     size_t off_b, off_pts, off_nodes, off_dx, off_dy, off_hist, off_partial, off_active, total;
 };
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 ScoreLayout score_layout(int n, int64_t cap, int64_t gt_points)
 {
     ScoreLayout L;

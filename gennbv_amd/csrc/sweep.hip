@@ -17,9 +17,9 @@
 //        cut into pieces no longer than about the shortest cell edge (at most kMaxPieces: longer pieces list more cells, never
 //        fewer);
 //     2. per piece: the cell range of its R-grown AABB, minus the cells the previous piece's range held (along a straight
-//        line the ranges move monotonically, so a cell is listed once per run of pieces).  Up to 64 cells at a time: lane j
-//        reads cell j's list bounds, one wave scan makes the lists one flat range the lanes stride over (as collide_code).  A
-//        triangle listed in several cells is tested more than once: the results are ORed;
+//        line the ranges move monotonically, so a cell is listed once per run of pieces), walked by the wave as collide_code
+//        walks its range (scene_cells.h cell_range, wave_any_listed_tri).  A triangle listed in several cells is tested more
+//        than once: the results are ORed;
 //     3. per triangle, fp64: an AABB reject against the whole segment's R-grown box, then the exact predicate against the WHOLE
 //        segment: dist = 0 if the segment pierces the triangle, else the minimum of the plane distance of either endpoint
 //        whose projection falls inside the triangle and the three segment-edge distances (which hold every
@@ -29,6 +29,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "scene_cells.h"
 #include "../../include/gennbv_hip.h"
 
 namespace {
@@ -36,15 +37,6 @@ namespace {
 constexpr int kWavesPerBlock = 4;
 constexpr int kMaxPieces = 4096;
 
-struct V3 {
-    double x, y, z;
-};
-__device__ __forceinline__ V3 v3(double x, double y, double z) { return V3{x, y, z}; }
-__device__ __forceinline__ V3 operator-(V3 a, V3 b) { return v3(a.x - b.x, a.y - b.y, a.z - b.z); }
-__device__ __forceinline__ V3 operator+(V3 a, V3 b) { return v3(a.x + b.x, a.y + b.y, a.z + b.z); }
-__device__ __forceinline__ V3 operator*(V3 a, double s) { return v3(a.x * s, a.y * s, a.z * s); }
-__device__ __forceinline__ double dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ V3 cross(V3 a, V3 b) { return v3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
 __device__ __forceinline__ double clamp01(double v) { return fmin(fmax(v, 0.0), 1.0); }
 
 // squared distance between the segments p1 + s d1 and p2 + t d2, s, t in [0, 1] (either may have zero length)
@@ -110,7 +102,6 @@ __device__ bool tri_capsule(const float *q, V3 a, V3 d, double r2)
 __device__ __forceinline__ uint8_t sweep_code(const GnbvMeshScene &sc, int e, const float *__restrict__ pf, const float *__restrict__ pt,
                                               float radius, int ground)
 {
-    const int lane = threadIdx.x & (kWave - 1);
     const V3 a = v3((double)pf[0], (double)pf[1], (double)pf[2]);
     const V3 b = v3((double)pt[0], (double)pt[1], (double)pt[2]);
     if (!(isfinite(a.x) && isfinite(a.y) && isfinite(a.z) && isfinite(b.x) && isfinite(b.y) && isfinite(b.z))) return 0;
@@ -118,24 +109,23 @@ __device__ __forceinline__ uint8_t sweep_code(const GnbvMeshScene &sc, int e, co
     const V3 d = b - a;
     const uint8_t g_bit = (ground != 0 && fmin(a.z, b.z) - R <= 0.0) ? 16 : 0;
 
-    const int res[3] = {sc.cell_res[e * 3 + 0], sc.cell_res[e * 3 + 1], sc.cell_res[e * 3 + 2]};
-    if (res[0] <= 0) return g_bit;  // an env without triangles
+    const EnvCells cells = load_env_cells(sc, e);
+    if (cells.res[0] <= 0) return g_bit;  // an env without triangles
     const double av[3] = {a.x, a.y, a.z}, dv[3] = {d.x, d.y, d.z};
     const double amax = fmax(fmax(fabs(a.x), fabs(b.x)), fmax(fmax(fabs(a.y), fabs(b.y)), fmax(fabs(a.z), fabs(b.z))));
     const double grow = R + 1e-12 * (amax + R);  // R, and the rounding of the piece ends
-    double clo[3], csz[3], blo[3], bhi[3];
+    double blo[3], bhi[3];
     // ---- 1. the part s in [s0, s1] of the segment inside the grid grown by R
     double s0 = 0.0, s1 = 1.0, cmin = 0.0;
     bool any = true;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        clo[k] = (double)sc.cell_lo[e * 3 + k];
-        csz[k] = (double)sc.cell_size[e * 3 + k];
-        cmin = k == 0 ? csz[k] : fmin(cmin, csz[k]);
+        const double clo = cells.lo[k], csz = cells.size[k];
+        cmin = k == 0 ? csz : fmin(cmin, csz);
         blo[k] = fmin(av[k], av[k] + dv[k]) - grow;
         bhi[k] = fmax(av[k], av[k] + dv[k]) + grow;
-        const double pad = grow + 1e-6 * csz[k];
-        const double glo = clo[k] - pad, ghi = clo[k] + csz[k] * (double)res[k] + pad;
+        const double pad = grow + 1e-6 * csz;
+        const double glo = clo - pad, ghi = clo + csz * (double)cells.res[k] + pad;
         if (dv[k] == 0.0) {
             any = any && av[k] >= glo && av[k] <= ghi;
         } else {
@@ -148,73 +138,26 @@ __device__ __forceinline__ uint8_t sweep_code(const GnbvMeshScene &sc, int e, co
     const double len = sqrt(dot(d, d)) * (s1 - s0);
     const int np = (int)fmin(fmax(ceil(len / cmin), 1.0), (double)kMaxPieces);
 
-    // ---- 2./3. the pieces
-    bool hit = false;
-    const int rx = res[0], ry = res[1];
-    const int base = sc.cell_base[e];
-    int q0[3] = {0, 0, 0}, q1[3] = {-1, -1, -1};  // the previous piece's cell range (empty)
-    for (int p = 0; p < np; ++p) {  // wave-uniform trip counts: every lane reaches every shuffle
+    // ---- 2./3. the pieces (np is wave-uniform)
+    CellRange prev = no_cells();  // the previous piece's cell range
+    for (int p = 0; p < np; ++p) {
         const double sa = s0 + (s1 - s0) * ((double)p / (double)np), sb = s0 + (s1 - s0) * ((double)(p + 1) / (double)np);
-        int c0[3], c1[3];
-        bool in_grid = true;
+        double plo[3], phi[3];  // the piece's R-grown AABB
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             const double xa = av[k] + dv[k] * sa, xb = av[k] + dv[k] * sb;
-            // (a 1e-6-cell margin: a point on a cell boundary may count in either neighbour)
-            const double f0 = floor((fmin(xa, xb) - grow - clo[k]) / csz[k] - 1e-6), f1 = floor((fmax(xa, xb) + grow - clo[k]) / csz[k] + 1e-6);
-            in_grid = in_grid && f1 >= 0.0 && f0 <= (double)(res[k] - 1);
-            c0[k] = (int)fmin(fmax(f0, 0.0), (double)(res[k] - 1));
-            c1[k] = (int)fmax(fmin(f1, (double)(res[k] - 1)), 0.0);
+            plo[k] = fmin(xa, xb) - grow;
+            phi[k] = fmax(xa, xb) + grow;
         }
-        if (!in_grid) {
-            q1[0] = -1;
+        CellRange range;
+        if (!cell_range(cells, plo, phi, range)) {
+            prev = no_cells();
             continue;
         }
-        const int nx = c1[0] - c0[0] + 1, ny = c1[1] - c0[1] + 1, nz = c1[2] - c0[2] + 1;
-        const int ncell = nx * ny * nz;
-        for (int j0 = 0; j0 < ncell; j0 += kWave) {
-            const int j = j0 + lane;
-            int start = 0, cnt = 0;
-            if (j < ncell) {
-                const int kx = c0[0] + j % nx, ky = c0[1] + (j / nx) % ny, kz = c0[2] + j / (nx * ny);
-                const bool seen = kx >= q0[0] && kx <= q1[0] && ky >= q0[1] && ky <= q1[1] && kz >= q0[2] && kz <= q1[2];
-                if (!seen) {
-                    const int cell = base + kx + rx * (ky + ry * kz);
-                    start = sc.cell_start[cell];
-                    cnt = sc.cell_start[cell + 1] - start;
-                }
-            }
-            const int incl = wave_inclusive_scan(cnt);
-            const int off = start - (incl - cnt);  // entry of flat index i in this lane's cell = off + i
-            const int total = __shfl(incl, kWave - 1, kWave);
-            for (int i0 = 0; i0 < total; i0 += kWave) {
-                const int i = i0 + lane;
-                // the lane whose cell holds flat entry i: the number of lanes with incl <= i (6 fixed steps)
-                int pos = 0;
-#pragma unroll
-                for (int s = kWave / 2; s > 0; s >>= 1)
-                    if (__shfl(incl, pos + s - 1, kWave) <= i) pos += s;
-                const int k = __shfl(off, pos, kWave) + i;
-                if (i < total) {
-                    const int t = sc.cell_tris[k];
-                    const float *q = sc.tris + (size_t)t * 9;
-                    bool near = true;
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        const double tmin = fmin(fmin((double)q[c], (double)q[3 + c]), (double)q[6 + c]);
-                        const double tmax = fmax(fmax((double)q[c], (double)q[3 + c]), (double)q[6 + c]);
-                        near = near && tmax >= blo[c] && tmin <= bhi[c];
-                    }
-                    hit = near && tri_capsule(q, a, d, r2);
-                }
-                if (__any(hit)) return (uint8_t)(8 | g_bit);
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            q0[k] = c0[k];
-            q1[k] = c1[k];
-        }
+        if (wave_any_listed_tri(sc, cells, range, prev,
+                                [&](const float *q) { return tri_aabb_meets(q, blo, bhi) && tri_capsule(q, a, d, r2); }))
+            return (uint8_t)(8 | g_bit);
+        prev = range;
     }
     return g_bit;
 }
@@ -245,8 +188,7 @@ GNBV_API int gnbv_sweep_sphere(const GnbvMeshScene *scene, const float *from, in
 {
     GNBV_CHECK_ARG(scene != nullptr && from != nullptr && to != nullptr && contact_out != nullptr);
     const GnbvMeshScene sc = *scene;
-    GNBV_CHECK_ARG(sc.n > 0 && sc.cell_lo != nullptr && sc.cell_size != nullptr && sc.cell_res != nullptr && sc.cell_base != nullptr &&
-                   sc.cell_start != nullptr);
+    GNBV_CHECK_ARG(scene_ok(sc));
     GNBV_CHECK_ARG(k >= 1 && (int64_t)sc.n * k <= 0x7fffffff);
     GNBV_CHECK_ARG(to_row_stride >= 3 && from_env_stride >= 3 && (from_item_stride == 0 || from_item_stride >= 3));
     GNBV_CHECK_ARG(std::isfinite(radius) && radius > 0.0f && (accumulate == 0 || accumulate == 1));

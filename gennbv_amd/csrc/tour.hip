@@ -44,23 +44,6 @@ struct TourParams {
     int32_t *status;
 };
 
-__device__ __forceinline__ long long wave_min_all(long long v)
-{
-#pragma unroll
-    for (int d = kWave / 2; d > 0; d >>= 1) {
-        const long long o = __shfl_xor(v, d, kWave);
-        v = o < v ? o : v;
-    }
-    return v;  // the same value in every lane
-}
-
-__device__ __forceinline__ long long wave_sum_all(long long v)
-{
-#pragma unroll
-    for (int d = kWave / 2; d > 0; d >>= 1) v += __shfl_xor(v, d, kWave);
-    return v;
-}
-
 template <int kLanes>
 __global__ __launch_bounds__(kLanes) void k_tour_route(TourParams a)
 {

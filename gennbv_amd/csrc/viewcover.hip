@@ -5,7 +5,7 @@
 // For env e, candidate j and the pixel lattice u = s/2 + i s, v = s/2 + j s: the pixel's ray is traced with the renderer's own
 // code (raytrace.h trace_pixel: the same bits as k_render_depth), a foreground hit is back-projected with the voxel update's
 // canonical chain (backproject.h process_depth, pixel_to_world) and mapped to its voxel with the update's keep test
-// (voxel.hip point_to_voxel, restated below with explicit _rn intrinsics).  No image is ever stored.
+// (voxel_frame.h point_to_voxel, the update's own code).  No image is ever stored.
 //
 //   k_view_cover<WIN>   workgroup (env, chunk of candidates[, window of bit-set words]):
 //     1. 16 lanes build the camera matrices of the next 16 candidates (raytrace.h camera_of_pose: fp64 trig, off the
@@ -28,6 +28,8 @@
 #include "common.h"
 #include "backproject.h"
 #include "raytrace.h"
+#include "scene_cells.h"
+#include "voxel_frame.h"
 #include "../../include/gennbv_hip.h"
 
 namespace {
@@ -50,41 +52,6 @@ struct VcParams {
     uint32_t *seen;
     uint32_t *mask;  // [n, k, words], read by the MASK instantiations only
 };
-
-struct CoverFrame {  // per-env constants of scanned_pts_to_idx_3D (voxel.hip load_frame)
-    float vmin[3], vmax[3], vox[3];
-};
-
-__device__ __forceinline__ CoverFrame load_cover_frame(const float *range6, const float *vox3)
-{
-    CoverFrame f;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float v = vox3[a];
-        const float half = __fmul_rn(0.5f, v);
-        f.vox[a] = v;
-        f.vmax[a] = __fadd_rn(range6[2 * a], half);
-        f.vmin[a] = __fsub_rn(range6[2 * a + 1], half);
-    }
-    return f;
-}
-
-// voxel.hip point_to_voxel: the linear voxel index (x*G + y)*G + z, or -1 when the point is dropped (strict bounds)
-__device__ __forceinline__ int cover_point_to_voxel(const float *p, const CoverFrame &f, int g)
-{
-    bool keep = true;
-    int ix[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float q = __fdiv_rn(__fsub_rn(p[a], f.vmin[a]), f.vox[a]);
-        const float fl = floorf(q);
-        keep = keep && (f.vmax[a] > p[a]) && (p[a] > f.vmin[a]);
-        int i = (fl == fl && fabsf(fl) < 1.0e9f) ? (int)fl : 0;
-        i = i < 0 ? 0 : (i > g - 1 ? g - 1 : i);
-        ix[a] = i;
-    }
-    return keep ? (ix[0] * g + ix[1]) * g + ix[2] : -1;
-}
 
 __global__ __launch_bounds__(256) void k_vc_zero(int32_t *cover, int64_t count)
 {
@@ -114,7 +81,7 @@ __global__ __launch_bounds__(kMaxThreads) void k_view_cover(VcParams p)
     uint4 *s_bits4 = reinterpret_cast<uint4 *>(s_bits);
     for (int i = tid; i < nw / 4; i += nthreads) s_bits4[i] = make_uint4(0u, 0u, 0u, 0u);
 
-    const CoverFrame f = load_cover_frame(p.range_gt + e * 6, p.voxel_size + e * 3);
+    const VoxelFrame f = load_frame(p.range_gt + e * 6, p.voxel_size + e * 3);
     const uint32_t *gt = p.gt + (size_t)e * p.words;
     const uint32_t *scanned = p.scanned != nullptr ? p.scanned + (size_t)e * p.words : nullptr;
     const bool count = p.cover != nullptr;
@@ -158,7 +125,8 @@ __global__ __launch_bounds__(kMaxThreads) void k_view_cover(VcParams p)
             const float d = process_depth(-best, p.sense_dist);
             float wp[3];
             pixel_to_world(d, fu, fv, p.kinv, M, wp);
-            const int lin = cover_point_to_voxel(wp, f, g);
+            int ix[3];
+            const int lin = point_to_voxel(wp, f, g, ix);
             if (lin < 0) continue;
             if (!WIN || win == 0) ++n_hits;
             const unsigned wi = (unsigned)((lin >> 5) - w0);
@@ -270,8 +238,7 @@ static int view_cover_impl(const GnbvMeshScene *scene, const GnbvViewCover *args
         GNBV_CHECK_ARG(mask_bits != nullptr && ((uintptr_t)mask_bits & 15) == 0);
     else
         GNBV_CHECK_ARG(a.cover != nullptr || a.seen_bits != nullptr);
-    GNBV_CHECK_ARG(sc.cell_lo != nullptr && sc.cell_size != nullptr && sc.cell_res != nullptr && sc.cell_base != nullptr);
-    GNBV_CHECK_ARG(sc.cell_start != nullptr);  // tris / tri_obj / cell_tris may be NULL when no env has a triangle
+    GNBV_CHECK_ARG(scene_ok(sc));
     GNBV_CHECK_ARG((((uintptr_t)a.gt_bits | (uintptr_t)a.scanned_bits | (uintptr_t)a.seen_bits) & 15) == 0);
     VcParams p;
     p.sc = sc;

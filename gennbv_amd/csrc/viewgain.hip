@@ -567,8 +567,6 @@ struct VsPlan {
     size_t off_cams, off_rec, off_meta, bytes;
 };
 
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 inline bool vs_plan(int n, int k, int g, int h, int w, int stride, VsPlan &pl)
 {
     if (!(n > 0 && k > 0 && g >= 2 && g <= kMaxSlabGrid && h > 0 && w > 0 && stride >= 1 && h <= 32768 && w <= 32768)) return false;

@@ -35,48 +35,7 @@
 #include <stdio.h>
 
 #include "backproject.h"
-
-struct VoxelFrame {  // per-env constants of scanned_pts_to_idx_3D
-    float vmin[3], vmax[3], vox[3];
-};
-
-__device__ __forceinline__ VoxelFrame load_frame(const float *range6, const float *vox3)
-{
-    VoxelFrame f;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float v = vox3[a];
-        const float half = __fmul_rn(0.5f, v);
-        f.vox[a] = v;
-        f.vmax[a] = __fadd_rn(range6[2 * a], half);
-        f.vmin[a] = __fsub_rn(range6[2 * a + 1], half);
-    }
-    return f;
-}
-
-// returns the linear voxel index (x*G + y)*G + z, or -1 when the point is dropped
-__device__ __forceinline__ int point_to_voxel(const float *p, const VoxelFrame &f, int g, int *ix)
-{
-    bool keep = true;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float q = __fdiv_rn(__fsub_rn(p[a], f.vmin[a]), f.vox[a]);
-        const float fl = floorf(q);
-        keep = keep && (f.vmax[a] > p[a]) && (p[a] > f.vmin[a]);
-        int i = (fl == fl && fabsf(fl) < 1.0e9f) ? (int)fl : 0;
-        i = i < 0 ? 0 : (i > g - 1 ? g - 1 : i);
-        ix[a] = i;
-    }
-    return keep ? (ix[0] * g + ix[1]) * g + ix[2] : -1;
-}
-
-__device__ __forceinline__ int pose_axis_to_idx(float p, float range_min, float v)
-{
-    const float vmin = __fsub_rn(range_min, __fmul_rn(0.5f, v));
-    const float fl = floorf(__fdiv_rn(__fsub_rn(p, vmin), v));
-    // float -> int64 -> int32 (pts_source.int(), utils.py:32); poses are finite
-    return (int)(long long)fl;
-}
+#include "voxel_frame.h"
 
 // ---------------------------------------------------------------------------
 // integer 3-D Bresenham (gennbv/utils.py:48-167).  Visit(x, y, z) is invoked for
