@@ -15,36 +15,20 @@
 //     kLds (mode 1): the workgroup first packs "this voxel blocks" into one bit per voxel in LDS (64 voxels per wave ballot,
 //       coalesced reads of either grid form; G^3 / 8 bytes, 32 KiB at 64^3) and a node reads the z-run of a (x, y) column as whole
 //       words: a word with no blocking bit inside the window costs no arithmetic.  Lanes of a wave are x-neighbours, their words lie
-//       G^2 / 32 apart -- at G = 64 all on one bank -- so word w is kept at w ^ ((w >> shift) & 31), shift ~ log2(G^2 / 32), >= 5: a
-//       permutation inside each aligned group of 32 words that spreads x-neighbours over the banks.
+//       G^2 / 32 apart -- at G = 64 all on one bank -- so the words are swizzled (map_bits.h has the pack, shared with sweepmap.hip).
 //     !kLds (mode 2): the same decisions with the voxels read from global memory, for grids whose bits do not fit (up to 128^3).
 //     kF32: the grid is the fp32 slice of an observation row, else int8 rows.
 #include <algorithm>
 #include <cmath>
 
 #include "common.h"
+#include "map_bits.h"
 #include "../../include/gennbv_hip.h"
 
 namespace {
 
 constexpr int kMapLanes = 512;
 constexpr int kMapWaves = kMapLanes / kWave;
-constexpr int kMapLdsBytes = 160 * 1024;
-constexpr int kMapMaxGrid = 128;
-
-// LDS of mode 1: one bit per voxel in whole 64-voxel ballots, rounded up to a group of 32 words (the swizzle stays inside a group)
-constexpr size_t map_lds_bytes(int g)
-{
-    const size_t words = 2 * (((size_t)g * g * g + 63) / 64);
-    return 4 * ((words + 31) / 32 * 32);
-}
-
-constexpr int map_lds_max_grid()
-{
-    int g = 1;
-    while (g < kMapMaxGrid && map_lds_bytes(g + 1) <= (size_t)kMapLdsBytes) ++g;
-    return g;
-}
 
 struct MapArgs {
     int g, nx, ny, nz, m, words;
@@ -53,19 +37,6 @@ struct MapArgs {
     int unknown_blocks, outside_blocks, ground;
     double lo[3], h[3], rho, rho2;
 };
-
-template <bool kF32>
-__device__ __forceinline__ bool voxel_blocks(const void *__restrict__ tri, int idx, bool unknown_blocks)
-{
-    if (kF32) {
-        const float t = static_cast<const float *>(tri)[idx];
-        return t > 0.0f || (unknown_blocks && t == 0.0f);
-    }
-    const int t = static_cast<const int8_t *>(tri)[idx];
-    return t > 0 || (unknown_blocks && t == 0);
-}
-
-__device__ __forceinline__ int map_swizzle(int w, int shift) { return w ^ ((w >> shift) & 31); }
 
 // the squared gap on one axis between node coordinate p and voxel i = [o + i v, o + (i + 1) v]
 __device__ __forceinline__ double gap2(double o, double v, int i, double p)
@@ -142,17 +113,7 @@ __global__ __launch_bounds__(kMapLanes) void k_flight_blocked_tri(const void *__
     const void *tri = static_cast<const char *>(tri_base) + (size_t)e * row_bytes;
 
     if (kLds) {
-        const int g3 = a.g * a.g * a.g, groups = (g3 + kWave - 1) / kWave;
-        const bool unk = a.unknown_blocks != 0;
-        for (int q = wave; q < groups; q += kMapWaves) {  // (q is the same in every lane of a wave: the ballot is whole)
-            const int vox = q * kWave + lane;
-            const bool b = vox < g3 && voxel_blocks<kF32>(tri, vox, unk);
-            const unsigned long long mask = __ballot(b);
-            if (lane == 0) {
-                bits[map_swizzle(2 * q, a.shift)] = (uint32_t)mask;
-                bits[map_swizzle(2 * q + 1, a.shift)] = (uint32_t)(mask >> 32);
-            }
-        }
+        map_pack_bits<kF32, kMapWaves>(tri, a.g, a.unknown_blocks != 0, a.shift, bits);
         __syncthreads();
     }
 
@@ -237,8 +198,7 @@ GNBV_API int gnbv_flight_blocked_tri(const int8_t *tri_i8, int64_t tri_i8_row_st
     a.chunk_waves = (int)((groups + chunks - 1) / chunks);
     a.chunks = (int)((groups + a.chunk_waves - 1) / a.chunk_waves);
     GNBV_CHECK_ARG((int64_t)n * a.chunks <= 0x7fffffff);
-    a.shift = 5;
-    while (a.shift < 20 && (2 << a.shift) * 3 <= (g * g / 32) * 4) ++a.shift;  // ~ round(log2(G^2 / 32))
+    a.shift = map_swizzle_shift(g);
     a.unknown_blocks = unknown_blocks != 0;
     a.outside_blocks = outside_blocks != 0;
     a.ground = ground != 0;

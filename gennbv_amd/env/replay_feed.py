@@ -44,6 +44,11 @@ go through ONE sweep_candidates call and their codes are ORed into `path_code` a
 dropped.  `flight_length` adds the route's length where there is one and the straight distance otherwise.  After the voxel
 update the field is refreshed from the tri-class grid the step has just written (grid_i8_out where given, else the observation's
 grid slice) and updated from the poses arrived at.
+With `flight.shortcut` the pilot also asks its map about straight legs (BeliefFlightField.sweep, csrc/sweepmap.hip, over the
+snapshot of the map it had): it flies straight from the previous pose to the farthest waypoint of the route -- the new pose
+included -- that the map shows in the clear, and the rest of the route from there.  The flown legs alone go to the truth,
+`flight_length` adds their Euclidean lengths, `routed` is true where a route node was flown, and `skipped` [N] int64 is the number
+of waypoints the straight first leg passed over (0: the route as it was; the route's node count: straight to the new pose).
 """
 from __future__ import annotations
 
@@ -159,6 +164,7 @@ class ReplayFeedEnv:
         self.path_code = torch.zeros(n, dtype=torch.uint8, device=self.device) if flight is not None else None
         self._belief = flight is not None and bool(getattr(flight, "belief", False))
         self.route_overflow = self.routed = None
+        self.skipped = None  # with flight.shortcut: the waypoints the last step's straight first leg skipped, int64 [N]
         if self._belief:
             if int(flight.grid_size) != int(cfg.grid_size):
                 raise ValueError(f"flight is built for a {flight.grid_size}^3 grid, the env's is {cfg.grid_size}^3")
@@ -170,6 +176,9 @@ class ReplayFeedEnv:
             self._node_pos = torch.as_tensor(flight.lattice.node_positions(), device=self.device).to(torch.float32)
             self.route_overflow = torch.zeros((), dtype=torch.int64, device=self.device)  # routes longer than the buffer, so far
             self.routed = torch.zeros(n, dtype=torch.bool, device=self.device)  # the last step flew a route of the field
+            if getattr(flight, "shortcut", False):
+                self._map_codes = torch.zeros(n, length + 1, dtype=torch.uint8, device=self.device)
+                self.skipped = torch.zeros(n, dtype=torch.int64, device=self.device)
         self.grid_size = cfg.grid_size
         self.max_episode_length = int(cfg.max_episode_length if max_episode_length is None else max_episode_length)
         self.max_episode_length_s = cfg.episode_length_s
@@ -360,16 +369,15 @@ class ReplayFeedEnv:
         self.flight_length.copy_(torch.where(first, torch.zeros_like(flown), self.flight_length + flown))
         fl.update(poses)
 
-    def _fly_belief_step(self):
-        """The sweep of _collide_step for a pilot that plans on its own map (module docstring): `flight` still holds the field
-        from the previous poses over the previous map.  Waypoints: previous pose, the route's nodes, new pose; an env without a
-        route has the one leg previous pose -> new pose, the straight flight.  The truth judges every leg."""
+    def _route_waypoints(self):
+        """The waypoints of the belief pilot's route [N, L + 2, 3] (previous pose, the route's nodes, then the new pose up to the
+        end) and the number of nodes [N] int64 (0: no route): `flight` still holds the field from the previous poses over the
+        previous map."""
         fl, poses, prev = self.flight, self.poses, self._prev_poses
         n, length = self.num_envs, self._route_len
         nodes, count = self._route_nodes, self._route_count
         fl.path_into(poses, nodes, count)
         self.route_overflow += (count < 0).sum()
-        routed = count > 0
         cnt = count.clamp(min=0).long()
         j = torch.arange(length, device=self.device)[None]
         back = (cnt[:, None] - 1 - j).clamp(min=0)  # nodes run target -> source: waypoint 1 + j is node count - 1 - j
@@ -379,6 +387,18 @@ class ReplayFeedEnv:
         way[:, 0] = prev[:, :3]
         way[:, 1:length + 1] = torch.where((j < cnt[:, None])[..., None], self._node_pos[ids], new)  # past the route: the new pose
         way[:, length + 1] = poses[:, :3]
+        return way, cnt
+
+    def _fly_belief_step(self):
+        """The sweep of _collide_step for a pilot that plans on its own map (module docstring): `flight` still holds the field
+        from the previous poses over the previous map.  Waypoints: previous pose, the route's nodes, new pose; an env without a
+        route has the one leg previous pose -> new pose, the straight flight.  The truth judges every leg."""
+        if self.flight.shortcut:
+            return self._fly_belief_shortcut_step()
+        fl, poses, prev = self.flight, self.poses, self._prev_poses
+        length = self._route_len
+        way, cnt = self._route_waypoints()
+        routed = self._route_count > 0
         codes = self.collision_mesh.sweep_candidates(way[:, :-1].contiguous(), way[:, 1:].contiguous(), self.collision,
                                                      self.episode_length_buf, out=self._route_codes)
         legs = torch.arange(length + 1, device=self.device)[None] <= cnt[:, None]  # count + 1 legs; 1 without a route
@@ -391,6 +411,39 @@ class ReplayFeedEnv:
         first = self.episode_length_buf <= 1  # after the step's head: the pose was set, not flown to
         self.flight_length.copy_(torch.where(first, torch.zeros_like(flown), self.flight_length + flown))
         self.routed.copy_(routed & ~first)
+
+    def _fly_belief_shortcut_step(self):
+        """_fly_belief_step with the straight shortcut judged on the map (`flight.shortcut`): of the legs w_0 -> w_j, j = 1 .. c + 1
+        (c route nodes, w_{c+1} the new pose), one gnbv_sweep_tri launch over the snapshot of the map the pilot had; j* is the
+        farthest one the map shows in the clear (1 if none).  The drone flies w_0 -> w_j* -> w_{j*+1} -> ... -> new pose, exactly
+        those legs are judged by the truth (the one sweep_candidates call, the skipped ones masked), `flight_length` adds their
+        Euclidean lengths, `routed` says whether a route node was flown, `skipped` = j* - 1."""
+        fl = self.flight
+        n, length = self.num_envs, self._route_len
+        way, cnt = self._route_waypoints()
+        ahead = way[:, 1:].contiguous()
+        if fl.has_map:
+            map_codes = fl.sweep(self._prev_poses, ahead, out=self._map_codes)
+        else:  # the env's very first step, the reset: no map yet, and every pose is set, not flown to
+            map_codes = self._map_codes.zero_()
+        jj = torch.arange(1, length + 2, device=self.device)[None]
+        clear = (map_codes == 0) & (jj <= cnt[:, None] + 1)
+        jstar = torch.where(clear, jj, torch.zeros_like(jj)).max(dim=1).values.clamp(min=1)
+        ahead[:, 0] = way[torch.arange(n, device=self.device), jstar]  # the first leg flown: w_0 -> w_j*
+        start = way[:, :-1].contiguous()
+        codes = self.collision_mesh.sweep_candidates(start, ahead, self.collision, self.episode_length_buf, out=self._route_codes)
+        leg = jj - 1  # leg i > 0 is w_i -> w_{i+1}
+        legs = (leg == 0) | ((leg >= jstar[:, None]) & (leg <= cnt[:, None]))
+        codes = torch.where(legs, codes, torch.zeros_like(codes))
+        code = ((codes & 8) != 0).any(dim=1).to(torch.uint8) * 8 | ((codes & 16) != 0).any(dim=1).to(torch.uint8) * 16
+        self.path_code.copy_(code)
+        self.collision_buf |= code
+        lens = (ahead - start).norm(dim=-1)
+        flown = torch.where(legs, lens, torch.zeros_like(lens)).sum(dim=1)
+        first = self.episode_length_buf <= 1  # after the step's head: the pose was set, not flown to
+        self.flight_length.copy_(torch.where(first, torch.zeros_like(flown), self.flight_length + flown))
+        self.routed.copy_((jstar <= cnt) & ~first)
+        self.skipped.copy_(torch.where(first, torch.zeros_like(jstar), jstar - 1))
 
     def _rgba_or_zero(self, rgba):
         if rgba is None:

@@ -169,13 +169,20 @@ class MapGreedyPolicy(GreedyGainPolicy):
     """GreedyGainPolicy for a pilot that knows only its own map: a candidate is refused iff the env's BeliefFlightField
     (ops/flight_field.py) holds no route to it -- contact = ~env.flight.reachable(poses) and nothing else.  The collision mesh is
     never consulted: not for the candidate's pose, not for the flight to it.  What the drone then really meets is the env's
-    business (ReplayFeedEnv flies the field's route and lets the true mesh judge it)."""
+    business (ReplayFeedEnv flies the field's route and lets the true mesh judge it).
+    `shortcut` (None: as env.flight.shortcut) also asks the map about the straight leg from env.poses to the candidate
+    (BeliefFlightField.sweep, the body's own radius instead of a node's inflated one): a candidate is then refused iff no route
+    reaches it AND its straight leg is blocked on the map -- contact = ~reachable & (sweep != 0).  Still no mesh predicate."""
 
     def __init__(self, env, k: int = 32, weights=(1, 4), seed: int = 0, stride: int = 4, look_at_scene: bool = False,
-                 gain_backend: Optional[Callable] = None):
+                 gain_backend: Optional[Callable] = None, shortcut: Optional[bool] = None):
         if not getattr(getattr(env, "flight", None), "belief", False):
             from .. import _lib
             raise _lib.GennbvHipError("MapGreedyPolicy needs an env whose flight is a BeliefFlightField")
+        self.shortcut = bool(getattr(env.flight, "shortcut", False)) if shortcut is None else bool(shortcut)
+        if self.shortcut and not getattr(env.flight, "shortcut", False):
+            from .. import _lib
+            raise _lib.GennbvHipError("MapGreedyPolicy(shortcut=True) needs BeliefFlightField(shortcut=True): the map snapshot")
         super().__init__(env, k=k, weights=weights, seed=seed, stride=stride, avoid_collisions=False, look_at_scene=look_at_scene,
                          gain_backend=gain_backend)
         self.avoid_collisions = True  # by the map: `contact` below; `sweep` stays off, no mesh predicate is launched
@@ -192,7 +199,10 @@ class MapGreedyPolicy(GreedyGainPolicy):
         return cand[torch.arange(n, device=cand.device), best], None, None
 
     def contact(self, poses: torch.Tensor) -> torch.Tensor:
-        return self._contact.copy_(~self.env.flight.reachable(poses))
+        fl = self.env.flight
+        if self.shortcut:
+            return self._contact.copy_(~fl.reachable(poses) & (fl.sweep(self.env.poses, poses) != 0))
+        return self._contact.copy_(~fl.reachable(poses))
 
 
 class OracleGainPolicy:

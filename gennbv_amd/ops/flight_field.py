@@ -14,7 +14,8 @@ The sweep count of the field kernel has a hard cap; an env that hit it is report
 by `path()`, the way ScanAccumulator reports its flags.  GPU only.
 
 BeliefFlightField is the same field over the agent's own map: its blocked bits are recomputed every step from the tri-class
-grid (csrc/flightmap.hip) and no mesh is consulted.
+grid (csrc/flightmap.hip) and no mesh is consulted.  With `shortcut=True` it also keeps a snapshot of that map and judges straight
+legs on it (`sweep`: gnbv_sweep_tri, csrc/sweepmap.hip).
 """
 from __future__ import annotations
 
@@ -242,11 +243,19 @@ class BeliefFlightField(FlightField):
     `outside="blocked"` where it leaves the grid (range_gt bounds every solid of a scene by grid_spec's construction, hence the
     default "free"), and with body.ground where it reaches z <= 0.  The drone is at its own nearest node, so update() calls
     that node flyable whatever the map says; `blocked_map` stays the pure kernel output.  `map_mode`: 0 auto, 1 the grid's
-    bits packed into LDS (refused where they do not fit), 2 the grid read from global memory.  GPU only."""
+    bits packed into LDS (refused where they do not fit), 2 the grid read from global memory.  GPU only.
+
+    `shortcut=True` adds the straight leg judged on the map: refresh() also keeps `map_i8` [N, G^3] int8, a snapshot of the map
+    (int8 rows copied, fp32 rows as their sign -- the buffer the map was written to may be reused before the env flies, and the
+    pilot's knowledge must not alias it), and `sweep` moves the sphere of radius `sweep_radius` = body.path_radius +
+    shortcut_margin along straight legs over it (a lattice node needs the inflated rho so that its edges are safe; a straight leg
+    needs only the body's own radius).  `sweeps` counts those launches.  With shortcut=False nothing is allocated or launched
+    that was not before."""
     belief = True
 
     def __init__(self, num_envs: int, lattice, body, range_gt: torch.Tensor, voxel_size: torch.Tensor, grid_size: int,
-                 unknown: str = "free", outside: str = "free", margin: float = 0.0, mode: int = 0, map_mode: int = 0, device="cuda:0"):
+                 unknown: str = "free", outside: str = "free", margin: float = 0.0, mode: int = 0, map_mode: int = 0, device="cuda:0",
+                 shortcut: bool = False, shortcut_margin: float = 0.0):
         import types
         device = torch.device(device)
         for name, val in (("unknown", unknown), ("outside", outside)):
@@ -257,6 +266,10 @@ class BeliefFlightField(FlightField):
         n, g = int(num_envs), int(grid_size)
         if not 1 <= g <= 128:
             raise ValueError(f"BeliefFlightField: grid_size must be in 1..128, got {grid_size}")
+        self.shortcut = bool(shortcut)
+        self.sweep_radius = float(body.path_radius) + float(shortcut_margin)
+        if not (np.isfinite(self.sweep_radius) and self.sweep_radius > 0.0):
+            raise ValueError(f"BeliefFlightField: the path radius plus shortcut_margin must be finite and > 0, got {self.sweep_radius}")
         if device.type != "cuda":
             raise _lib.GennbvHipError("BeliefFlightField runs on the GPU only (no CPU fallback)")
         lib = _lib.load()
@@ -274,16 +287,15 @@ class BeliefFlightField(FlightField):
         super().__init__(types.SimpleNamespace(device=device, num_envs=n), lattice, body, mode=mode, blocked=blocked)
         self.blocked_map = torch.full_like(self.blocked, -1)
         self.refreshes = 0  # map launches so far
+        self.sweeps = 0  # gnbv_sweep_tri launches so far
+        self.map_i8 = torch.zeros(n, g ** 3, dtype=torch.int8, device=device) if self.shortcut else None  # all unknown until refresh()
+        self.has_map = False  # a refresh() has filled the snapshot
 
     def refresh(self, tri: torch.Tensor) -> "BeliefFlightField":
         """gnbv_flight_blocked_tri on the current stream into `blocked_map`: tri [N, >= G^3] int8 or float32, unit element
         stride, any row stride (e.g. obs[:, state_dim:state_dim + grid_dim])."""
         n, g3 = self.num_envs, self.grid_size ** 3
-        _lib.require_cuda(tri)
-        if tri.dtype not in (torch.int8, torch.float32) or tri.dim() != 2 or tri.shape[0] != n or tri.shape[1] < g3 or tri.stride(1) != 1:
-            raise _lib.GennbvHipError(f"BeliefFlightField.refresh: tri must be int8 or float32 [{n}, >= {g3}] with unit element stride, "
-                                      f"got {tri.dtype} {tuple(tri.shape)} strides {tuple(tri.stride())}")
-        row = int(tri.stride(0)) if n > 1 else max(int(tri.stride(0)), g3)
+        row = self._check_tri(tri, "refresh")
         i8 = tri.dtype == torch.int8
         nx, ny, nz = self.lattice.dims
         _lib.check(self.lib.gnbv_flight_blocked_tri(tri.data_ptr() if i8 else None, row if i8 else 0, None if i8 else tri.data_ptr(),
@@ -292,7 +304,59 @@ class BeliefFlightField(FlightField):
                                                     int(self.outside_blocks), int(bool(self.body.ground)), self.blocked_map.data_ptr(),
                                                     self.map_mode, _lib.stream_ptr(self.device)), "gnbv_flight_blocked_tri")
         self.refreshes += 1
+        if self.shortcut:
+            self.map_i8.copy_(tri[:, :g3] if i8 else torch.sign(tri[:, :g3]))
+            self.has_map = True
         return self
+
+    def _check_tri(self, tri: torch.Tensor, what: str) -> int:
+        """The tensor checks of refresh() and sweep(); returns the row stride in elements."""
+        n, g3 = self.num_envs, self.grid_size ** 3
+        _lib.require_cuda(tri)
+        if tri.dtype not in (torch.int8, torch.float32) or tri.dim() != 2 or tri.shape[0] != n or tri.shape[1] < g3 or tri.stride(1) != 1:
+            raise _lib.GennbvHipError(f"BeliefFlightField.{what}: tri must be int8 or float32 [{n}, >= {g3}] with unit element stride, "
+                                      f"got {tri.dtype} {tuple(tri.shape)} strides {tuple(tri.stride())}")
+        return int(tri.stride(0)) if n > 1 else max(int(tri.stride(0)), g3)
+
+    def sweep(self, from_poses: torch.Tensor, to_poses: torch.Tensor, tri: Optional[torch.Tensor] = None, radius: Optional[float] = None,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One gnbv_sweep_tri launch on the current stream: uint8 [N,K], the code (1 MAP | 2 OUTSIDE | 4 GROUND) of the sphere of
+        `radius` (default `sweep_radius`) moved along the straight legs from from_poses [N, >= 3] (one start per env) or
+        [N, K, >= 3] to to_poses [N, K, >= 3] f32, judged on `tri` (refresh()'s forms) or, where tri is None, on the snapshot
+        `map_i8` of the last refresh -- with the field's unknown / outside flags, body.ground and map_mode.  0 = the map shows the
+        leg in the clear.  No host synchronisation."""
+        n = self.num_envs
+        if tri is None:
+            if not (self.shortcut and self.has_map):
+                raise _lib.GennbvHipError("BeliefFlightField.sweep: no map snapshot (shortcut=True and a refresh()) and no tri given")
+            tri = self.map_i8
+        row = self._check_tri(tri, "sweep")
+        r = self.sweep_radius if radius is None else float(radius)
+        if not (np.isfinite(r) and r > 0.0):
+            raise ValueError(f"BeliefFlightField.sweep: radius must be finite and > 0, got {radius}")
+        to_poses, k, to_row = self._targets(to_poses)
+        _lib.require_cuda(from_poses)
+        if from_poses.dtype != torch.float32 or from_poses.dim() not in (2, 3) or from_poses.shape[0] != n or from_poses.shape[-1] < 3 \
+                or (from_poses.dim() == 3 and from_poses.shape[1] != k):
+            raise _lib.GennbvHipError(f"BeliefFlightField.sweep: from_poses must be float32 [{n}, >= 3] or [{n}, {k}, >= 3], got "
+                                      f"{from_poses.dtype} {tuple(from_poses.shape)}")
+        if from_poses.stride(-1) != 1 or (n > 1 and from_poses.stride(0) < 3) or \
+                (from_poses.dim() == 3 and k > 1 and from_poses.stride(1) != 0 and from_poses.stride(1) < 3):
+            from_poses = from_poses.contiguous()
+        f_env = max(int(from_poses.stride(0)), 3)
+        f_item = 0 if from_poses.dim() == 2 or k == 1 else int(from_poses.stride(1))
+        if out is None:
+            out = torch.empty(n, k, dtype=torch.uint8, device=self.device)
+        _lib.require_cuda(out)
+        assert out.dtype == torch.uint8 and out.shape == (n, k) and out.is_contiguous()
+        i8 = tri.dtype == torch.int8
+        _lib.check(self.lib.gnbv_sweep_tri(tri.data_ptr() if i8 else None, row if i8 else 0, None if i8 else tri.data_ptr(), 0 if i8 else row,
+                                           self.grid_size, self.range_gt.data_ptr(), self.voxel_size.data_ptr(), n, from_poses.data_ptr(),
+                                           f_env, f_item, to_poses.data_ptr(), k, to_row, r, int(self.unknown_blocks),
+                                           int(self.outside_blocks), int(bool(self.body.ground)), out.data_ptr(), self.map_mode,
+                                           _lib.stream_ptr(self.device)), "gnbv_sweep_tri")
+        self.sweeps += 1
+        return out
 
     def update(self, poses: torch.Tensor) -> "BeliefFlightField":
         """blocked = blocked_map with the bit of each env's own nearest node cleared (the drone is there; an env with a

@@ -344,6 +344,33 @@ int gnbv_flight_blocked_tri(const int8_t *tri_i8 /*[N, >= G^3] or NULL*/, int64_
                             const double *lo /*[host] 3*/, const double *h /*[host] 3*/, double rho, int unknown_blocks,
                             int outside_blocks, int ground, uint32_t *blocked_out /*[N,ceil(M/32)]*/, int mode, void *stream);
 
+/* A straight flight judged on the scanned map (an additive entry point of ABI 5; csrc/sweepmap.hip): the sphere of radius R moved
+ * along N x K straight legs against each env's tri-class grid.  The grid forms, the signs (< 0 free, 0 unknown, > 0 occupied), the
+ * voxel order (x G + y) G + z and the voxel frame (o_a, v_a; voxel i of axis a spans [o_a + i v_a, o_a + (i + 1) v_a]) are those of
+ * gnbv_flight_blocked_tri; the item layout (from / to, the strides, xyz the first three floats of a row) is gnbv_sweep_sphere's.
+ * Item (e, j) is the segment a -> b, fp32 taken to fp64, x(s) = a + s (b - a).  code_out[e, j], one byte:
+ *   1 (MAP):     some voxel that is occupied, or unknown with unknown_blocks, is touched:
+ *                min over s in [0, 1] of sum_a g_a(s)^2 <= R^2, g_a(s) = max(lo_a - x_a(s), 0, x_a(s) - hi_a) -- the distance from the
+ *                segment to the closed box, evaluated in closed form in fp64 (the ends, the at most six breakpoints where a
+ *                coordinate crosses a face, each piece's vertex clamped to the piece).  A zero-length segment gives the ball test
+ *                of gnbv_flight_blocked_tri.
+ *   2 (OUTSIDE): outside_blocks and, on some axis, min(a_a, b_a) - R < o_a or max(a_a, b_a) + R > o_a + (double)G v_a.
+ *   4 (GROUND):  ground and min(a_z, b_z) - R <= 0.
+ * An item with a non-finite coordinate gets 0.  mode: 0 auto (1 where G <= gnbv_sweepmap_lds_max_grid(), else 2), 1 one bit per
+ * voxel packed into LDS per workgroup (hipErrorInvalidValue where the bits do not fit), 2 the grid read from global memory; the
+ * result is the same.  One launch, one writer per byte, no atomics, no workspace, no allocation, no host synchronisation; every
+ * loop is bounded by a function of G and compile-time constants whatever the device arrays hold.  hipErrorInvalidValue before any
+ * launch for: both or neither grid form, a NULL required pointer, n < 1, k < 1, N * k > 2^31 - 1, G outside 1..128, a grid row
+ * stride below G^3, to_row_stride or from_env_stride < 3, from_item_stride neither 0 nor >= 3, radius not finite or <= 0, a mode
+ * outside 0..2, mode 1 above its limit. */
+int gnbv_sweepmap_lds_max_grid(void); /* the largest G of mode 1: 109 */
+int gnbv_sweep_tri(const int8_t *tri_i8 /*[N, >= G^3] or NULL*/, int64_t tri_i8_row_stride /*bytes*/,
+                   const float *tri_f32 /*[N, >= G^3] or NULL*/, int64_t tri_f32_row_stride /*floats*/, int g,
+                   const float *range_gt /*[N,6]*/, const float *voxel_size /*[N,3]*/, int n, const float *from,
+                   int64_t from_env_stride /*floats*/, int64_t from_item_stride /*floats, 0 = broadcast*/, const float *to, int k,
+                   int64_t to_row_stride /*floats*/, double radius, int unknown_blocks, int outside_blocks, int ground,
+                   uint8_t *code_out /*[N,K]*/, int mode, void *stream);
+
 /* compute_reward (env_train_base.py:377-398), _reward_* / check_termination /
  * reset_idx (env_train_gennbv.py:377-457,535-556), update_extra_episode_info
  * (env_train_base.py:629-639). All pointers device, arrays [N] unless noted. [host struct] */

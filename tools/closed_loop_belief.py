@@ -9,10 +9,14 @@ steps, each env's first episode).  Rows:
   greedy / privileged        GreedyGainPolicy, flight=FlightField(mesh): contacts and routes from the ground-truth mesh
   map-greedy / optimistic    MapGreedyPolicy, flight=BeliefFlightField(unknown="free"): routes through what it has not seen
   map-greedy / conservative  MapGreedyPolicy, flight=BeliefFlightField(unknown="blocked"): routes through seen free space only
+  ... + shortcut             the two belief rows with shortcut=True: straight legs judged on the map (csrc/sweepmap.hip), in the env
+                             (straight to the farthest waypoint in the clear) and in the planner (a clear straight leg reaches)
 
 Columns: final coverage, episode length, metres flown (env.flight_length at the step that ends the episode), the share of
-flown steps that followed a route of the field (the others flew straight), the share of episodes ended by a path collision
-and by a pose collision, and for the belief rows the share of decisions in which every candidate was unreachable.
+flown steps that followed a route of the field (with the shortcut: flew at least one route node), the share flown fully
+straight (privileged: the straight flight was free; belief: no route node was flown), the share of episodes ended by a path
+collision and by a pose collision, for the belief rows the share of decisions in which every candidate was refused, and for
+the shortcut rows the mean number of waypoints a step's straight first leg skipped.  Reported, not asserted.
 """
 from __future__ import annotations
 
@@ -43,7 +47,8 @@ def run(policy, env, steps):
     belief = bool(getattr(env.flight, "belief", False))
     obs = env.reset()
     alive = torch.ones(n, dtype=torch.bool, device=DEV)
-    final, length, flown, routed, moved, stuck, decisions = (torch.zeros(n, device=DEV) for _ in range(7))
+    final, length, flown, routed, moved, stuck, decisions, straight, skipped = (torch.zeros(n, device=DEV) for _ in range(9))
+    shortcut = belief and bool(getattr(env.flight, "shortcut", False))
     code = torch.zeros(n, dtype=torch.uint8, device=DEV)
     for t in range(steps):
         act = policy(obs)[0]
@@ -54,8 +59,12 @@ def run(policy, env, steps):
         moved += alive.float()  # reset() set the first pose: every step of an env's first episode is flown
         if belief:
             routed += (alive & env.routed).float()
+            straight += (alive & ~env.routed).float()
         else:  # the privileged env flies straight where it can and the field's detour where it must
             routed += (alive & (env.path_code != 0) & ((env.collision_buf & (PATH | PATH_GROUND)) == 0)).float()
+            straight += (alive & (env.path_code == 0)).float()
+        if shortcut:
+            skipped += torch.where(alive, env.skipped, torch.zeros_like(env.skipped)).float()
         flown = torch.where(alive, env.flight_length, flown)
         ends = alive & done
         final = torch.where(ends, env.coverage_ratio, final)
@@ -69,11 +78,14 @@ def run(policy, env, steps):
     pose_hit = (code & 7) != 0
     path_hit = (code & (PATH | PATH_GROUND)) != 0
     out = {"final_coverage": float(final.mean()), "mean_length": float(length.mean()), "mean_flown_m": float(flown.mean()),
-           "routed_share": float(routed.sum() / moved.sum().clamp(min=1.0)), "ended_by_path_collision": float(path_hit.float().mean()),
+           "routed_share": float(routed.sum() / moved.sum().clamp(min=1.0)),
+           "straight_share": float(straight.sum() / moved.sum().clamp(min=1.0)), "ended_by_path_collision": float(path_hit.float().mean()),
            "ended_by_pose_collision": float(pose_hit.float().mean())}
     if belief:
         out["all_candidates_unreachable_share"] = float(stuck.sum() / decisions.sum().clamp(min=1.0))
         out["route_overflows"] = int(env.route_overflow)
+    if shortcut:
+        out["mean_skipped"] = float(skipped.sum() / moved.sum().clamp(min=1.0))
     return out
 
 
@@ -98,12 +110,14 @@ def main():
     blocked = mesh.flight_blocked(lattice, body)  # once per scene set
     res = {"envs": n, "grid": g, "steps": args.steps, "k": args.k, "stride": args.stride, "rows": []}
     for seed in (int(s) for s in args.seeds.split(",")):
-        for name in ("greedy / privileged", "map-greedy / optimistic", "map-greedy / conservative"):
+        for name in ("greedy / privileged", "map-greedy / optimistic", "map-greedy / conservative", "map-greedy / optimistic + shortcut",
+                     "map-greedy / conservative + shortcut"):
             if name.startswith("greedy"):
                 flight = FlightField(mesh, lattice, body, blocked=blocked)
             else:
                 flight = BeliefFlightField(n, lattice, body, scene.range_gt, scene.voxel_size, g,
-                                           unknown="free" if name.endswith("optimistic") else "blocked", device=DEV)
+                                           unknown="free" if "optimistic" in name else "blocked", device=DEV,
+                                           shortcut=name.endswith("shortcut"))
             env = ReplayFeedEnv(cfg, scene, RenderFeed(mesh, cfg), DEV, max_episode_length=args.steps, collision=body, flight=flight)
             pol = (GreedyGainPolicy if name.startswith("greedy") else MapGreedyPolicy)(env, k=args.k, weights=(1, 4), seed=seed)
             row = {"seed": seed, "row": name}
