@@ -20,6 +20,7 @@ _i64 = C.c_int64
 _f = C.c_float
 _d = C.c_double
 _sz = C.c_size_t
+_u32 = C.c_uint32
 
 # name -> (restype, argtypes): must list every symbol include/gennbv_hip.h declares
 SIGNATURES = {
@@ -61,7 +62,11 @@ SIGNATURES = {
     "gnbv_flight_field": (_i, [_p, _i, _i, _i, _i, _p, _p, _i64, _p, _p, _p, _p, _i, _p]),
     "gnbv_flight_query": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _i, _i64, _p, _p]),
     "gnbv_flight_path": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _i64, _p, _i, _p, _p]),
+    "gnbv_flight_field_w": (_i, [_p, _p, _u32, _i, _i, _i, _i, _p, _p, _i64, _p, _p, _p, _p, _i, _p]),
+    "gnbv_flight_path_w": (_i, [_p, _p, _u32, _i, _i, _i, _i, _p, _p, _p, _p, _i64, _p, _i, _p, _p]),
     "gnbv_flightmap_lds_max_grid": (_i, []),
+    "gnbv_flightmap_classify_lds_max_grid": (_i, []),
+    "gnbv_flight_classify_tri": (_i, [_p, _i64, _p, _i64, _i, _p, _p, _i, _i, _i, _i, _p, _p, _d, _i, _i, _p, _p, _i, _p]),
     "gnbv_flight_blocked_tri": (_i, [_p, _i64, _p, _i64, _i, _p, _p, _i, _i, _i, _i, _p, _p, _d, _i, _i, _i, _p, _i, _p]),
     "gnbv_sweepmap_lds_max_grid": (_i, []),
     "gnbv_sweep_tri": (_i, [_p, _i64, _p, _i64, _i, _p, _p, _i, _p, _i64, _i64, _p, _i, _i64, _d, _i, _i, _i, _p, _i, _p]),

@@ -21,8 +21,14 @@
 //     of sweep s, cleared by lane 0 after the barrier of sweep s + 1 for sweep s + 3), so the whole workgroup leaves on
 //     the same sweep; the sweep count is capped at M (Bellman-Ford needs fewer), a capped env sets status_out[e] = 1.
 //     At the end kFree becomes kInf.
+//     kW (gnbv_flight_field_w): entering a node whose `costly` bit is set costs penalty_mm more, whichever neighbour it is entered
+//       from, so the bit belongs to the node relaxed, not to the 26 neighbours read: d[c] = min(d[c], min_n(d[n] + cost) + pen(c)).
+//       In LDS a lane owns at most ceil(40956 / 1024) = 40 nodes and keeps their bits in one 64-bit register for all sweeps; in
+//       global memory it reads the word of the node it relaxes.  The argument above is untouched: every stored value is still
+//       the cost of a real route, values only fall, and M (max cost + penalty) < kFree keeps every sum inside 32 bits.
 //   k_flight_query   one lane per (env, target): the field at the target's nearest node.
-//   k_flight_path    one lane per env: the walk from the target's node down the field to the source.
+//   k_flight_path<kW>  one lane per env: the walk from the target's node down the field to the source (kW: the penalty of the
+//     node walked from is part of the equation).
 #include <cmath>
 
 #include "common.h"
@@ -62,10 +68,11 @@ __device__ __forceinline__ int nearest_node(const Lattice &lat, const float *__r
 __device__ __forceinline__ uint32_t ld(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 __device__ __forceinline__ void st(uint32_t *p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 
-template <bool kLds>
+template <bool kLds, bool kW>
 __global__ __launch_bounds__(kFieldLanes) void k_flight_field(const uint32_t *__restrict__ blocked, int words, Lattice lat,
                                                               const float *__restrict__ poses, int64_t pose_stride,
-                                                              uint32_t *__restrict__ field_out, int32_t *__restrict__ status_out)
+                                                              uint32_t *__restrict__ field_out, int32_t *__restrict__ status_out,
+                                                              const uint32_t *__restrict__ costly, uint32_t penalty)
 {
     extern __shared__ __attribute__((aligned(16))) char flight_lds[];
     int *flags = reinterpret_cast<int *>(flight_lds);
@@ -90,11 +97,19 @@ __global__ __launch_bounds__(kFieldLanes) void k_flight_field(const uint32_t *__
     // ---- sweeps
     const int per_lane = (m + kFieldLanes - 1) / kFieldLanes;
     const int plane = nx * ny;
+    const uint32_t *pen_bits = kW ? costly + (size_t)e * words : nullptr;
+    unsigned long long mine = 0ull;  // kW && kLds: bit q = the costly bit of this lane's node q * 1024 + tid (per_lane <= 40)
+    if (kW && kLds)
+        for (int q = 0; q < per_lane; ++q) {
+            const int c = q * kFieldLanes + tid;
+            if (c < m) mine |= (unsigned long long)((pen_bits[c >> 5] >> (c & 31)) & 1u) << q;
+        }
     int sweep = 0, more = 1;
     while (more != 0 && sweep < m) {  // `more` and `sweep` are the same in every lane
         bool changed = false;
         for (int q = 0; q < per_lane; ++q) {  // chunk q is about one z slab: up the lattice in even sweeps, down in odd ones
-            const int c = ((sweep & 1) ? per_lane - 1 - q : q) * kFieldLanes + tid;
+            const int chunk = (sweep & 1) ? per_lane - 1 - q : q;
+            const int c = chunk * kFieldLanes + tid;
             if (c >= m) continue;
             const int i = c % nx, j = (c / nx) % ny, k = c / plane;
             const uint32_t own = ld(d + c);
@@ -110,13 +125,15 @@ __global__ __launch_bounds__(kFieldLanes) void k_flight_field(const uint32_t *__
                 const bool in = okx[dx + 1] && oky[dy + 1] && okz[dz + 1];
                 dn[q3] = ld(d + (in ? c + dz * plane + dy * nx + dx : c));
             }
+            uint32_t pen = 0u;
+            if (kW) pen = ((kLds ? (uint32_t)(mine >> chunk) : pen_bits[c >> 5] >> (c & 31)) & 1u) ? penalty : 0u;
             uint32_t best = own;
 #pragma unroll
             for (int q3 = 0; q3 < 27; ++q3) {
                 const int dx = q3 % 3 - 1, dy = (q3 / 3) % 3 - 1, dz = q3 / 9 - 1;
                 if (q3 == 13) continue;
                 const bool in = okx[dx + 1] && oky[dy + 1] && okz[dz + 1];
-                const uint32_t cand = dn[q3] + lat.cost[(dx != 0) | ((dy != 0) << 1) | ((dz != 0) << 2)];
+                const uint32_t cand = dn[q3] + lat.cost[(dx != 0) | ((dy != 0) << 1) | ((dz != 0) << 2)] + pen;
                 best = (in && dn[q3] < kFree && cand < best) ? cand : best;  // (>= kFree: blocked or not reached)
             }
             if (best < own) {
@@ -151,9 +168,11 @@ __global__ __launch_bounds__(256) void k_flight_query(const uint32_t *__restrict
     cost_out[item] = node < 0 ? kInf : field[(size_t)e * m + node];
 }
 
+template <bool kW>
 __global__ __launch_bounds__(kWave) void k_flight_path(const uint32_t *__restrict__ field, Lattice lat, const float *__restrict__ targets, int n,
                                                        int64_t row_stride, int32_t *__restrict__ nodes_out, int max_len,
-                                                       int32_t *__restrict__ len_out)
+                                                       int32_t *__restrict__ len_out, const uint32_t *__restrict__ costly, int words,
+                                                       uint32_t penalty)
 {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= n) return;
@@ -174,6 +193,8 @@ __global__ __launch_bounds__(kWave) void k_flight_path(const uint32_t *__restric
         const int i = cur % nx, j = (cur / nx) % ny, k = cur / plane;
         int next = -1;
         uint32_t dnext = 0;
+        uint32_t pen = 0u;  // of the node walked from, once per node
+        if (kW) pen = ((costly[(size_t)e * words + (cur >> 5)] >> (cur & 31)) & 1u) ? penalty : 0u;
         for (int dz = -1; dz <= 1 && next < 0; ++dz) {
             if ((unsigned)(k + dz) >= (unsigned)nz) continue;
             for (int dy = -1; dy <= 1 && next < 0; ++dy) {
@@ -182,7 +203,8 @@ __global__ __launch_bounds__(kWave) void k_flight_path(const uint32_t *__restric
                     if ((unsigned)(i + dx) >= (unsigned)nx || (dx | dy | dz) == 0) continue;
                     const int nb = cur + dz * plane + dy * nx + dx;
                     const uint32_t dn = d[nb];
-                    if (dn < dc && dn + lat.cost[(dx != 0) | ((dy != 0) << 1) | ((dz != 0) << 2)] == dc) {
+                    const uint32_t step = lat.cost[(dx != 0) | ((dy != 0) << 1) | ((dz != 0) << 2)];
+                    if (dn < dc && (kW ? (uint64_t)dn + step + pen == (uint64_t)dc : dn + step == dc)) {
                         next = nb;
                         dnext = dn;
                         break;
@@ -201,8 +223,8 @@ __global__ __launch_bounds__(kWave) void k_flight_path(const uint32_t *__restric
 }
 
 // nx, ny, nz in 1..1024, a finite lattice with h > 0 on every axis that has more than one node, positive edge costs whose sum
-// over a route through every node stays below kFree
-bool make_lattice(int nx, int ny, int nz, const uint32_t *cost, const double *lo, const double *h, Lattice *out)
+// over a route through every node -- with `penalty` added at every node entered -- stays below kFree
+bool make_lattice(int nx, int ny, int nz, const uint32_t *cost, const double *lo, const double *h, Lattice *out, uint32_t penalty = 0)
 {
     if (cost == nullptr || lo == nullptr || h == nullptr) return false;
     const int n[3] = {nx, ny, nz};
@@ -222,11 +244,40 @@ bool make_lattice(int nx, int ny, int nz, const uint32_t *cost, const double *lo
         out->cost[b] = cost[b];
     }
     const uint64_t m = (uint64_t)nx * ny * nz;
-    if (m > 0x7fffffffull || m * (uint64_t)cmax >= (uint64_t)kFree) return false;
+    if (m > 0x7fffffffull || m * ((uint64_t)cmax + penalty) >= (uint64_t)kFree) return false;
     out->nx = nx;
     out->ny = ny;
     out->nz = nz;
     return true;
+}
+
+template <bool kW>
+int launch_field(const uint32_t *blocked, int n, int nx, int ny, int nz, const uint32_t *cost, const float *poses, int64_t poses_row_stride,
+                 const double *lo, const double *h, uint32_t *field_out, int32_t *status_out, const uint32_t *costly, uint32_t penalty,
+                 int mode, void *stream)
+{
+    GNBV_CHECK_ARG(blocked != nullptr && poses != nullptr && field_out != nullptr && status_out != nullptr && (!kW || costly != nullptr));
+    GNBV_CHECK_ARG(n >= 1 && poses_row_stride >= 3 && mode >= 0 && mode <= 2);
+    Lattice lat;
+    GNBV_CHECK_ARG(make_lattice(nx, ny, nz, cost, lo, h, &lat, penalty));
+    const int m = nx * ny * nz, words = (m + 31) / 32;
+    const bool fits = m <= kLdsMaxNodes;
+    GNBV_CHECK_ARG(mode != 1 || fits);
+    if (mode == 1 || (mode == 0 && fits)) {
+        const size_t lds = (size_t)kLdsHeader + 4 * (size_t)m;
+        static size_t lds_allowed = 64 * 1024;  // what a launch may ask for without the attribute (one per instantiation)
+        if (lds > lds_allowed) {
+            const hipError_t err = hipFuncSetAttribute((const void *)k_flight_field<true, kW>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
+            if (err != hipSuccess) return (int)err;
+            lds_allowed = kLdsBytes;
+        }
+        hipLaunchKernelGGL((k_flight_field<true, kW>), dim3(n), dim3(kFieldLanes), lds, gnbv_stream(stream), blocked, words, lat, poses,
+                           poses_row_stride, field_out, status_out, costly, penalty);
+    } else {
+        hipLaunchKernelGGL((k_flight_field<false, kW>), dim3(n), dim3(kFieldLanes), kLdsHeader, gnbv_stream(stream), blocked, words, lat, poses,
+                           poses_row_stride, field_out, status_out, costly, penalty);
+    }
+    return gnbv_launch_status();
 }
 
 }  // namespace
@@ -237,28 +288,15 @@ GNBV_API int gnbv_flight_field(const uint32_t *blocked, int n, int nx, int ny, i
                                int64_t poses_row_stride, const double *lo, const double *h, uint32_t *field_out, int32_t *status_out,
                                int mode, void *stream)
 {
-    GNBV_CHECK_ARG(blocked != nullptr && poses != nullptr && field_out != nullptr && status_out != nullptr);
-    GNBV_CHECK_ARG(n >= 1 && poses_row_stride >= 3 && mode >= 0 && mode <= 2);
-    Lattice lat;
-    GNBV_CHECK_ARG(make_lattice(nx, ny, nz, cost, lo, h, &lat));
-    const int m = nx * ny * nz, words = (m + 31) / 32;
-    const bool fits = m <= kLdsMaxNodes;
-    GNBV_CHECK_ARG(mode != 1 || fits);
-    if (mode == 1 || (mode == 0 && fits)) {
-        const size_t lds = (size_t)kLdsHeader + 4 * (size_t)m;
-        static size_t lds_allowed = 64 * 1024;  // what a launch may ask for without the attribute
-        if (lds > lds_allowed) {
-            const hipError_t err = hipFuncSetAttribute((const void *)k_flight_field<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-            if (err != hipSuccess) return (int)err;
-            lds_allowed = kLdsBytes;
-        }
-        hipLaunchKernelGGL(k_flight_field<true>, dim3(n), dim3(kFieldLanes), lds, gnbv_stream(stream), blocked, words, lat, poses,
-                           poses_row_stride, field_out, status_out);
-    } else {
-        hipLaunchKernelGGL(k_flight_field<false>, dim3(n), dim3(kFieldLanes), kLdsHeader, gnbv_stream(stream), blocked, words, lat, poses,
-                           poses_row_stride, field_out, status_out);
-    }
-    return gnbv_launch_status();
+    return launch_field<false>(blocked, n, nx, ny, nz, cost, poses, poses_row_stride, lo, h, field_out, status_out, nullptr, 0u, mode, stream);
+}
+
+GNBV_API int gnbv_flight_field_w(const uint32_t *blocked, const uint32_t *costly, uint32_t penalty_mm, int n, int nx, int ny, int nz,
+                                 const uint32_t *cost, const float *poses, int64_t poses_row_stride, const double *lo, const double *h,
+                                 uint32_t *field_out, int32_t *status_out, int mode, void *stream)
+{
+    return launch_field<true>(blocked, n, nx, ny, nz, cost, poses, poses_row_stride, lo, h, field_out, status_out, costly, penalty_mm, mode,
+                              stream);
 }
 
 GNBV_API int gnbv_flight_query(const uint32_t *field, int n, int nx, int ny, int nz, const double *lo, const double *h, const float *targets,
@@ -283,7 +321,20 @@ GNBV_API int gnbv_flight_path(const uint32_t *field, int n, int nx, int ny, int 
     GNBV_CHECK_ARG(n >= 1 && max_len >= 1 && targets_row_stride >= 3);
     Lattice lat;
     GNBV_CHECK_ARG(make_lattice(nx, ny, nz, cost, lo, h, &lat));
-    hipLaunchKernelGGL(k_flight_path, dim3((n + kWave - 1) / kWave), dim3(kWave), 0, gnbv_stream(stream), field, lat, targets, n,
-                       targets_row_stride, nodes_out, max_len, len_out);
+    hipLaunchKernelGGL(k_flight_path<false>, dim3((n + kWave - 1) / kWave), dim3(kWave), 0, gnbv_stream(stream), field, lat, targets, n,
+                       targets_row_stride, nodes_out, max_len, len_out, nullptr, 0, 0u);
+    return gnbv_launch_status();
+}
+
+GNBV_API int gnbv_flight_path_w(const uint32_t *field, const uint32_t *costly, uint32_t penalty_mm, int n, int nx, int ny, int nz,
+                                const uint32_t *cost, const double *lo, const double *h, const float *targets, int64_t targets_row_stride,
+                                int32_t *nodes_out, int max_len, int32_t *len_out, void *stream)
+{
+    GNBV_CHECK_ARG(field != nullptr && costly != nullptr && targets != nullptr && nodes_out != nullptr && len_out != nullptr);
+    GNBV_CHECK_ARG(n >= 1 && max_len >= 1 && targets_row_stride >= 3);
+    Lattice lat;
+    GNBV_CHECK_ARG(make_lattice(nx, ny, nz, cost, lo, h, &lat, penalty_mm));
+    hipLaunchKernelGGL(k_flight_path<true>, dim3((n + kWave - 1) / kWave), dim3(kWave), 0, gnbv_stream(stream), field, lat, targets, n,
+                       targets_row_stride, nodes_out, max_len, len_out, costly, (nx * ny * nz + 31) / 32, penalty_mm);
     return gnbv_launch_status();
 }

@@ -1,4 +1,5 @@
-// flightmap.hip -- the free set of the flight lattice from the map the agent has scanned so far (gnbv_flight_blocked_tri).
+// flightmap.hip -- the free set of the flight lattice from the map the agent has scanned so far (gnbv_flight_blocked_tri,
+// gnbv_flight_classify_tri).
 //
 // flight.hip routes over blocked bits; MeshScene.flight_blocked takes them from the ground-truth mesh.  This file takes them from
 // an env's own tri-class grid (< 0 free, 0 unknown, > 0 occupied: gnbv_view_gain's signs), once per env step: node c of env e is
@@ -18,6 +19,12 @@
 //       G^2 / 32 apart -- at G = 64 all on one bank -- so the words are swizzled (map_bits.h has the pack, shared with sweepmap.hip).
 //     !kLds (mode 2): the same decisions with the voxels read from global memory, for grids whose bits do not fit (up to 128^3).
 //     kF32: the grid is the fp32 slice of an observation row, else int8 rows.
+//   k_flight_classify_tri<kLds, kF32>   the same launch shape with two outputs (gnbv_flight_classify_tri): "blocked" as with
+//     unknown_blocks = 0, and "costly" = not blocked, but the ball touches an unknown voxel -- what two launches of the kernel above
+//     (unknown_blocks = 0 and 1) and an AND-NOT would give, from one pass over the window.  The walk still ends at the first touched
+//     occupied voxel; a touched unknown voxel only sets a flag, and from then on unknown voxels are skipped.
+//     kLds: two bit planes, occupied then unknown (map_pack_planes: every voxel read once), G^3 / 4 bytes, so the limit is lower
+//       (map_planes_max_grid, 86); a word of the window is occ | unk until the flag is set, occ alone afterwards.
 #include <algorithm>
 #include <cmath>
 
@@ -47,29 +54,46 @@ __device__ __forceinline__ double gap2(double o, double v, int i, double p)
     return gap * gap;
 }
 
+// the ball of node c: its centre, its per-axis voxel window [i0, i1] (clamped to the grid in fp64 before conversion), whether it
+// leaves the grid and whether the window is empty
+struct NodeWindow {
+    double p[3];
+    int i0[3], i1[3];
+    bool outside, empty;
+};
+
+__device__ __forceinline__ NodeWindow node_window(const MapArgs &a, int c, const double *o, const double *v)
+{
+    const int g = a.g;
+    const int idx[3] = {c % a.nx, (c / a.nx) % a.ny, c / (a.nx * a.ny)};
+    const double top = (double)(g - 1);
+    NodeWindow n;
+    n.outside = false;
+    n.empty = false;
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax) {
+        n.p[ax] = a.lo[ax] + a.h[ax] * (double)idx[ax];
+        const double pm = n.p[ax] - a.rho, pp = n.p[ax] + a.rho;
+        const double f0 = floor((pm - o[ax]) / v[ax]), f1 = floor((pp - o[ax]) / v[ax]);
+        n.empty = n.empty || f1 < 0.0 || f0 > top;
+        n.i0[ax] = (int)fmin(fmax(f0, 0.0), top);  // (a NaN clamps to 0: the loops stay inside the grid)
+        n.i1[ax] = (int)fmin(fmax(f1, 0.0), top);
+        n.outside = n.outside || pm < o[ax] || pp > o[ax] + (double)g * v[ax];
+    }
+    return n;
+}
+
 template <bool kLds, bool kF32>
 __device__ __forceinline__ bool node_blocked(const MapArgs &a, int c, const double *o, const double *v, const void *__restrict__ tri,
                                              const uint32_t *bits)
 {
     const int g = a.g;
-    const int idx[3] = {c % a.nx, (c / a.nx) % a.ny, c / (a.nx * a.ny)};
-    const double top = (double)(g - 1);
-    double p[3];
-    int i0[3], i1[3];
-    bool outside = false, empty = false;
-#pragma unroll
-    for (int ax = 0; ax < 3; ++ax) {
-        p[ax] = a.lo[ax] + a.h[ax] * (double)idx[ax];
-        const double pm = p[ax] - a.rho, pp = p[ax] + a.rho;
-        const double f0 = floor((pm - o[ax]) / v[ax]), f1 = floor((pp - o[ax]) / v[ax]);
-        empty = empty || f1 < 0.0 || f0 > top;
-        i0[ax] = (int)fmin(fmax(f0, 0.0), top);  // (a NaN clamps to 0: the loops stay inside the grid)
-        i1[ax] = (int)fmin(fmax(f1, 0.0), top);
-        outside = outside || pm < o[ax] || pp > o[ax] + (double)g * v[ax];
-    }
-    if (a.outside_blocks && outside) return true;
+    const NodeWindow n = node_window(a, c, o, v);
+    const double *p = n.p;
+    const int *i0 = n.i0, *i1 = n.i1;
+    if (a.outside_blocks && n.outside) return true;
     if (a.ground && p[2] - a.rho <= 0.0) return true;
-    if (empty) return false;
+    if (n.empty) return false;
     const bool unk = a.unknown_blocks != 0;
     for (int x = i0[0]; x <= i1[0]; ++x) {
         const double gx2 = gap2(o[0], v[0], x, p[0]);
@@ -99,6 +123,60 @@ __device__ __forceinline__ bool node_blocked(const MapArgs &a, int c, const doub
         }
     }
     return false;
+}
+
+// node_blocked with unknown space told apart (gnbv_flight_classify_tri): kBlocked where the ball touches an occupied voxel (or the
+// outside / the ground, by flag) -- the walk ends there as above -- else kCostly where it touches an unknown one (a flag; the walk
+// goes on, looking for occupied voxels only), else kClear.  kLds: the two planes of map_pack_planes.
+enum { kClear = 0, kBlocked = 1, kCostly = 2 };
+
+template <bool kLds, bool kF32>
+__device__ __forceinline__ int node_class(const MapArgs &a, int c, const double *o, const double *v, const void *__restrict__ tri,
+                                          const uint32_t *occ, const uint32_t *unk)
+{
+    const int g = a.g;
+    const NodeWindow n = node_window(a, c, o, v);
+    const double *p = n.p;
+    const int *i0 = n.i0, *i1 = n.i1;
+    if (a.outside_blocks && n.outside) return kBlocked;
+    if (a.ground && p[2] - a.rho <= 0.0) return kBlocked;
+    if (n.empty) return kClear;
+    bool costly = false;
+    for (int x = i0[0]; x <= i1[0]; ++x) {
+        const double gx2 = gap2(o[0], v[0], x, p[0]);
+        if (gx2 > a.rho2) continue;
+        for (int y = i0[1]; y <= i1[1]; ++y) {
+            const double s = gx2 + gap2(o[1], v[1], y, p[1]);
+            if (s > a.rho2) continue;
+            const int base = (x * g + y) * g;
+            if (kLds) {
+                const int b0 = base + i0[2], b1 = base + i1[2];
+                for (int w = b0 >> 5; w <= (b1 >> 5); ++w) {
+                    const int first = max(b0, w << 5), last = min(b1, (w << 5) + 31);
+                    const uint32_t span = (0xFFFFFFFFu >> (31 - (last - first))) << (first & 31);
+                    const int at = map_swizzle(w, a.shift);
+                    const uint32_t wo = occ[at] & span;
+                    const uint32_t word = costly ? wo : (wo | (unk[at] & span));  // (once costly, unknown voxels decide nothing)
+                    if (word == 0u) continue;
+                    for (int b = first; b <= last; ++b) {
+                        if (((word >> (b & 31)) & 1u) == 0u) continue;
+                        if (s + gap2(o[2], v[2], b - base, p[2]) > a.rho2) continue;
+                        if ((wo >> (b & 31)) & 1u) return kBlocked;
+                        costly = true;
+                    }
+                }
+            } else {
+                for (int z = i0[2]; z <= i1[2]; ++z) {
+                    const int cls = voxel_class<kF32>(tri, base + z);
+                    if (cls < 0 || (cls == 0 && costly)) continue;
+                    if (s + gap2(o[2], v[2], z, p[2]) > a.rho2) continue;
+                    if (cls > 0) return kBlocked;
+                    costly = true;
+                }
+            }
+        }
+    }
+    return costly ? kCostly : kClear;
 }
 
 template <bool kLds, bool kF32>
@@ -156,23 +234,80 @@ int launch_map(const void *tri, int64_t row_bytes, const float *range_gt, const 
     return gnbv_launch_status();
 }
 
-}  // namespace
+// k_flight_blocked_tri with two outputs: the ballot of kBlocked (padding set) and the ballot of kCostly (padding clear)
+template <bool kLds, bool kF32>
+__global__ __launch_bounds__(kMapLanes) void k_flight_classify_tri(const void *__restrict__ tri_base, int64_t row_bytes,
+                                                                   const float *__restrict__ range_gt, const float *__restrict__ voxel_size,
+                                                                   MapArgs a, int plane_words, uint32_t *__restrict__ blocked_out,
+                                                                   uint32_t *__restrict__ costly_out)
+{
+    extern __shared__ __attribute__((aligned(16))) char map_lds[];
+    uint32_t *occ = reinterpret_cast<uint32_t *>(map_lds), *unk = occ + plane_words;
+    const int e = blockIdx.x / a.chunks, chunk = blockIdx.x - e * a.chunks;
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    const void *tri = static_cast<const char *>(tri_base) + (size_t)e * row_bytes;
 
-GNBV_API int gnbv_flightmap_lds_max_grid(void) { return map_lds_max_grid(); }
+    if (kLds) {
+        map_pack_planes<kF32, kMapWaves>(tri, a.g, a.shift, occ, unk);
+        __syncthreads();
+    }
 
-GNBV_API int gnbv_flight_blocked_tri(const int8_t *tri_i8, int64_t tri_i8_row_stride, const float *tri_f32, int64_t tri_f32_row_stride,
-                                     int g, const float *range_gt, const float *voxel_size, int n, int nx, int ny, int nz, const double *lo,
-                                     const double *h, double rho, int unknown_blocks, int outside_blocks, int ground,
-                                     uint32_t *blocked_out, int mode, void *stream)
+    double o[3], v[3];
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax) {
+        const float vf = voxel_size[e * 3 + ax];
+        o[ax] = (double)__fsub_rn(range_gt[e * 6 + 2 * ax + 1], __fmul_rn(0.5f, vf));
+        v[ax] = (double)vf;
+    }
+
+    uint32_t *out_b = blocked_out + (size_t)e * a.words, *out_c = costly_out + (size_t)e * a.words;
+    for (int t = wave; t < a.chunk_waves; t += kMapWaves) {
+        const int c0 = (chunk * a.chunk_waves + t) * kWave, c = c0 + lane;
+        int cls = kBlocked;  // padding
+        if (c < a.m) cls = node_class<kLds, kF32>(a, c, o, v, tri, occ, unk);
+        const unsigned long long mb = __ballot(cls == kBlocked), mc = __ballot(cls == kCostly);
+        const int w = c0 >> 5;
+        if (lane == 0 && w < a.words) {
+            out_b[w] = (uint32_t)mb;
+            out_c[w] = (uint32_t)mc;
+        }
+        if (lane == 0 && w + 1 < a.words) {
+            out_b[w + 1] = (uint32_t)(mb >> 32);
+            out_c[w + 1] = (uint32_t)(mc >> 32);
+        }
+    }
+}
+
+template <bool kLds, bool kF32>
+int launch_classify(const void *tri, int64_t row_bytes, const float *range_gt, const float *voxel_size, const MapArgs &a, int n, size_t lds,
+                    uint32_t *blocked_out, uint32_t *costly_out, hipStream_t stream)
+{
+    if (kLds && lds > 64 * 1024) {  // what a launch may ask for without the attribute
+        static bool raised = false;
+        if (!raised) {
+            const hipError_t err = hipFuncSetAttribute((const void *)k_flight_classify_tri<kLds, kF32>,
+                                                       hipFuncAttributeMaxDynamicSharedMemorySize, kMapLdsBytes);
+            if (err != hipSuccess) return (int)err;
+            raised = true;
+        }
+    }
+    hipLaunchKernelGGL((k_flight_classify_tri<kLds, kF32>), dim3((unsigned)(n * a.chunks)), dim3(kMapLanes), lds, stream, tri, row_bytes,
+                       range_gt, voxel_size, a, (int)(lds / 8), blocked_out, costly_out);
+    return gnbv_launch_status();
+}
+
+// the argument checks and the launch shape shared by the two entry points; `max_grid` the LDS limit of the caller's mode 1
+int make_map_args(const void *tri_i8, int64_t tri_i8_row_stride, const void *tri_f32, int64_t tri_f32_row_stride, int g, const float *range_gt,
+                  const float *voxel_size, int n, int nx, int ny, int nz, const double *lo, const double *h, double rho, int unknown_blocks,
+                  int outside_blocks, int ground, const void *out, int mode, int max_grid, MapArgs *args, bool *use_lds)
 {
     GNBV_CHECK_ARG((tri_i8 != nullptr) != (tri_f32 != nullptr));
-    GNBV_CHECK_ARG(range_gt != nullptr && voxel_size != nullptr && blocked_out != nullptr && lo != nullptr && h != nullptr);
+    GNBV_CHECK_ARG(range_gt != nullptr && voxel_size != nullptr && out != nullptr && lo != nullptr && h != nullptr);
     GNBV_CHECK_ARG(n >= 1 && g >= 1 && g <= kMapMaxGrid && mode >= 0 && mode <= 2);
     GNBV_CHECK_ARG(std::isfinite(rho) && rho > 0.0);
     const int64_t g3 = (int64_t)g * g * g;
-    const bool f32 = tri_f32 != nullptr;
-    GNBV_CHECK_ARG((f32 ? tri_f32_row_stride : tri_i8_row_stride) >= g3);
-    MapArgs a;
+    GNBV_CHECK_ARG((tri_f32 != nullptr ? tri_f32_row_stride : tri_i8_row_stride) >= g3);
+    MapArgs &a = *args;
     const int dims[3] = {nx, ny, nz};
     for (int ax = 0; ax < 3; ++ax) {
         GNBV_CHECK_ARG(dims[ax] >= 1 && dims[ax] <= 1024 && std::isfinite(lo[ax]) && std::isfinite(h[ax]));
@@ -181,7 +316,7 @@ GNBV_API int gnbv_flight_blocked_tri(const int8_t *tri_i8, int64_t tri_i8_row_st
         a.h[ax] = h[ax];
     }
     const int64_t m = (int64_t)nx * ny * nz;
-    const bool fits = g <= map_lds_max_grid();
+    const bool fits = g <= max_grid;
     GNBV_CHECK_ARG(mode != 1 || fits);
     const bool lds = mode == 1 || (mode == 0 && fits);
     a.g = g;
@@ -204,6 +339,25 @@ GNBV_API int gnbv_flight_blocked_tri(const int8_t *tri_i8, int64_t tri_i8_row_st
     a.ground = ground != 0;
     a.rho = rho;
     a.rho2 = rho * rho;
+    *use_lds = lds;
+    return 0;
+}
+
+}  // namespace
+
+GNBV_API int gnbv_flightmap_lds_max_grid(void) { return map_lds_max_grid(); }
+
+GNBV_API int gnbv_flight_blocked_tri(const int8_t *tri_i8, int64_t tri_i8_row_stride, const float *tri_f32, int64_t tri_f32_row_stride,
+                                     int g, const float *range_gt, const float *voxel_size, int n, int nx, int ny, int nz, const double *lo,
+                                     const double *h, double rho, int unknown_blocks, int outside_blocks, int ground,
+                                     uint32_t *blocked_out, int mode, void *stream)
+{
+    MapArgs a;
+    bool lds;
+    const int bad = make_map_args(tri_i8, tri_i8_row_stride, tri_f32, tri_f32_row_stride, g, range_gt, voxel_size, n, nx, ny, nz, lo, h, rho,
+                                  unknown_blocks, outside_blocks, ground, blocked_out, mode, map_lds_max_grid(), &a, &lds);
+    if (bad != 0) return bad;
+    const bool f32 = tri_f32 != nullptr;
     const void *tri = f32 ? static_cast<const void *>(tri_f32) : static_cast<const void *>(tri_i8);
     const int64_t row_bytes = f32 ? 4 * tri_f32_row_stride : tri_i8_row_stride;
     const hipStream_t s = gnbv_stream(stream);
@@ -214,4 +368,30 @@ GNBV_API int gnbv_flight_blocked_tri(const int8_t *tri_i8, int64_t tri_i8_row_st
     }
     return f32 ? launch_map<false, true>(tri, row_bytes, range_gt, voxel_size, a, n, 0, blocked_out, s)
                : launch_map<false, false>(tri, row_bytes, range_gt, voxel_size, a, n, 0, blocked_out, s);
+}
+
+GNBV_API int gnbv_flightmap_classify_lds_max_grid(void) { return map_planes_max_grid(); }
+
+GNBV_API int gnbv_flight_classify_tri(const int8_t *tri_i8, int64_t tri_i8_row_stride, const float *tri_f32, int64_t tri_f32_row_stride,
+                                      int g, const float *range_gt, const float *voxel_size, int n, int nx, int ny, int nz, const double *lo,
+                                      const double *h, double rho, int outside_blocks, int ground, uint32_t *blocked_out,
+                                      uint32_t *costly_out, int mode, void *stream)
+{
+    GNBV_CHECK_ARG(costly_out != nullptr);
+    MapArgs a;
+    bool lds;
+    const int bad = make_map_args(tri_i8, tri_i8_row_stride, tri_f32, tri_f32_row_stride, g, range_gt, voxel_size, n, nx, ny, nz, lo, h, rho,
+                                  0, outside_blocks, ground, blocked_out, mode, map_planes_max_grid(), &a, &lds);
+    if (bad != 0) return bad;
+    const bool f32 = tri_f32 != nullptr;
+    const void *tri = f32 ? static_cast<const void *>(tri_f32) : static_cast<const void *>(tri_i8);
+    const int64_t row_bytes = f32 ? 4 * tri_f32_row_stride : tri_i8_row_stride;
+    const hipStream_t s = gnbv_stream(stream);
+    if (lds) {
+        const size_t bytes = 2 * map_lds_bytes(g);
+        return f32 ? launch_classify<true, true>(tri, row_bytes, range_gt, voxel_size, a, n, bytes, blocked_out, costly_out, s)
+                   : launch_classify<true, false>(tri, row_bytes, range_gt, voxel_size, a, n, bytes, blocked_out, costly_out, s);
+    }
+    return f32 ? launch_classify<false, true>(tri, row_bytes, range_gt, voxel_size, a, n, 0, blocked_out, costly_out, s)
+               : launch_classify<false, false>(tri, row_bytes, range_gt, voxel_size, a, n, 0, blocked_out, costly_out, s);
 }

@@ -49,6 +49,11 @@ snapshot of the map it had): it flies straight from the previous pose to the far
 included -- that the map shows in the clear, and the rest of the route from there.  The flown legs alone go to the truth,
 `flight_length` adds their Euclidean lengths, `routed` is true where a route node was flown, and `skipped` [N] int64 is the number
 of waypoints the straight first leg passed over (0: the route as it was; the route's node count: straight to the new pose).
+With a field that puts a price on unknown space (`flight.costly_map`, BeliefFlightField(unknown="costly")) the route is the
+penalised field's; `flight_length` still counts metres -- the Euclidean lengths of the flown legs, never `flight.cost`, which
+holds penalties -- and `route_unknown` [N] int64 is the number of costly nodes entered on the route flown this step: the flown
+route nodes but the first, the node the drone already sat at (0 on an episode's first pose and without a route; None for
+other fields).
 """
 from __future__ import annotations
 
@@ -165,6 +170,8 @@ class ReplayFeedEnv:
         self._belief = flight is not None and bool(getattr(flight, "belief", False))
         self.route_overflow = self.routed = None
         self.skipped = None  # with flight.shortcut: the waypoints the last step's straight first leg skipped, int64 [N]
+        self.route_unknown = None  # with a price on unknown space: the costly nodes entered on the last step's route, int64 [N]
+        self._cautious = self._belief and getattr(flight, "costly_map", None) is not None
         if self._belief:
             if int(flight.grid_size) != int(cfg.grid_size):
                 raise ValueError(f"flight is built for a {flight.grid_size}^3 grid, the env's is {cfg.grid_size}^3")
@@ -176,6 +183,7 @@ class ReplayFeedEnv:
             self._node_pos = torch.as_tensor(flight.lattice.node_positions(), device=self.device).to(torch.float32)
             self.route_overflow = torch.zeros((), dtype=torch.int64, device=self.device)  # routes longer than the buffer, so far
             self.routed = torch.zeros(n, dtype=torch.bool, device=self.device)  # the last step flew a route of the field
+            self.route_unknown = torch.zeros(n, dtype=torch.int64, device=self.device) if self._cautious else None
             if getattr(flight, "shortcut", False):
                 self._map_codes = torch.zeros(n, length + 1, dtype=torch.uint8, device=self.device)
                 self.skipped = torch.zeros(n, dtype=torch.int64, device=self.device)
@@ -387,6 +395,7 @@ class ReplayFeedEnv:
         way[:, 0] = prev[:, :3]
         way[:, 1:length + 1] = torch.where((j < cnt[:, None])[..., None], self._node_pos[ids], new)  # past the route: the new pose
         way[:, length + 1] = poses[:, :3]
+        self._route_ids = torch.where(j < cnt[:, None], ids, torch.full_like(ids, -1))  # the node of waypoint 1 + j; -1 past the route
         return way, cnt
 
     def _fly_belief_step(self):
@@ -406,11 +415,23 @@ class ReplayFeedEnv:
         code = ((codes & 8) != 0).any(dim=1).to(torch.uint8) * 8 | ((codes & 16) != 0).any(dim=1).to(torch.uint8) * 16
         self.path_code.copy_(code)
         self.collision_buf |= code
-        straight = (poses[:, :3] - prev[:, :3]).norm(dim=-1)
-        flown = torch.where(routed, fl.cost(poses.unsqueeze(1))[:, 0], straight)
         first = self.episode_length_buf <= 1  # after the step's head: the pose was set, not flown to
+        if self._cautious:  # the field holds penalties: the metres are the legs' own (an env without a route has the one straight leg)
+            lens = (way[:, 1:] - way[:, :-1]).norm(dim=-1)
+            flown = torch.where(legs, lens, torch.zeros_like(lens)).sum(dim=1)
+            self._count_unknown(torch.ones_like(cnt), first)
+        else:
+            straight = (poses[:, :3] - prev[:, :3]).norm(dim=-1)
+            flown = torch.where(routed, fl.cost(poses.unsqueeze(1))[:, 0], straight)
         self.flight_length.copy_(torch.where(first, torch.zeros_like(flown), self.flight_length + flown))
         self.routed.copy_(routed & ~first)
+
+    def _count_unknown(self, jstar, first):
+        """route_unknown: the costly nodes among the flown route nodes, waypoints max(j*, 2) .. count (waypoint 1 is the node the
+        drone sat at: not entered)."""
+        wp = torch.arange(1, self._route_len + 1, device=self.device)[None]
+        entered = self.flight.costly_at(self._route_ids) & (wp >= jstar[:, None].clamp(min=2))
+        self.route_unknown.copy_(torch.where(first, torch.zeros_like(jstar), entered.sum(dim=1)))
 
     def _fly_belief_shortcut_step(self):
         """_fly_belief_step with the straight shortcut judged on the map (`flight.shortcut`): of the legs w_0 -> w_j, j = 1 .. c + 1
@@ -444,6 +465,8 @@ class ReplayFeedEnv:
         self.flight_length.copy_(torch.where(first, torch.zeros_like(flown), self.flight_length + flown))
         self.routed.copy_((jstar <= cnt) & ~first)
         self.skipped.copy_(torch.where(first, torch.zeros_like(jstar), jstar - 1))
+        if self._cautious:
+            self._count_unknown(jstar, first)
 
     def _rgba_or_zero(self, rgba):
         if rgba is None:

@@ -172,10 +172,16 @@ class MapGreedyPolicy(GreedyGainPolicy):
     business (ReplayFeedEnv flies the field's route and lets the true mesh judge it).
     `shortcut` (None: as env.flight.shortcut) also asks the map about the straight leg from env.poses to the candidate
     (BeliefFlightField.sweep, the body's own radius instead of a node's inflated one): a candidate is then refused iff no route
-    reaches it AND its straight leg is blocked on the map -- contact = ~reachable & (sweep != 0).  Still no mesh predicate."""
+    reaches it AND its straight leg is blocked on the map -- contact = ~reachable & (sweep != 0).  Still no mesh predicate.
+    `max_cost_m` (None: the contact rule above alone) is a risk budget for a field with a price on unknown space
+    (BeliefFlightField(unknown="costly")): a candidate with a route is also refused when env.flight.cost to it -- metres plus the
+    penalties of the costly nodes entered -- exceeds max_cost_m.  One more query of the field, no mesh predicate."""
 
     def __init__(self, env, k: int = 32, weights=(1, 4), seed: int = 0, stride: int = 4, look_at_scene: bool = False,
-                 gain_backend: Optional[Callable] = None, shortcut: Optional[bool] = None):
+                 gain_backend: Optional[Callable] = None, shortcut: Optional[bool] = None, max_cost_m: Optional[float] = None):
+        if max_cost_m is not None and not float(max_cost_m) > 0.0:  # (a NaN fails too)
+            raise ValueError(f"MapGreedyPolicy: max_cost_m must be > 0 or None, got {max_cost_m}")
+        self.max_cost_m = None if max_cost_m is None else float(max_cost_m)
         if not getattr(getattr(env, "flight", None), "belief", False):
             from .. import _lib
             raise _lib.GennbvHipError("MapGreedyPolicy needs an env whose flight is a BeliefFlightField")
@@ -200,9 +206,13 @@ class MapGreedyPolicy(GreedyGainPolicy):
 
     def contact(self, poses: torch.Tensor) -> torch.Tensor:
         fl = self.env.flight
+        refused = ~fl.reachable(poses)
         if self.shortcut:
-            return self._contact.copy_(~fl.reachable(poses) & (fl.sweep(self.env.poses, poses) != 0))
-        return self._contact.copy_(~fl.reachable(poses))
+            refused &= fl.sweep(self.env.poses, poses) != 0
+        if self.max_cost_m is not None:
+            cost = fl.cost(poses)
+            refused |= torch.isfinite(cost) & (cost > self.max_cost_m)
+        return self._contact.copy_(refused)
 
 
 class OracleGainPolicy:

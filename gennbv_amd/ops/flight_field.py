@@ -15,7 +15,9 @@ by `path()`, the way ScanAccumulator reports its flags.  GPU only.
 
 BeliefFlightField is the same field over the agent's own map: its blocked bits are recomputed every step from the tri-class
 grid (csrc/flightmap.hip) and no mesh is consulted.  With `shortcut=True` it also keeps a snapshot of that map and judges straight
-legs on it (`sweep`: gnbv_sweep_tri, csrc/sweepmap.hip).
+legs on it (`sweep`: gnbv_sweep_tri, csrc/sweepmap.hip).  With `unknown="costly"` unknown space is flyable at a price: the nodes
+whose ball touches an unknown voxel cost `unknown_penalty_m` more to enter (gnbv_flight_classify_tri, gnbv_flight_field_w,
+gnbv_flight_path_w).
 """
 from __future__ import annotations
 
@@ -52,6 +54,9 @@ class FlightField:
         self._lo = (C.c_double * 3)(*[float(v) for v in lattice.lo])
         self._h = (C.c_double * 3)(*[float(v) for v in lattice.h])
         self.launches = 0  # field launches so far
+        # a field with a price on some nodes (BeliefFlightField, unknown="costly"): their bits [N, words] and the price; None keeps
+        # every launch the plain one
+        self.costly, self.penalty_mm = None, 0
         # pairwise_mm: its private field (shares `blocked`), its sticky device flags (1 sweep cap, 2 a sum too wide), its buffers per P
         self._pair, self._pair_status, self._pair_rows, self._pair_out = None, None, {}, {}
 
@@ -63,9 +68,13 @@ class FlightField:
         assert poses.dtype == torch.float32 and poses.dim() == 2 and poses.shape[0] == n and poses.shape[1] >= 3 and poses.stride(1) == 1
         nx, ny, nz = self.lattice.dims
         self.source.copy_(poses[:, :3])
-        _lib.check(self.lib.gnbv_flight_field(self.blocked.data_ptr(), n, nx, ny, nz, self._cost, poses.data_ptr(), max(int(poses.stride(0)), 3),
-                                              self._lo, self._h, self.field.data_ptr(), self.status.data_ptr(), self.mode,
-                                              _lib.stream_ptr(self.device)), "gnbv_flight_field")
+        tail = (self._cost, poses.data_ptr(), max(int(poses.stride(0)), 3), self._lo, self._h, self.field.data_ptr(), self.status.data_ptr(),
+                self.mode, _lib.stream_ptr(self.device))
+        if self.costly is None:
+            _lib.check(self.lib.gnbv_flight_field(self.blocked.data_ptr(), n, nx, ny, nz, *tail), "gnbv_flight_field")
+        else:
+            _lib.check(self.lib.gnbv_flight_field_w(self.blocked.data_ptr(), self.costly.data_ptr(), self.penalty_mm, n, nx, ny, nz, *tail),
+                       "gnbv_flight_field_w")
         self.launches += 1
         return self
 
@@ -150,7 +159,8 @@ class FlightField:
 
     def cost_mm(self, targets: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """gnbv_flight_query: int32 [N,K] holding the u32 field value (mm) at the nearest node of targets [N, K, >= 3] f32;
-        -1 (0xFFFFFFFF) = blocked, unreachable or no node."""
+        -1 (0xFFFFFFFF) = blocked, unreachable or no node.  Over a field with a price on unknown space (`costly`) the value holds
+        the penalties of the costly nodes entered: it is a cost, not a length."""
         targets, k, row = self._targets(targets)
         n = self.num_envs
         if out is None:
@@ -163,7 +173,9 @@ class FlightField:
 
     def cost(self, targets: torch.Tensor) -> torch.Tensor:
         """f32 [N,K]: the length in metres of the route from the poses of the last update() to targets [N, K, >= 3] -- the stub
-        from the pose to its node, the lattice distance, the stub from the target's node to the target -- or inf."""
+        from the pose to its node, the lattice distance, the stub from the target's node to the target -- or inf.  Over a field
+        with a price on unknown space (`costly`) the lattice term is the penalised value: metres flown plus `unknown_penalty_m` per
+        costly node entered."""
         mm = self.cost_mm(targets)
         lat = self.lattice
         t = targets[..., :3].to(torch.float64)
@@ -173,7 +185,7 @@ class FlightField:
         return torch.where(mm == -1, torch.full_like(metres, float("inf")), metres)
 
     def reachable(self, targets: torch.Tensor) -> torch.Tensor:
-        """bool [N,K]: a route exists from the poses of the last update() to each target."""
+        """bool [N,K]: a route over non-blocked nodes exists from the poses of the last update() to each target."""
         return self.cost_mm(targets) != -1
 
     def path(self, targets: torch.Tensor, max_len: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -202,7 +214,7 @@ class FlightField:
         return way, torch.where(ok, count + 2, torch.zeros_like(count))
 
     def path_into(self, targets: torch.Tensor, nodes_out: torch.Tensor, len_out: torch.Tensor):
-        """One gnbv_flight_path launch into the caller's buffers: nodes_out int32 [N, L], len_out int32 [N] (0 no route, -needed where
+        """One gnbv_flight_path (with `costly`: gnbv_flight_path_w) launch into the caller's buffers: nodes_out int32 [N, L], len_out int32 [N] (0 no route, -needed where
         L is too short).  No host synchronisation."""
         n = self.num_envs
         nx, ny, nz = self.lattice.dims
@@ -210,9 +222,12 @@ class FlightField:
         assert targets.dtype == torch.float32 and targets.dim() == 2 and targets.shape[0] == n and targets.shape[1] >= 3 and targets.stride(1) == 1
         assert nodes_out.dtype == torch.int32 and nodes_out.dim() == 2 and nodes_out.shape[0] == n and nodes_out.is_contiguous()
         assert len_out.dtype == torch.int32 and len_out.shape == (n,) and len_out.is_contiguous()
-        _lib.check(self.lib.gnbv_flight_path(self.field.data_ptr(), n, nx, ny, nz, self._cost, self._lo, self._h, targets.data_ptr(),
-                                             max(int(targets.stride(0)), 3), nodes_out.data_ptr(), int(nodes_out.shape[1]), len_out.data_ptr(),
-                                             _lib.stream_ptr(self.device)), "gnbv_flight_path")
+        tail = (n, nx, ny, nz, self._cost, self._lo, self._h, targets.data_ptr(), max(int(targets.stride(0)), 3), nodes_out.data_ptr(),
+                int(nodes_out.shape[1]), len_out.data_ptr(), _lib.stream_ptr(self.device))
+        if self.costly is None:
+            _lib.check(self.lib.gnbv_flight_path(self.field.data_ptr(), *tail), "gnbv_flight_path")
+        else:
+            _lib.check(self.lib.gnbv_flight_path_w(self.field.data_ptr(), self.costly.data_ptr(), self.penalty_mm, *tail), "gnbv_flight_path_w")
 
     def path_nodes(self, targets: torch.Tensor, max_len: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """The raw walk: (nodes int32 [N, L] from the target's node back to the source, count int32 [N]; 0 = no route).  Runs the
@@ -239,7 +254,7 @@ class BeliefFlightField(FlightField):
         field.update(poses)    # blocked = blocked_map with each env's own node cleared, then the field launch
 
     A node is blocked where the ball of radius rho = lattice.inflated_radius(body) + margin touches an occupied voxel
-    (`unknown="blocked"`: or an unknown one, the conservative pilot; the default "free" is the optimistic one), with
+    (`unknown="blocked"`: or an unknown one, the conservative pilot; the default "free" is the optimistic one; "costly" below), with
     `outside="blocked"` where it leaves the grid (range_gt bounds every solid of a scene by grid_spec's construction, hence the
     default "free"), and with body.ground where it reaches z <= 0.  The drone is at its own nearest node, so update() calls
     that node flyable whatever the map says; `blocked_map` stays the pure kernel output.  `map_mode`: 0 auto, 1 the grid's
@@ -250,17 +265,38 @@ class BeliefFlightField(FlightField):
     pilot's knowledge must not alias it), and `sweep` moves the sphere of radius `sweep_radius` = body.path_radius +
     shortcut_margin along straight legs over it (a lattice node needs the inflated rho so that its edges are safe; a straight leg
     needs only the body's own radius).  `sweeps` counts those launches.  With shortcut=False nothing is allocated or launched
-    that was not before."""
+    that was not before.
+
+    `unknown="costly", unknown_penalty_m=<metres>` is the cautious pilot: unknown space is flyable but expensive.  refresh() is one
+    gnbv_flight_classify_tri launch into `blocked_map` (occupied, outside, ground: what "free" blocks) and `costly_map` (not blocked,
+    the ball touches an unknown voxel); update() clears the drone's own node in `blocked` only and launches gnbv_flight_field_w with
+    penalty_mm = rint(1000 * unknown_penalty_m) per costly node entered, and the path methods walk with gnbv_flight_path_w.
+    `cost_mm` / `cost` then hold penalties; `reachable` and `pairwise_mm` (the plain kernel over `blocked`: geometric lengths) do
+    not.  `sweep` and the shortcut judge straight legs with unknown voxels blocking: the cautious pilot cuts corners only
+    through space it has seen.  There is no default penalty: nobody has measured one.  With any other `unknown` nothing is
+    allocated or launched that was not before."""
     belief = True
 
     def __init__(self, num_envs: int, lattice, body, range_gt: torch.Tensor, voxel_size: torch.Tensor, grid_size: int,
                  unknown: str = "free", outside: str = "free", margin: float = 0.0, mode: int = 0, map_mode: int = 0, device="cuda:0",
-                 shortcut: bool = False, shortcut_margin: float = 0.0):
+                 shortcut: bool = False, shortcut_margin: float = 0.0, unknown_penalty_m: Optional[float] = None):
         import types
         device = torch.device(device)
-        for name, val in (("unknown", unknown), ("outside", outside)):
-            if val not in ("free", "blocked"):
-                raise ValueError(f"BeliefFlightField: {name} must be 'free' or 'blocked', got {val!r}")
+        if unknown not in ("free", "blocked", "costly"):
+            raise ValueError(f"BeliefFlightField: unknown must be 'free', 'blocked' or 'costly', got {unknown!r}")
+        if outside not in ("free", "blocked"):
+            raise ValueError(f"BeliefFlightField: outside must be 'free' or 'blocked', got {outside!r}")
+        penalty_mm = 0
+        if unknown == "costly":
+            if unknown_penalty_m is None or not np.isfinite(float(unknown_penalty_m)) or not float(unknown_penalty_m) > 0.0:
+                raise ValueError(f"BeliefFlightField: unknown='costly' needs a finite unknown_penalty_m > 0, got {unknown_penalty_m!r}")
+            penalty_mm = int(np.rint(1000.0 * float(unknown_penalty_m)))
+            # the bound of gnbv_flight_field_w: every route's cost must stay below 0xFFFFFFFE
+            if penalty_mm < 1 or int(lattice.num_nodes) * (int(max(lattice.cost)) + penalty_mm) >= INF_MM - 1:
+                raise ValueError(f"BeliefFlightField: unknown_penalty_m = {unknown_penalty_m} gives {penalty_mm} mm, outside what "
+                                 f"{lattice.num_nodes} nodes admit (M * (max edge cost + penalty) < 0xFFFFFFFE, at least 1 mm)")
+        elif unknown_penalty_m is not None:
+            raise ValueError("BeliefFlightField: unknown_penalty_m goes with unknown='costly' only")
         if int(map_mode) not in (0, 1, 2):
             raise ValueError(f"BeliefFlightField: map_mode must be 0, 1 or 2, got {map_mode}")
         n, g = int(num_envs), int(grid_size)
@@ -273,41 +309,70 @@ class BeliefFlightField(FlightField):
         if device.type != "cuda":
             raise _lib.GennbvHipError("BeliefFlightField runs on the GPU only (no CPU fallback)")
         lib = _lib.load()
-        if int(map_mode) == 1 and g > int(lib.gnbv_flightmap_lds_max_grid()):
+        cautious = unknown == "costly"
+        if int(map_mode) == 1 and g > int(lib.gnbv_flightmap_classify_lds_max_grid() if cautious else lib.gnbv_flightmap_lds_max_grid()):
             raise _lib.GennbvHipError(f"BeliefFlightField: the bits of a {g}^3 grid do not fit LDS (map_mode 1)")
         self.rho = float(lattice.inflated_radius(body)) + float(margin)
         if not (np.isfinite(self.rho) and self.rho > 0.0):
             raise ValueError(f"BeliefFlightField: the inflated radius plus margin must be finite and > 0, got {self.rho}")
         self.grid_size, self.map_mode = g, int(map_mode)
-        self.unknown_blocks, self.outside_blocks = unknown == "blocked", outside == "blocked"
+        # (cautious: what sweep() hands to gnbv_sweep_tri -- straight legs only through seen space; the nodes' unknown goes to costly_map)
+        self.unknown, self.unknown_blocks, self.outside_blocks = unknown, unknown in ("blocked", "costly"), outside == "blocked"
         self.range_gt = range_gt.to(device, torch.float32).contiguous()
         self.voxel_size = voxel_size.to(device, torch.float32).contiguous()
         assert self.range_gt.shape == (n, 6) and self.voxel_size.shape == (n, 3)
         blocked = torch.full((n, lattice.words), -1, dtype=torch.int32, device=device)  # all blocked until the first refresh
         super().__init__(types.SimpleNamespace(device=device, num_envs=n), lattice, body, mode=mode, blocked=blocked)
         self.blocked_map = torch.full_like(self.blocked, -1)
+        self.costly_map = None
+        if cautious:
+            self.costly_map = torch.zeros_like(self.blocked)
+            self.costly, self.penalty_mm = self.costly_map, penalty_mm
         self.refreshes = 0  # map launches so far
         self.sweeps = 0  # gnbv_sweep_tri launches so far
         self.map_i8 = torch.zeros(n, g ** 3, dtype=torch.int8, device=device) if self.shortcut else None  # all unknown until refresh()
         self.has_map = False  # a refresh() has filled the snapshot
 
     def refresh(self, tri: torch.Tensor) -> "BeliefFlightField":
-        """gnbv_flight_blocked_tri on the current stream into `blocked_map`: tri [N, >= G^3] int8 or float32, unit element
-        stride, any row stride (e.g. obs[:, state_dim:state_dim + grid_dim])."""
+        """gnbv_flight_blocked_tri on the current stream into `blocked_map` (unknown="costly": gnbv_flight_classify_tri into `blocked_map`
+        and `costly_map`): tri [N, >= G^3] int8 or float32, unit element stride, any row stride (e.g.
+        obs[:, state_dim:state_dim + grid_dim])."""
         n, g3 = self.num_envs, self.grid_size ** 3
         row = self._check_tri(tri, "refresh")
         i8 = tri.dtype == torch.int8
         nx, ny, nz = self.lattice.dims
-        _lib.check(self.lib.gnbv_flight_blocked_tri(tri.data_ptr() if i8 else None, row if i8 else 0, None if i8 else tri.data_ptr(),
-                                                    0 if i8 else row, self.grid_size, self.range_gt.data_ptr(), self.voxel_size.data_ptr(),
-                                                    n, nx, ny, nz, self._lo, self._h, self.rho, int(self.unknown_blocks),
-                                                    int(self.outside_blocks), int(bool(self.body.ground)), self.blocked_map.data_ptr(),
-                                                    self.map_mode, _lib.stream_ptr(self.device)), "gnbv_flight_blocked_tri")
+        head = (tri.data_ptr() if i8 else None, row if i8 else 0, None if i8 else tri.data_ptr(), 0 if i8 else row, self.grid_size,
+                self.range_gt.data_ptr(), self.voxel_size.data_ptr(), n, nx, ny, nz, self._lo, self._h, self.rho)
+        flags = (int(self.outside_blocks), int(bool(self.body.ground)))
+        tail = (self.map_mode, _lib.stream_ptr(self.device))
+        if self.costly_map is None:
+            _lib.check(self.lib.gnbv_flight_blocked_tri(*head, int(self.unknown_blocks), *flags, self.blocked_map.data_ptr(), *tail),
+                       "gnbv_flight_blocked_tri")
+        else:
+            _lib.check(self.lib.gnbv_flight_classify_tri(*head, *flags, self.blocked_map.data_ptr(), self.costly_map.data_ptr(), *tail),
+                       "gnbv_flight_classify_tri")
         self.refreshes += 1
         if self.shortcut:
             self.map_i8.copy_(tri[:, :g3] if i8 else torch.sign(tri[:, :g3]))
             self.has_map = True
         return self
+
+    def costly_at(self, nodes: torch.Tensor) -> torch.Tensor:
+        """bool, the shape of nodes [N, ...] (integer node ids, row e of env e): the `costly_map` bit of each node; False for an id
+        below 0.  Torch gathers, no host synchronisation."""
+        if self.costly_map is None:
+            raise _lib.GennbvHipError("BeliefFlightField.costly_at: the field has no costly_map (unknown='costly')")
+        ids = nodes.long().reshape(self.num_envs, -1)
+        safe = ids.clamp(min=0)
+        bit = (self.costly_map.gather(1, safe >> 5).long() >> (safe & 31)) & 1
+        return ((bit != 0) & (ids >= 0)).reshape(nodes.shape)
+
+    def costly_count(self, nodes: torch.Tensor, count: torch.Tensor) -> torch.Tensor:
+        """int64 [N]: the number of costly nodes ENTERED on a walked route -- nodes int32 [N, L] from the target's node back to the
+        source and count int32 [N] as path_nodes / path_into give them; the source (the last node) is not entered, and a count
+        <= 0 gives 0.  penalty_mm times this is the penalty part of the field at the target."""
+        inside = torch.arange(nodes.shape[1], device=self.device)[None] < (count[:, None].long() - 1)
+        return (self.costly_at(nodes) & inside).sum(dim=1)
 
     def _check_tri(self, tri: torch.Tensor, what: str) -> int:
         """The tensor checks of refresh() and sweep(); returns the row stride in elements."""

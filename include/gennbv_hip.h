@@ -316,6 +316,27 @@ int gnbv_flight_path(const uint32_t *field /*[N,M]*/, int n, int nx, int ny, int
                      int64_t targets_row_stride /*floats*/, int32_t *nodes_out /*[N,max_len]*/, int max_len, int32_t *len_out /*[N]*/,
                      void *stream);
 
+/* Unknown space at a price (additive entry points of ABI 5): gnbv_flight_field / gnbv_flight_path with a penalty for entering a
+ * "costly" node.  costly [N, ceil(M / 32)] u32, the layout of `blocked`; a costly bit on a blocked node is ignored, padding bits are
+ * not read.  field_out[e, c] = the minimum, over routes from the source node to c through non-blocked nodes, of the sum of the edge
+ * costs plus penalty_mm times the number of costly nodes entered on the route (c included, the source not); the source holds 0,
+ * blocked and unreachable nodes 0xFFFFFFFF, and so does every node of an env whose source is blocked or absent.  Integer sums: the
+ * result is exact and independent of the order of relaxation; with penalty_mm = 0 or an all-zero `costly` it is byte for byte
+ * gnbv_flight_field's.  Modes, status_out and the sweep cap as gnbv_flight_field.  Refused (hipErrorInvalidValue, before any launch)
+ * for everything gnbv_flight_field refuses, a NULL costly, and M * (max used cost + penalty_mm) >= 0xFFFFFFFE (in 64 bits). */
+int gnbv_flight_field_w(const uint32_t *blocked /*[N,ceil(M/32)]*/, const uint32_t *costly /*[N,ceil(M/32)]*/, uint32_t penalty_mm, int n,
+                        int nx, int ny, int nz, const uint32_t *cost /*[host] 8*/, const float *poses, int64_t poses_row_stride /*floats*/,
+                        const double *lo /*[host] 3*/, const double *h /*[host] 3*/, uint32_t *field_out /*[N,M]*/,
+                        int32_t *status_out /*[N]*/, int mode, void *stream);
+/* gnbv_flight_path over a field of gnbv_flight_field_w (the same costly and penalty_mm): from each node the walk takes the first
+ * neighbour, in the fixed order dz, dy, dx with dx fastest, with field[neighbour] < field[node] and
+ * field[neighbour] + cost + penalty_mm * costly(node) == field[node].  len_out as gnbv_flight_path.  gnbv_flight_query reads such a
+ * field unchanged. */
+int gnbv_flight_path_w(const uint32_t *field /*[N,M]*/, const uint32_t *costly /*[N,ceil(M/32)]*/, uint32_t penalty_mm, int n, int nx,
+                       int ny, int nz, const uint32_t *cost /*[host] 8*/, const double *lo /*[host] 3*/, const double *h /*[host] 3*/,
+                       const float *targets, int64_t targets_row_stride /*floats*/, int32_t *nodes_out /*[N,max_len]*/, int max_len,
+                       int32_t *len_out /*[N]*/, void *stream);
+
 /* The free set of the flight lattice from the scanned map (an additive entry point of ABI 5; csrc/flightmap.hip): the blocked bits
  * gnbv_flight_field reads, from each env's tri-class grid instead of the ground-truth mesh.  tri [G,G,G] per env in C order x, y, z
  * with gnbv_view_gain's signs: < 0 free, 0 unknown, > 0 occupied.  Exactly one of the two forms: tri_i8 (int8 rows, row stride in
@@ -343,6 +364,21 @@ int gnbv_flight_blocked_tri(const int8_t *tri_i8 /*[N, >= G^3] or NULL*/, int64_
                             const float *range_gt /*[N,6]*/, const float *voxel_size /*[N,3]*/, int n, int nx, int ny, int nz,
                             const double *lo /*[host] 3*/, const double *h /*[host] 3*/, double rho, int unknown_blocks,
                             int outside_blocks, int ground, uint32_t *blocked_out /*[N,ceil(M/32)]*/, int mode, void *stream);
+
+/* gnbv_flight_blocked_tri with unknown space told apart, in one launch (an additive entry point of ABI 5): the arguments of
+ * gnbv_flight_blocked_tri without unknown_blocks, two outputs [N, ceil(M / 32)], every word of both written.  The predicate, the
+ * voxel frame and the rule of the window are those above.  blocked_out = gnbv_flight_blocked_tri(unknown_blocks = 0, the same
+ * outside_blocks and ground), padding bits set.  Bit c of costly_out is set iff node c is not blocked and a touched voxel is
+ * unknown -- gnbv_flight_blocked_tri(unknown_blocks = 1) & ~blocked_out inside M -- padding bits clear.  mode 1 packs two bit planes
+ * (occupied, unknown) into LDS and is refused above gnbv_flightmap_classify_lds_max_grid(); the other refusals, the loop bounds and
+ * "one launch, one writer per word, no atomics, no workspace, no host synchronisation" as gnbv_flight_blocked_tri; a NULL costly_out
+ * is refused too. */
+int gnbv_flightmap_classify_lds_max_grid(void); /* the largest G of mode 1 of gnbv_flight_classify_tri: 86 */
+int gnbv_flight_classify_tri(const int8_t *tri_i8 /*[N, >= G^3] or NULL*/, int64_t tri_i8_row_stride /*bytes*/,
+                             const float *tri_f32 /*[N, >= G^3] or NULL*/, int64_t tri_f32_row_stride /*floats*/, int g,
+                             const float *range_gt /*[N,6]*/, const float *voxel_size /*[N,3]*/, int n, int nx, int ny, int nz,
+                             const double *lo /*[host] 3*/, const double *h /*[host] 3*/, double rho, int outside_blocks, int ground,
+                             uint32_t *blocked_out /*[N,ceil(M/32)]*/, uint32_t *costly_out /*[N,ceil(M/32)]*/, int mode, void *stream);
 
 /* A straight flight judged on the scanned map (an additive entry point of ABI 5; csrc/sweepmap.hip): the sphere of radius R moved
  * along N x K straight legs against each env's tri-class grid.  The grid forms, the signs (< 0 free, 0 unknown, > 0 occupied), the

@@ -1,7 +1,7 @@
 """Closed-loop table of DESIGN.md "Flying on the scanned map": the greedy planner with the privileged flight field beside the
 pilot that knows only its own map.
 
-    python tools/closed_loop_belief.py [--envs 16] [--grid 20] [--steps 20] [--k 32] [--seeds 1] [--stride 2] [--out FILE.json]
+    python tools/closed_loop_belief.py [--envs 16] [--grid 20] [--steps 20] [--k 32] [--seeds 1] [--stride 2] [--penalties 1,5,20] [--out FILE.json]
 
 The set-up of tools/closed_loop_flight.py (box scenes, 60 x 80 camera, CollisionBody(sweep=True), episodes of at most `steps`
 steps, each env's first episode).  Rows:
@@ -9,14 +9,17 @@ steps, each env's first episode).  Rows:
   greedy / privileged        GreedyGainPolicy, flight=FlightField(mesh): contacts and routes from the ground-truth mesh
   map-greedy / optimistic    MapGreedyPolicy, flight=BeliefFlightField(unknown="free"): routes through what it has not seen
   map-greedy / conservative  MapGreedyPolicy, flight=BeliefFlightField(unknown="blocked"): routes through seen free space only
-  ... + shortcut             the two belief rows with shortcut=True: straight legs judged on the map (csrc/sweepmap.hip), in the env
+  map-greedy / cautious P m  MapGreedyPolicy, flight=BeliefFlightField(unknown="costly", unknown_penalty_m=P), P = 1, 5, 20: unknown
+                             space is flyable at P metres per node entered (gnbv_flight_classify_tri, gnbv_flight_field_w)
+  ... + shortcut             the belief rows with shortcut=True: straight legs judged on the map (csrc/sweepmap.hip), in the env
                              (straight to the farthest waypoint in the clear) and in the planner (a clear straight leg reaches)
 
 Columns: final coverage, episode length, metres flown (env.flight_length at the step that ends the episode), the share of
 flown steps that followed a route of the field (with the shortcut: flew at least one route node), the share flown fully
 straight (privileged: the straight flight was free; belief: no route node was flown), the share of episodes ended by a path
 collision and by a pose collision, for the belief rows the share of decisions in which every candidate was refused, and for
-the shortcut rows the mean number of waypoints a step's straight first leg skipped.  Reported, not asserted.
+the shortcut rows the mean number of waypoints a step's straight first leg skipped, and for the cautious rows the mean
+env.route_unknown per flown step (costly nodes entered).  Reported, not asserted.
 """
 from __future__ import annotations
 
@@ -47,7 +50,8 @@ def run(policy, env, steps):
     belief = bool(getattr(env.flight, "belief", False))
     obs = env.reset()
     alive = torch.ones(n, dtype=torch.bool, device=DEV)
-    final, length, flown, routed, moved, stuck, decisions, straight, skipped = (torch.zeros(n, device=DEV) for _ in range(9))
+    final, length, flown, routed, moved, stuck, decisions, straight, skipped, unknown = (torch.zeros(n, device=DEV) for _ in range(10))
+    cautious = belief and env.route_unknown is not None
     shortcut = belief and bool(getattr(env.flight, "shortcut", False))
     code = torch.zeros(n, dtype=torch.uint8, device=DEV)
     for t in range(steps):
@@ -65,6 +69,8 @@ def run(policy, env, steps):
             straight += (alive & (env.path_code == 0)).float()
         if shortcut:
             skipped += torch.where(alive, env.skipped, torch.zeros_like(env.skipped)).float()
+        if cautious:
+            unknown += torch.where(alive, env.route_unknown, torch.zeros_like(env.route_unknown)).float()
         flown = torch.where(alive, env.flight_length, flown)
         ends = alive & done
         final = torch.where(ends, env.coverage_ratio, final)
@@ -86,6 +92,8 @@ def run(policy, env, steps):
         out["route_overflows"] = int(env.route_overflow)
     if shortcut:
         out["mean_skipped"] = float(skipped.sum() / moved.sum().clamp(min=1.0))
+    if cautious:
+        out["mean_route_unknown"] = float(unknown.sum() / moved.sum().clamp(min=1.0))
     return out
 
 
@@ -97,6 +105,7 @@ def main():
     ap.add_argument("--k", type=int, default=32)
     ap.add_argument("--seeds", default="1")
     ap.add_argument("--stride", type=int, default=2)
+    ap.add_argument("--penalties", default="1,5,20", help="the cautious rows' unknown_penalty_m, metres per unknown node entered")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -110,14 +119,17 @@ def main():
     blocked = mesh.flight_blocked(lattice, body)  # once per scene set
     res = {"envs": n, "grid": g, "steps": args.steps, "k": args.k, "stride": args.stride, "rows": []}
     for seed in (int(s) for s in args.seeds.split(",")):
-        for name in ("greedy / privileged", "map-greedy / optimistic", "map-greedy / conservative", "map-greedy / optimistic + shortcut",
-                     "map-greedy / conservative + shortcut"):
+        names = ["greedy / privileged", "map-greedy / optimistic", "map-greedy / conservative"]
+        names += [f"map-greedy / cautious {p} m" for p in args.penalties.split(",")]
+        for name in names + [f"{b} + shortcut" for b in names[1:]]:
             if name.startswith("greedy"):
                 flight = FlightField(mesh, lattice, body, blocked=blocked)
             else:
-                flight = BeliefFlightField(n, lattice, body, scene.range_gt, scene.voxel_size, g,
-                                           unknown="free" if "optimistic" in name else "blocked", device=DEV,
-                                           shortcut=name.endswith("shortcut"))
+                kind = name.split(" / ")[1].split(" ")[0]
+                kw = dict(unknown="costly", unknown_penalty_m=float(name.split(" ")[3])) if kind == "cautious" else \
+                    dict(unknown="free" if kind == "optimistic" else "blocked")
+                flight = BeliefFlightField(n, lattice, body, scene.range_gt, scene.voxel_size, g, device=DEV,
+                                           shortcut=name.endswith("shortcut"), **kw)
             env = ReplayFeedEnv(cfg, scene, RenderFeed(mesh, cfg), DEV, max_episode_length=args.steps, collision=body, flight=flight)
             pol = (GreedyGainPolicy if name.startswith("greedy") else MapGreedyPolicy)(env, k=args.k, weights=(1, 4), seed=seed)
             row = {"seed": seed, "row": name}

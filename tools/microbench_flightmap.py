@@ -7,7 +7,10 @@ Device events around `iters` back-to-back calls, after warm-up, `repeats` times,
 median / min / max us per launch.  Cases: N envs of box scenes, the default task's lattice at each stride, the tri-class grid
 of a closed-loop env ten steps into its episode (tools/microbench_view_gain.mid_episode_grid) at each grid size, as int8 rows
 and as fp32 rows; the optimistic pilot (unknown = free) and the conservative one (unknown = blocked); map_mode 1 (bits packed
-into LDS, where the grid fits) and 2 (the grid read from global memory).
+into LDS, where the grid fits) and 2 (the grid read from global memory).  `unknown = costly` is the cautious pilot's case: the one gnbv_flight_classify_tri launch
+(`classify_*`) beside the two gnbv_flight_blocked_tri launches it replaces (`two_launches_*`: unknown_blocks = 0, then 1, over the same
+grid), and gnbv_flight_field_w (`field_w`, penalty 5 m) beside gnbv_flight_field (`field`) over the same blocked bits, all alternated
+in one process.
 """
 from __future__ import annotations
 
@@ -65,6 +68,51 @@ def map_case(cfg, scene, tri_i8, stride, unknown, args):
     return r
 
 
+def classify_case(cfg, scene, tri_i8, stride, args, penalty_m=5.0):
+    """The cautious pilot: classify vs the two blocked_tri launches it replaces, field_w vs field on the same bits."""
+    n, g = scene.range_gt.shape[0], cfg.grid_size
+    lat = FlightLattice(cfg, stride=stride)
+    body = CollisionBody(sweep=True)
+    tri_f32 = tri_i8.to(torch.float32)
+    poses = torch.tensor(cfg.init_pose_buf, dtype=torch.float32, device=DEV).repeat(n, 1)
+    mk = lambda **kw: BeliefFlightField(n, lat, body, scene.range_gt, scene.voxel_size, g, map_mode=0, device=DEV, **kw)  # noqa: E731
+    fns, names, cautious = [], [], []
+    cap = None
+    for mode in (1, 2):
+        ff = mk(unknown="costly", unknown_penalty_m=penalty_m)
+        free, strict = mk(unknown="free"), mk(unknown="blocked")
+        cap = int(ff.lib.gnbv_flightmap_classify_lds_max_grid())
+        if mode == 1 and g > cap:  # (between the two limits the pair still has its LDS form: compared like with like, mode 2 only)
+            continue
+        ff.map_mode = free.map_mode = strict.map_mode = mode
+        cautious.append((ff, free, strict))
+        for form, tri in (("i8", tri_i8), ("f32", tri_f32)):
+            fns.append(lambda ff=ff, tri=tri: ff.refresh(tri))
+            names.append(f"classify_mode{mode}_{form}")
+            fns.append(lambda free=free, strict=strict, tri=tri: (free.refresh(tri), strict.refresh(tri)))
+            names.append(f"two_launches_mode{mode}_{form}")
+    ff, free, _ = cautious[0]
+    ff.refresh(tri_i8).update(poses)
+    free.refresh(tri_i8).update(poses)
+    fns.append(lambda: FlightField.update(ff, poses))
+    names.append("field_w")
+    fns.append(lambda: FlightField.update(free, poses))
+    names.append("field")
+    us = alternate(fns, args.iters, args.repeats)
+    for one, loose, strict in cautious:
+        assert torch.equal(one.blocked_map, loose.blocked_map) and torch.equal(one.costly_map, strict.blocked_map & ~loose.blocked_map), \
+            "classify disagrees with the two launches"
+    pad = lat.words * 32 - lat.num_nodes
+    ones = lambda row: sum(bin(int(w) & 0xFFFFFFFF).count("1") for w in row.tolist())  # noqa: E731
+    r = {"envs": n, "grid": g, "stride": stride, "nodes": lat.num_nodes, "unknown": "costly", "penalty_m": penalty_m, "rho": ff.rho,
+         "classify_lds_max_grid": cap, "blocked_node_frac_env0": float(ones(ff.blocked_map[0]) - pad) / lat.num_nodes,
+         "costly_node_frac_env0": float(ones(ff.costly_map[0])) / lat.num_nodes,
+         "reachable_node_frac_env0": float((ff.field[0] != -1).float().mean())}
+    for name, u in zip(names, us):
+        r[name] = stats(u)
+    return r
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=5)
@@ -86,6 +134,9 @@ def main():
                 r = map_case(cfg, scene, tri, stride, unknown, args)
                 print(json.dumps(r), flush=True)
                 results.append(r)
+            r = classify_case(cfg, scene, tri, stride, args)
+            print(json.dumps(r), flush=True)
+            results.append(r)
         del tri
         torch.cuda.empty_cache()
     if args.out:
