@@ -194,7 +194,30 @@ int gnbv_env_observe(const int64_t *actions_in, const GnbvLattice *lattice /*[ho
 /* Closed-loop camera (a new entry point of ABI 5): renders every env from the pose step() computed, in place of the
  * Isaac Gym camera sensors (env_train_gennbv.py:346-354).  The scene is a triangle soup per env (env-local frame, the
  * frame of the poses and range_gt) with a uniform cell grid of conservative triangle lists (CSR), built once by
- * gennbv_amd/env/mesh_scene.py.  [host struct]; every pointer in it is device. */
+ * gennbv_amd/env/mesh_scene.py.  [host struct]; every pointer in it is device.
+ *
+ * The grid contract, for a caller that builds the arrays itself.  Every kernel that takes a scene (gnbv_render_depth,
+ * gnbv_view_cover[_masks], gnbv_voxelize_surface, gnbv_collide_cylinder[_batch], gnbv_sweep_sphere) asks one thing of the
+ * lists: they are conservative (below).  Its outputs then do not depend on which conservative grid it is given -- box,
+ * resolution, list order, layout: the same bits (tests/test_mesh_grids_gpu.py; rgba alone may differ where two triangles
+ * of different objects tie exactly for the closest hit, because the first one visited wins).
+ *   - A cell's list may be in any order and may repeat a triangle.  (The voxelizer looks a triangle up in neighbouring
+ *     cells by binary search only to skip duplicate work; on an unsorted list the search misses and the triangle is
+ *     tested again, the results are ORed.)
+ *   - A list may name triangles that do not touch its cell, up to every triangle of the env in every cell; it may only
+ *     name triangles of its own env.  Cost grows with the lists, the result does not change.
+ *   - The box [cell_lo, cell_lo + cell_res * cell_size] must hold every vertex of the env strictly inside; beyond that it
+ *     may be any size and lie anywhere (around the cameras, below z = 0), cell_res may be 1 on any axis and the cell edges
+ *     may differ between axes (tested up to 1024 cells on an axis).
+ *   - The cell blocks of the envs may lie anywhere in cell_start, in any order, with unused cells (empty lists) between
+ *     them.  cell_base of an env with cell_res 0 indexes nothing.
+ *   - Conservative means the builder's rule (MeshScene._bin): a triangle is listed in every cell that its axis-aligned
+ *     bounding box, grown on every side by eps = 1e-4 * L + 1e-5 m, overlaps, with the cell index
+ *     floor((x - cell_lo) / cell_size) taken in fp32 and clamped to the grid.  L = the largest extent of the env's triangle
+ *     bounds; a box much larger than the triangles takes its own largest extent, because the rounding below grows with the
+ *     box.  The exact overlap alone is not enough: the renderer walks the cells in fp32 and adds one rounded step per cell
+ *     crossed, so a boundary crossing it computes lies up to 3.5e-4 m (measured at 1024 cells on an axis of 19 m,
+ *     tests/test_mesh_grids_cpu.py) from the true one; eps is 1.9e-3 m there. */
 typedef struct GnbvMeshScene {
     int n;                          /* envs */
     const float *tris;              /* [T,3,3] triangle vertices, all envs concatenated (NULL if T == 0) */

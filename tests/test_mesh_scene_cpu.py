@@ -4,6 +4,7 @@ import torch
 
 from gennbv_amd.env import synthetic as S
 from gennbv_amd.env.mesh_scene import MeshScene, box_triangles, random_rotation, sphere_triangles
+from tests.mesh_grid_util import brute_force_cells as _brute_force_cells, listed as _listed  # (shared with test_mesh_grids_cpu.py)
 
 
 def _areas_normals(t):
@@ -31,43 +32,6 @@ def test_from_boxes_area_normals_and_ids():
         centre = 0.5 * (sc.boxes_min[e, k] + sc.boxes_max[e, k]).double()
         assert ((nrm * (t.double().mean(1) - centre)).sum(-1) > 0).all()
         assert sorted(set(ids.tolist())) == [int(i) + 1 for i in torch.nonzero(valid).flatten()]
-
-
-def _brute_force_cells(m, e):
-    """Cells of env e whose box intersects each triangle (separating-axis test, fp64), as a set of (cell, tri)."""
-    t, _ = m.env_triangles(e)
-    first = int(m.tri_count[:e].sum())
-    r = m.cell_res[e].tolist()
-    ncell = r[0] * r[1] * r[2]
-    lo = torch.stack([m.cell_box(e, c)[0] for c in range(ncell)]).double()
-    hi = torch.stack([m.cell_box(e, c)[1] for c in range(ncell)]).double()
-    ctr, half = 0.5 * (lo + hi), 0.5 * (hi - lo)
-    out = set()
-    axes_e = torch.eye(3, dtype=torch.float64)
-    for i in range(t.shape[0]):
-        v = t[i].double()[None] - ctr[:, None, :]  # [C,3,3]
-        edges = [v[0, 1] - v[0, 0], v[0, 2] - v[0, 1], v[0, 0] - v[0, 2]]
-        axes = [axes_e[a] for a in range(3)] + [torch.cross(edges[0], edges[1], dim=0)]
-        axes += [torch.cross(axes_e[a], ed, dim=0) for a in range(3) for ed in edges]
-        sep = torch.zeros(ncell, dtype=torch.bool)
-        for ax in axes:
-            if ax.norm() < 1e-12:
-                continue
-            p = v @ ax  # [C,3]
-            rad = (half * ax.abs()).sum(-1)
-            sep |= (p.amin(-1) > rad) | (p.amax(-1) < -rad)
-        out |= {(int(c), first + i) for c in torch.nonzero(~sep).flatten()}
-    return out
-
-
-def _listed(m, e):
-    r = m.cell_res[e].tolist()
-    base = int(m.cell_base[e])
-    out = set()
-    for c in range(r[0] * r[1] * r[2]):
-        s, t = int(m.cell_start[base + c]), int(m.cell_start[base + c + 1])
-        out |= {(c, int(k)) for k in m.cell_tris[s:t]}
-    return out
 
 
 def test_cell_lists_are_a_superset_of_the_exact_overlap():
