@@ -70,6 +70,7 @@ SIGNATURES = {
     "gnbv_flight_blocked_tri": (_i, [_p, _i64, _p, _i64, _i, _p, _p, _i, _i, _i, _i, _p, _p, _d, _i, _i, _i, _p, _i, _p]),
     "gnbv_sweepmap_lds_max_grid": (_i, []),
     "gnbv_sweep_tri": (_i, [_p, _i64, _p, _i64, _i, _p, _p, _i, _p, _i64, _i64, _p, _i, _i64, _d, _i, _i, _i, _p, _i, _p]),
+    "gnbv_frontier_tri": (_i, [_p, _i64, _p, _i64, _i, _i, _i, _p, _p, _i, _p]),
     "gnbv_rollout_add": (_i, [_i, _i, _p, _p, _p, _p, _i, _f, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "gnbv_input_autocorr_row_ints": (_i, []),
     "gnbv_input_autocorr": (_i, [_p, _i64, _i, _i, _p, _i64, _p]),

@@ -134,3 +134,35 @@ __device__ __forceinline__ void map_pack_planes(const void *__restrict__ tri, in
         }
     }
 }
+
+// map_pack_planes for a window of the grid (frontier.hip: a slab of x-planes with its halo), planes "free" then "unknown": bit i of
+// the window is voxel first + i -- the voxel order is the memory order, so a run of x-planes is one run of bits -- and a bit past
+// either end of the grid (first may be negative) is clear in both planes: neither free nor unknown.  `words` (even: whole
+// ballots) words of each plane are written, unswizzled: the reader walks consecutive words.  The caller synchronises afterwards.
+template <bool kF32, int kWaves>
+__device__ __forceinline__ void map_pack_window(const void *__restrict__ tri, int g3, int first, int words, uint32_t *fre, uint32_t *unk)
+{
+    constexpr int kUnroll = GNBV_MAP_PACK_UNROLL;
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    const int groups = words / 2;
+    for (int q0 = wave; q0 < groups; q0 += kWaves * kUnroll) {
+        int cls[kUnroll];
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            const int vox = first + (q0 + u * kWaves) * kWave + lane;
+            const int c = voxel_class<kF32>(tri, min(max(vox, 0), g3 - 1));  // (the load is unconditional, as above)
+            cls[u] = (vox >= 0 && vox < g3) ? c : 1;
+        }
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            const int q = q0 + u * kWaves;
+            const unsigned long long mf = __ballot(cls[u] < 0), mu = __ballot(cls[u] == 0);
+            if (q < groups && lane == 0) {
+                fre[2 * q] = (uint32_t)mf;
+                fre[2 * q + 1] = (uint32_t)(mf >> 32);
+                unk[2 * q] = (uint32_t)mu;
+                unk[2 * q + 1] = (uint32_t)(mu >> 32);
+            }
+        }
+    }
+}

@@ -47,6 +47,103 @@ class LatticeCandidates:
         return S.poses_from_actions(actions, self.cfg).float()
 
 
+class FrontierCandidates:
+    """LatticeCandidates aimed at the frontier of the scanned map (ops/frontier.py, csrc/frontier.hip): the same `sample` / `poses`
+    protocol plus `observe(tri)`, which the greedy planners call with the step's tri slice before `sample`.
+
+    `sample` first makes exactly the draw LatticeCandidates(cfg, k, seed) makes (the same generator calls: with equal seeds the base
+    actions are equal).  Then, per env, with M' the number of non-empty blocks among the `top` blocks holding the most frontier
+    voxels (Frontier.top: ties to the lowest block index): M' = 0 -- nothing scanned yet, or nothing left -- returns the base
+    candidates unchanged; otherwise candidate j looks at the frontier centroid c of the block of rank j mod M'.  Yaw is the lattice
+    index in [low, up] whose angle is circularly nearest to atan2(c_y - p_y, c_x - p_x), pitch the index nearest to
+    atan2(p_z - c_z, hypot(c_x - p_x, c_y - p_y)) (camera_to_world's sign: forward = (cos p cos y, cos p sin y, -sin p)); both are an
+    argmin over the lattice angles in fp64, lowest index on ties; where the horizontal offset is zero the base yaw stays.  With
+    `radius_m` the position is replaced too: per axis the lattice index nearest to c_a plus base_a mod (2 r_a + 1) - r_a,
+    r_a = floor(radius_m / unit_a) (0 where the unit is 0), clamped to clip_pose_idx_low / up; with None the base position stays, so
+    the two sources differ in aim only.  `set_blocks` injects a block summary [N, nb^3, 4] in place of a launch (tests).  All torch
+    on the device, no host synchronisation; the pinned asynchronous copy of the base draw is LatticeCandidates' own."""
+
+    def __init__(self, cfg: TaskConfig, k: int, seed: int, frontier, range_gt: torch.Tensor, voxel_size: torch.Tensor, top: int = 8,
+                 radius_m: Optional[float] = None):
+        if int(top) < 1:
+            raise ValueError(f"FrontierCandidates: top must be >= 1, got {top}")
+        if radius_m is not None and not float(radius_m) >= 0.0:  # (a NaN fails too)
+            raise ValueError(f"FrontierCandidates: radius_m must be >= 0 or None, got {radius_m}")
+        self.cfg, self.k, self.top = cfg, int(k), int(top)
+        self.base = LatticeCandidates(cfg, k, seed)
+        self.frontier, self.range_gt, self.voxel_size = frontier, range_gt, voxel_size
+        self.radius_m = None if radius_m is None else float(radius_m)
+        self.blocks = None
+        self._consts = {}
+
+    def observe(self, tri: torch.Tensor) -> None:
+        self.blocks = self.frontier(tri)
+
+    def set_blocks(self, blocks: torch.Tensor) -> None:
+        self.blocks = blocks
+
+    def _lattice(self, device):
+        """The lattice as fp64 / int64 tensors on `device`, built once per device."""
+        c = self._consts.get(device)
+        if c is None:
+            cfg = self.cfg
+            f = lambda v: torch.tensor(v, dtype=torch.float64, device=device)  # noqa: E731
+            low_i, up_i = self.base.low.to(device), self.base.up.to(device)
+            unit, low = f(cfg.action_unit), f(cfg.clip_pose_low)
+            r = torch.zeros(3, dtype=torch.int64, device=device)
+            if self.radius_m is not None:
+                r = torch.tensor([int(self.radius_m // u) if u > 0 else 0 for u in cfg.action_unit[:3]], dtype=torch.int64, device=device)
+            angles = {ax: torch.arange(int(cfg.clip_pose_idx_low[ax]), int(cfg.clip_pose_idx_up[ax]) + 1, device=device).double() * unit[ax]
+                      + low[ax] for ax in (4, 5)}
+            c = self._consts[device] = (low_i, up_i, unit, low, r, angles, self.range_gt.to(device), self.voxel_size.to(device))
+        return c
+
+    def sample(self, num_envs: int, device="cpu") -> torch.Tensor:
+        from ..ops.frontier import block_centroids, top_blocks
+        a = self.base.sample(num_envs, device)
+        if self.blocks is None:
+            return a
+        device = a.device
+        low_i, up_i, unit, low, r, angles, range_gt, voxel_size = self._lattice(device)
+        blocks = self.blocks.to(device)
+        idx, cnt = top_blocks(blocks, min(self.top, blocks.shape[1]))
+        live = (cnt > 0).sum(dim=1)  # M' [N]: topk sorts by count, so the non-empty blocks come first
+        aimed = (live > 0)[:, None]
+        rank = torch.arange(self.k, device=device)[None] % live.clamp(min=1)[:, None]
+        cent = block_centroids(blocks, idx, range_gt, voxel_size)
+        c = cent.gather(1, rank[..., None].expand(-1, -1, 3))
+        c = torch.where(aimed[..., None], c, torch.zeros_like(c))  # (an empty block's centroid is NaN: never used, never converted)
+        pos_i = a[..., :3]
+        if self.radius_m is not None:
+            safe = torch.where(unit[:3] > 0, unit[:3], torch.ones_like(unit[:3]))
+            near = torch.where(unit[:3] > 0, torch.round((c - low[:3]) / safe), torch.zeros_like(c)).long()
+            near = torch.minimum(torch.maximum(near, low_i[:3]), up_i[:3])
+            pos_i = torch.minimum(torch.maximum(near + a[..., :3] % (2 * r + 1) - r, low_i[:3]), up_i[:3])
+        p = pos_i.double() * unit[:3] + low[:3]
+        dx, dy = c[..., 0] - p[..., 0], c[..., 1] - p[..., 1]
+        want_yaw = torch.atan2(dy, dx)
+        want_pitch = torch.atan2(p[..., 2] - c[..., 2], torch.hypot(dx, dy))
+        two_pi = 2.0 * torch.pi
+        d_yaw = (torch.remainder(angles[5] - want_yaw[..., None] + torch.pi, two_pi) - torch.pi).abs()
+        yaw = d_yaw.argmin(dim=-1) + low_i[5]  # (argmin returns the first minimum: the lowest index on ties)
+        yaw = torch.where((dx == 0) & (dy == 0), a[..., 5], yaw)
+        pitch = (angles[4] - want_pitch[..., None]).abs().argmin(dim=-1) + low_i[4]
+        out = torch.cat([pos_i, a[..., 3:4], pitch[..., None], yaw[..., None]], dim=-1)
+        return torch.where(aimed[..., None], out, a)
+
+    def poses(self, actions: torch.Tensor) -> torch.Tensor:
+        return self.base.poses(actions)
+
+
+def _candidates(cfg: TaskConfig, k: int, seed: int, look_at_scene: bool, candidates):
+    """The planners' candidate source: LatticeCandidates unless one is given, whose k must be the planner's."""
+    if candidates is None:
+        return LatticeCandidates(cfg, k, seed, look_at_scene)
+    if int(getattr(candidates, "k", -1)) != int(k):
+        raise ValueError(f"candidates.k = {getattr(candidates, 'k', None)} must equal the policy's k = {k}")
+    return candidates
+
+
 class RandomLatticePolicy:
     """A uniformly random lattice pose per env and step."""
 
@@ -108,14 +205,16 @@ class GreedyGainPolicy:
     contact buffer) counts exactly like one in contact -- that needs a collision mesh with `sweep_candidates`; where the env also
     flies detours (`env.flight`) only a candidate that no route reaches is refused for its path (`candidate_contact`).  No host
     synchronisation inside a decision.  `gain_backend(tri [N,G^3], poses [N,K,6]) -> gain [N,K,3]` replaces the kernel in
-    tests only: the product path has no CPU fallback."""
+    tests only: the product path has no CPU fallback.  `candidates` (None: LatticeCandidates(cfg, k, seed, look_at_scene)) is
+    another source with the same `k`, e.g. FrontierCandidates; if it has `observe`, it is shown the step's tri slice before
+    `sample`.  Gain, contact rule and `choose` do not depend on the source."""
 
     def __init__(self, env, k: int = 32, weights=(1, 4), seed: int = 0, stride: int = 4, avoid_collisions: bool = True,
-                 look_at_scene: bool = False, gain_backend: Optional[Callable] = None):
+                 look_at_scene: bool = False, gain_backend: Optional[Callable] = None, candidates=None):
         cfg = env.cfg
         self.env, self.cfg, self.k, self.weights = env, cfg, int(k), (int(weights[0]), int(weights[1]))
         self.num_envs = int(env.num_envs)
-        self.cands = LatticeCandidates(cfg, k, seed, look_at_scene)
+        self.cands = _candidates(cfg, k, seed, look_at_scene, candidates)
         self.avoid_collisions = bool(avoid_collisions) and getattr(env, "collision", None) is not None
         self.sweep = self.avoid_collisions and _sweeps(env)
         if self.sweep and not (hasattr(env.collision_mesh, "sweep_candidates") and hasattr(env.collision_mesh, "collide_candidates")):
@@ -132,9 +231,9 @@ class GreedyGainPolicy:
 
     def __call__(self, obs, deterministic: bool = True):
         cfg, n, k = self.cfg, self.num_envs, self.k
-        cand = self.cands.sample(n, obs.device)
-        poses = self.cands.poses(cand)
         tri = obs[:, cfg.state_dim:cfg.state_dim + cfg.grid_dim]
+        cand = self._sample(tri)
+        poses = self.cands.poses(cand)
         gain = self.gain_backend(tri, poses)
         self.last_gain = gain
         contact = None
@@ -152,6 +251,13 @@ class GreedyGainPolicy:
                 contact = self._contact.t()
         best = choose(gain, self.weights, contact)
         return cand[torch.arange(n, device=cand.device), best], None, None
+
+    def _sample(self, tri: torch.Tensor) -> torch.Tensor:
+        """The step's candidates [N,K,6]; a source with `observe` (FrontierCandidates) is shown the step's tri slice first."""
+        observe = getattr(self.cands, "observe", None)
+        if observe is not None:
+            observe(tri)
+        return self.cands.sample(self.num_envs, tri.device)
 
     def contact(self, poses: torch.Tensor) -> torch.Tensor:
         """u8 [N,K] into `self._contact`: non-zero where candidate poses [N,K,6] is refused (the hook MapGreedyPolicy replaces)."""
@@ -178,7 +284,8 @@ class MapGreedyPolicy(GreedyGainPolicy):
     penalties of the costly nodes entered -- exceeds max_cost_m.  One more query of the field, no mesh predicate."""
 
     def __init__(self, env, k: int = 32, weights=(1, 4), seed: int = 0, stride: int = 4, look_at_scene: bool = False,
-                 gain_backend: Optional[Callable] = None, shortcut: Optional[bool] = None, max_cost_m: Optional[float] = None):
+                 gain_backend: Optional[Callable] = None, shortcut: Optional[bool] = None, max_cost_m: Optional[float] = None,
+                 candidates=None):
         if max_cost_m is not None and not float(max_cost_m) > 0.0:  # (a NaN fails too)
             raise ValueError(f"MapGreedyPolicy: max_cost_m must be > 0 or None, got {max_cost_m}")
         self.max_cost_m = None if max_cost_m is None else float(max_cost_m)
@@ -190,14 +297,15 @@ class MapGreedyPolicy(GreedyGainPolicy):
             from .. import _lib
             raise _lib.GennbvHipError("MapGreedyPolicy(shortcut=True) needs BeliefFlightField(shortcut=True): the map snapshot")
         super().__init__(env, k=k, weights=weights, seed=seed, stride=stride, avoid_collisions=False, look_at_scene=look_at_scene,
-                         gain_backend=gain_backend)
+                         gain_backend=gain_backend, candidates=candidates)
         self.avoid_collisions = True  # by the map: `contact` below; `sweep` stays off, no mesh predicate is launched
 
     def __call__(self, obs, deterministic: bool = True):
         cfg, n = self.cfg, self.num_envs
-        cand = self.cands.sample(n, obs.device)
+        tri = obs[:, cfg.state_dim:cfg.state_dim + cfg.grid_dim]
+        cand = self._sample(tri)
         poses = self.cands.poses(cand)
-        gain = self.gain_backend(obs[:, cfg.state_dim:cfg.state_dim + cfg.grid_dim], poses)
+        gain = self.gain_backend(tri, poses)
         self.last_gain = gain
         if self._contact is None:
             self._contact = torch.zeros(n, self.k, dtype=torch.uint8, device=obs.device)

@@ -430,6 +430,27 @@ int gnbv_sweep_tri(const int8_t *tri_i8 /*[N, >= G^3] or NULL*/, int64_t tri_i8_
                    int64_t to_row_stride /*floats*/, double radius, int unknown_blocks, int outside_blocks, int ground,
                    uint8_t *code_out /*[N,K]*/, int mode, void *stream);
 
+/* The frontier of the scanned map (an additive entry point of ABI 5; csrc/frontier.hip): the boundary between what each env's
+ * tri-class grid knows to be free and what it does not know.  The grid forms (exactly one of tri_i8 / tri_f32, row stride in bytes /
+ * floats), the signs (< 0 free, 0 unknown, > 0 occupied) and the voxel order (x G + y) G + z are those of gnbv_flight_blocked_tri.
+ * Voxel (x, y, z) of env e is a frontier voxel iff its class is unknown and at least one of its six face neighbours that lie inside
+ * the grid is free; a neighbour outside the grid is no neighbour (the voxel that follows (x, y, G - 1) in memory is not its
+ * z-neighbour).  Integers only: one right answer.
+ *   bits_out   [N, ceil(G^3 / 32)] u32 or NULL: bit vox & 31 of word vox >> 5, unswizzled; every word written, padding bits clear.
+ *   blocks_out [N, nb^3, 4] int32, nb = ceil(G / block): the record of block (bx nb + by) nb + bz covers the voxels with
+ *              x / block == bx, y / block == by, z / block == bz and holds {count, sum x, sum y, sum z} over its frontier voxels;
+ *              every record written, zeros where empty.  The frontier count of an env is the sum of its records' counts.
+ * One launch over workgroups (env, slab of x-planes); `slab` is the slab height in planes, 0 = auto; a given height is rounded up
+ * to a multiple of `block` and lowered to what the two LDS bit planes admit ((slab + 2) G^2 / 4 bytes).  The result is the same for
+ * every slab.  One writer per output word and per record, no atomics, no workspace, no allocation, no host synchronisation; every
+ * loop is bounded by a function of G and compile-time constants whatever the device arrays hold.  hipErrorInvalidValue before any
+ * launch for: both or neither grid form, a NULL blocks_out, n < 1, G outside 1..128, block outside 1..16, a row stride below G^3,
+ * slab < 0. */
+int gnbv_frontier_tri(const int8_t *tri_i8 /*[N, >= G^3] or NULL*/, int64_t tri_i8_row_stride /*bytes*/,
+                      const float *tri_f32 /*[N, >= G^3] or NULL*/, int64_t tri_f32_row_stride /*floats*/, int g, int n, int block,
+                      uint32_t *bits_out /*[N,ceil(G^3/32)] or NULL*/, int32_t *blocks_out /*[N,nb^3,4]*/, int slab /*0 = auto*/,
+                      void *stream);
+
 /* compute_reward (env_train_base.py:377-398), _reward_* / check_termination /
  * reset_idx (env_train_gennbv.py:377-457,535-556), update_extra_episode_info
  * (env_train_base.py:629-639). All pointers device, arrays [N] unless noted. [host struct] */
