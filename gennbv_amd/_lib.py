@@ -71,6 +71,8 @@ SIGNATURES = {
     "gnbv_sweepmap_lds_max_grid": (_i, []),
     "gnbv_sweep_tri": (_i, [_p, _i64, _p, _i64, _i, _p, _p, _i, _p, _i64, _i64, _p, _i, _i64, _d, _i, _i, _i, _p, _i, _p]),
     "gnbv_frontier_tri": (_i, [_p, _i64, _p, _i64, _i, _i, _i, _p, _p, _i, _p]),
+    "gnbv_frontview_lds_max_grid": (_i, []),
+    "gnbv_frontier_viewpoints": (_i, [_p, _p]),
     "gnbv_rollout_add": (_i, [_i, _i, _p, _p, _p, _p, _i, _f, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "gnbv_input_autocorr_row_ints": (_i, []),
     "gnbv_input_autocorr": (_i, [_p, _i64, _i, _i, _p, _i64, _p]),
@@ -169,6 +171,14 @@ class GnbvViewGain(C.Structure):
     _fields_ = [("n", _i), ("k", _i), ("g", _i), ("tri_i8", _p), ("tri_row_stride", _i64), ("poses", _p), ("range_gt", _p),
                 ("voxel_size", _p), ("inv_intri", _p), ("h", _i), ("w", _i), ("stride", _i), ("range", _f), ("gain", _p),
                 ("c2w_out", _p), ("chunk", _i), ("ablate", _i)]
+
+
+class GnbvFrontView(C.Structure):
+    """include/gennbv_hip.h: GnbvFrontView"""
+    _fields_ = [("n", _i), ("t", _i), ("g", _i), ("tri_i8", _p), ("tri_i8_row_stride", _i64), ("tri_f32", _p),
+                ("tri_f32_row_stride", _i64), ("range_gt", _p), ("voxel_size", _p), ("nx", _i), ("ny", _i), ("nz", _i),
+                ("lo", _d * 3), ("h", _d * 3), ("field", _p), ("targets", _p), ("r_min", _d), ("r_max", _d), ("max_unknown", _i),
+                ("node_out", _p), ("cost_out", _p), ("count_out", _p), ("chunk", _i), ("mode", _i)]
 
 
 class GnbvViewCover(C.Structure):

@@ -3,7 +3,8 @@ next-best-view planner over the view gain (ops/view_gain.py, csrc/viewgain.hip; 
 oracle over the view coverage (ops/view_cover.py, csrc/viewcover.hip): the candidate that really adds the most
 ground-truth voxels, and the greedy set-cover planner over a fixed pool of views whose visible ground truth is cached
 as bit masks (ops/view_pool.py, csrc/covergreedy.hip) -- online, or as the plan-then-fly baseline: the set-cover plan ordered
-into a short flight tour (ops/tour.py, csrc/tour.hip) and flown by TourPolicy.
+into a short flight tour (ops/tour.py, csrc/tour.hip) and flown by TourPolicy.  FrontierViewPolicy is the nearest-frontier
+baseline of the pilot that knows only its own map (ops/frontier_view.py, csrc/frontview.hip).
 
 All speak the protocol `evaluate_policy_grid_obs` uses: `.policy(obs, deterministic=True) -> (actions, None, None)`,
 and `predict(obs)`; actions are int64 [N,6] on the lattice of the task (inside clip_pose_idx_low / clip_pose_idx_up).
@@ -100,6 +101,7 @@ class FrontierCandidates:
 
     def sample(self, num_envs: int, device="cpu") -> torch.Tensor:
         from ..ops.frontier import block_centroids, top_blocks
+        from ..ops.frontier_view import aim_indices
         a = self.base.sample(num_envs, device)
         if self.blocks is None:
             return a
@@ -120,14 +122,7 @@ class FrontierCandidates:
             near = torch.minimum(torch.maximum(near, low_i[:3]), up_i[:3])
             pos_i = torch.minimum(torch.maximum(near + a[..., :3] % (2 * r + 1) - r, low_i[:3]), up_i[:3])
         p = pos_i.double() * unit[:3] + low[:3]
-        dx, dy = c[..., 0] - p[..., 0], c[..., 1] - p[..., 1]
-        want_yaw = torch.atan2(dy, dx)
-        want_pitch = torch.atan2(p[..., 2] - c[..., 2], torch.hypot(dx, dy))
-        two_pi = 2.0 * torch.pi
-        d_yaw = (torch.remainder(angles[5] - want_yaw[..., None] + torch.pi, two_pi) - torch.pi).abs()
-        yaw = d_yaw.argmin(dim=-1) + low_i[5]  # (argmin returns the first minimum: the lowest index on ties)
-        yaw = torch.where((dx == 0) & (dy == 0), a[..., 5], yaw)
-        pitch = (angles[4] - want_pitch[..., None]).abs().argmin(dim=-1) + low_i[4]
+        pitch, yaw = aim_indices(p, c, angles[4], angles[5], low_i[4], low_i[5], a[..., 5])
         out = torch.cat([pos_i, a[..., 3:4], pitch[..., None], yaw[..., None]], dim=-1)
         return torch.where(aimed[..., None], out, a)
 
@@ -321,6 +316,115 @@ class MapGreedyPolicy(GreedyGainPolicy):
             cost = fl.cost(poses)
             refused |= torch.isfinite(cost) & (cost > self.max_cost_m)
         return self._contact.copy_(refused)
+
+
+class FrontierViewPolicy:
+    """The nearest-frontier baseline for the pilot that knows only its own map (Yamauchi's rule on the flight lattice): go to the
+    cheapest lattice node that sees a frontier block on the map, and look at the block.  No mesh is consulted.
+
+    Per decision: the tri slice goes to `frontier` (ops/frontier.py Frontier; None builds one with `block`) for the block records.
+    A block is ELIGIBLE iff its count is > 0 and differs from `tried_count` [N, nb^3] int32 -- the count it had when this env last
+    targeted it, -1 = never: the updater carves only along rays that hit foreground, so a frontier facing the sky never resolves,
+    and a nearest-frontier rule without memory returns to it forever.  The `top` fullest eligible blocks (top_blocks' key over the
+    masked counts: ties to the lowest block index) give the targets (block_target_voxels: the voxel holding the block's frontier
+    centroid); one FrontierViewpoints launch (ops/frontier_view.py, csrc/frontview.hip) against env.flight.field gives each
+    target's cheapest node in [r_min_m, r_max_m] with a line of sight that crosses at most `max_unknown` unknown voxels (None:
+    `block` -- a block's centroid voxel need not itself border free space; a stated choice, nobody has measured it).  Among the
+    targets with a node the winner maximises the int64 score count * voxel_value_mm - cost_mm (voxel_value_mm = 0: the nearest
+    frontier), ties to the lowest rank by a distinct key as `choose` builds one.  The action: the node's position (node_actions),
+    roll index 0, pitch and yaw aimed at the block's fp64 centroid (aim_indices; where the node is straight above or below it the
+    fallback's yaw stays); the winner's count goes to `tried_count`.  Envs without a winner -- nothing scanned yet, the frontier
+    exhausted, every frontier tried -- take the action of `fallback` (any policy of this protocol), which is evaluated for all envs
+    and selected with torch.where.  `tried_count` rows reset where env.episode_length_buf == 0.  No host synchronisation in the
+    policy's own part of a decision (what the fallback does is the fallback's).  `last_node` [N] int64 (-1 on a fallback row), `last_cost_mm` [N] int64, `last_count` [N] int64 and `fell_back`
+    [N] bool describe the last decision.  `view_backend(tri, field, target_vox) -> (node, cost_mm, count)` replaces the kernel in
+    tests only, as does a callable `frontier(tri) -> blocks`: the product path has no CPU fallback."""
+
+    def __init__(self, env, fallback, top: int = 8, block: int = 4, *, r_min_m: float, r_max_m: float, max_unknown: Optional[int] = None,
+                 voxel_value_mm: int = 0, frontier=None, view_backend: Optional[Callable] = None):
+        from ..ops.frontier import block_grid
+        flight = getattr(env, "flight", None)
+        if not getattr(flight, "belief", False):
+            from .. import _lib
+            raise _lib.GennbvHipError("FrontierViewPolicy needs an env whose flight is a BeliefFlightField")
+        cfg = env.cfg
+        g, n = int(cfg.grid_size), int(env.num_envs)
+        if int(block) < 1 or int(voxel_value_mm) < 0:
+            raise ValueError(f"FrontierViewPolicy: block >= 1 and voxel_value_mm >= 0, got {block}, {voxel_value_mm}")
+        nblk = block_grid(g, block) ** 3
+        if not 1 <= int(top) <= nblk:
+            raise ValueError(f"FrontierViewPolicy: top must be in 1..{nblk}, got {top}")
+        self.env, self.cfg, self.num_envs, self.fallback = env, cfg, n, fallback
+        self.top, self.block, self.voxel_value_mm = int(top), int(block), int(voxel_value_mm)
+        self.max_unknown = int(block) if max_unknown is None else int(max_unknown)
+        self.r_min_m, self.r_max_m = float(r_min_m), float(r_max_m)
+        device = torch.device(env.device)
+        if frontier is None:
+            from ..ops.frontier import Frontier
+            frontier = Frontier(n, g, block=self.block, device=device)
+        self.frontier = frontier
+        if view_backend is None:
+            from ..ops.frontier_view import FrontierViewpoints
+            view_backend = FrontierViewpoints(n, g, flight.lattice, flight.range_gt, flight.voxel_size, self.top, self.r_min_m,
+                                              self.r_max_m, max_unknown=self.max_unknown, device=device)
+        self.view_backend = view_backend
+        self.range_gt, self.voxel_size = flight.range_gt, flight.voxel_size
+        self.tried_count = torch.full((n, nblk), -1, dtype=torch.int32, device=device)
+        f = lambda v: torch.tensor(v, dtype=torch.float64, device=device)  # noqa: E731
+        self._unit, self._low = f(cfg.action_unit), f(cfg.clip_pose_low)
+        self._low_i = torch.tensor(cfg.clip_pose_idx_low, dtype=torch.int64, device=device)
+        self._angles = {ax: torch.arange(int(cfg.clip_pose_idx_low[ax]), int(cfg.clip_pose_idx_up[ax]) + 1, device=device).double()
+                        * self._unit[ax] + self._low[ax] for ax in (4, 5)}
+        self._roll = min(max(0, int(cfg.clip_pose_idx_low[3])), int(cfg.clip_pose_idx_up[3]))
+        self._rank_key = self.top - 1 - torch.arange(self.top, device=device)
+        self._rows = torch.arange(n, device=device)
+        self.last_node = self.last_cost_mm = self.last_count = self.fell_back = None
+
+    def __call__(self, obs, deterministic: bool = True):
+        from ..ops.frontier import block_centroids, top_blocks
+        from ..ops.frontier_view import aim_indices, block_target_voxels, node_actions
+        cfg, rows = self.cfg, self._rows
+        tri = obs[:, cfg.state_dim:cfg.state_dim + cfg.grid_dim]
+        fb = self.fallback(obs, deterministic)[0].to(torch.int64)
+        blocks = self.frontier(tri)
+        count = blocks[..., 0]
+        fresh = (self.env.episode_length_buf == 0)[:, None]
+        tried = torch.where(fresh, torch.full_like(self.tried_count, -1), self.tried_count)
+        eligible = (count > 0) & (count != tried)
+        masked = blocks.clone()
+        masked[..., 0] = torch.where(eligible, count, torch.zeros_like(count))
+        idx, cnt = top_blocks(masked, self.top)  # cnt: 0 where the rank holds no eligible block
+        vox = block_target_voxels(masked, idx)   # (-1 there: no target)
+        node, cost, _ = self.view_backend(tri, self.env.flight, vox)
+        cost = cost.to(torch.int64) & 0xFFFFFFFF
+        valid = (node >= 0) & (cnt > 0)
+        # one key per rank, strictly larger for the lower rank at equal score: argmax has a single answer
+        score = cnt * self.voxel_value_mm - cost
+        key = torch.where(valid, score * self.top + self._rank_key, torch.full_like(score, torch.iinfo(torch.int64).min))
+        best = key.argmax(dim=1)
+        has = valid.any(dim=1)
+        blk, won, n_best = idx[rows, best], cnt[rows, best], node[rows, best].to(torch.int64)
+        pos_i = node_actions(self.env.flight.lattice, cfg, n_best)
+        cent = block_centroids(blocks, blk[:, None], self.range_gt, self.voxel_size)[:, 0]
+        cent = torch.where(has[:, None], cent, torch.zeros_like(cent))  # (an empty block's centroid is NaN: never used)
+        p = pos_i.double() * self._unit[:3] + self._low[:3]
+        pitch, yaw = aim_indices(p, cent, self._angles[4], self._angles[5], self._low_i[4], self._low_i[5], fb[:, 5])
+        act = torch.cat([pos_i, torch.full_like(pitch, self._roll)[:, None], pitch[:, None], yaw[:, None]], dim=-1)
+        old = tried[rows, blk]
+        self.tried_count.copy_(tried)
+        self.tried_count[rows, blk] = torch.where(has, won.to(torch.int32), old)
+        self.fell_back = ~has
+        self.last_node = torch.where(has, n_best, torch.full_like(n_best, -1))
+        self.last_cost_mm = torch.where(has, cost[rows, best], torch.full_like(n_best, 0xFFFFFFFF))
+        self.last_count = torch.where(has, won, torch.zeros_like(won))
+        return torch.where(has[:, None], act, fb), None, None
+
+    @property
+    def policy(self):
+        return self
+
+    def predict(self, obs, state=None, episode_start=None, deterministic: bool = True):
+        return self(obs, deterministic)[0], state
 
 
 class OracleGainPolicy:

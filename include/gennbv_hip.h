@@ -451,6 +451,59 @@ int gnbv_frontier_tri(const int8_t *tri_i8 /*[N, >= G^3] or NULL*/, int64_t tri_
                       uint32_t *bits_out /*[N,ceil(G^3/32)] or NULL*/, int32_t *blocks_out /*[N,nb^3,4]*/, int slab /*0 = auto*/,
                       void *stream);
 
+/* Frontier viewpoints (an additive entry point of ABI 5; csrc/frontview.hip): for T target voxels per env, which node of the flight
+ * lattice sees the target on the scanned map, and which of those is cheapest to fly to.  The grid forms (exactly one of tri_i8 /
+ * tri_f32, row stride in bytes / floats), the signs (< 0 free, 0 unknown, > 0 occupied), the voxel order (x G + y) G + z and the
+ * voxel frame are those of gnbv_flight_blocked_tri; the lattice (nx, ny, nz, lo, h; node c = (k ny + j) nx + i) and `field` [N, M]
+ * u32 (0xFFFFFFFF = no route; any table in that layout) are those of gnbv_flight_field / _w; the ray rule is gnbv_view_gain's.
+ * Integers and fp64 in a stated order: one right answer.  For env e and target j = (tx, ty, tz) of targets [N, T, 3] int32:
+ *   voxel frame: v_a = (double)voxel_size[a], o_a = (double)fp32(range_gt[2a+1] - fp32(0.5f * voxel_size[a])); the target point is
+ *     q_a = o_a + ((double)t_a + 0.5) * v_a.  A target with any coordinate outside [0, G) is NO TARGET.
+ *   distance: node c sits at p_a = lo_a + h_a * idx_a (fp64); d2 = ((p_x - q_x)^2 + (p_y - q_y)^2) + (p_z - q_z)^2 in this
+ *     operation order, without FMA; the node is IN RANGE iff r_min * r_min <= d2 <= r_max * r_max.
+ *   line of sight: the source voxel is gnbv_pose_to_idx((float)p_x, (float)p_y, (float)p_z), unclamped (voxel coordinates beyond
+ *     +-2^24 saturate there); the line is gnbv_bresenham3d's from the source to the target (not symmetric: source first); its
+ *     in-grid voxels in order are w_0 .. w_L, w_L the target.  The node SEES the target iff none of w_0 .. w_{L-1} is occupied and
+ *     at most max_unknown of them are unknown.  The class of the target voxel itself is not looked at; L = 0 sees it.
+ *   node_out  [N,T] int32:   among the nodes in range that see the target and have field[e, c] != 0xFFFFFFFF, the one with the
+ *                            smallest (field[e, c], c) in lexicographic order; -1 where there is none, or no target.
+ *   cost_out  [N,T] u32:     its field value; 0xFFFFFFFF where node_out is -1.
+ *   count_out [N,T,2] int32: {nodes in range that see the target, of which with a route}.
+ * Every element of the three outputs is written.  The result is defined over all M nodes; the kernel visits the index window
+ * round the target that |p_a - q_a| <= r_max admits, one node wider on both sides and wider still by 2^-48 of the magnitudes
+ * involved over h_a (the rounding of p_a and of the window's own arithmetic), clamped to the lattice in fp64.
+ * mode: 0 auto (2 at every G: measured faster than 1 at every size tried), 1 the grid's classes packed into two LDS bit planes per
+ * workgroup (hipErrorInvalidValue where G > gnbv_frontview_lds_max_grid()), 2 the grid read in place; the result is the same.  chunk: targets per
+ * workgroup, 0 = chosen from n and t; any value gives the same result.  One launch, one writer per output element, no global
+ * atomics, no workspace, no allocation, no host synchronisation; every loop is bounded by a function of G, the lattice dimensions
+ * and compile-time constants whatever field, targets and the grid hold.  hipErrorInvalidValue before any launch for: both or
+ * neither grid form, a NULL required pointer, n < 1, t < 1, N * T > 2^31 - 1, G outside 1..128, a row stride below G^3, a lattice
+ * axis outside 1..1024, lo / h not finite or h <= 0 on an axis with more than one node, r_min / r_max not finite, r_min < 0,
+ * r_max <= 0, r_min > r_max, max_unknown < 0, chunk < 0, a mode outside 0..2, mode 1 above its limit.
+ * [host struct]; pointers are device unless noted. */
+typedef struct GnbvFrontView {
+    int n, t, g;                    /* envs, targets per env, grid edge */
+    const int8_t *tri_i8;           /* [n, >= g^3] or NULL; row stride in bytes */
+    int64_t tri_i8_row_stride;
+    const float *tri_f32;           /* [n, >= g^3] or NULL; row stride in floats */
+    int64_t tri_f32_row_stride;
+    const float *range_gt;          /* [n, 6] */
+    const float *voxel_size;        /* [n, 3] */
+    int nx, ny, nz;                 /* the flight lattice */
+    double lo[3], h[3];
+    const uint32_t *field;          /* [n, nx ny nz] */
+    const int32_t *targets;         /* [n, t, 3] voxel coordinates */
+    double r_min, r_max;            /* metres */
+    int max_unknown;
+    int32_t *node_out;              /* [n, t] */
+    uint32_t *cost_out;             /* [n, t] */
+    int32_t *count_out;             /* [n, t, 2] */
+    int chunk;                      /* targets per workgroup, 0 = auto */
+    int mode;                       /* 0 auto, 1 LDS bit planes, 2 the grid in place */
+} GnbvFrontView;
+int gnbv_frontview_lds_max_grid(void); /* the largest G of mode 1: 86 */
+int gnbv_frontier_viewpoints(const GnbvFrontView *args /*[host]*/, void *stream);
+
 /* compute_reward (env_train_base.py:377-398), _reward_* / check_termination /
  * reset_idx (env_train_gennbv.py:377-457,535-556), update_extra_episode_info
  * (env_train_base.py:629-639). All pointers device, arrays [N] unless noted. [host struct] */
