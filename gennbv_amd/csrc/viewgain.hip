@@ -22,6 +22,12 @@
 //        global atomics, every output is written once by one lane: deterministic;
 //     5. the workgroup clears both masks (16-byte stores) before the next candidate.
 //
+//   k_view_gain<true>   (gnbv_view_gain_masks) the same kernel, but the two visited masks are kept: after the barrier of step 4
+//     every lane copies 16-byte pieces of s_a / s_b to the candidate's rows of unknown_bits / hit_bits (lane i holds quad i:
+//     conflict-free 16-byte LDS reads, 1 KiB of consecutive addresses per wave store), zeroes the row's pad words and clears
+//     the LDS words it has just read -- store-and-clear replaces step 5 and also runs for the chunk's last candidate.  The
+//     workgroup owns its candidates' rows: no atomics.  k_view_gain<false> is the kernel gnbv_view_gain always launched.
+//
 //   k_vg_prep, k_vg_fate, k_vg_slab   the same integers for grids up to 128^3 (gnbv_view_gain_slab): further down.
 #include <cmath>
 
@@ -50,6 +56,9 @@ struct VgParams {
     int32_t *gain;
     float *c2w_out;
     int grid_words, mask_words, ablate;
+    // k_view_gain<true> only
+    uint32_t *unknown_bits, *hit_bits;  // [n, k, words] rows, 16-byte aligned, either may be NULL
+    int words;                          // a multiple of 4, >= mask_words
 };
 
 __device__ __forceinline__ uint32_t pack_codes4(uint32_t bytes4)
@@ -80,6 +89,7 @@ __device__ __forceinline__ uint32_t pack_word(const int8_t *row, int w, int g3, 
     return code;
 }
 
+template <bool MASKS>
 __global__ __launch_bounds__(kMaxThreads) void k_view_gain(VgParams p)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t s_mem[];
@@ -182,8 +192,29 @@ __global__ __launch_bounds__(kMaxThreads) void k_view_gain(VgParams p)
         }
         // ---- 5. clear the masks for the next candidate (ordered in front of its rays by the barrier at the loop's head;
         //         lane 0 reads s_part before it arrives there, the waves write it after)
-        if (j + 1 < j1 && mark)
-            for (int w = tid; w < mask_quads; w += nthreads) s_masks4[w] = make_uint4(0u, 0u, 0u, 0u);
+        if constexpr (MASKS) {
+            // store, then clear: a lane clears the quads it stored, so no barrier between the two.  Every word of the row is
+            // written: mask_words from LDS (the bits at and past g^3 were never set), zeros from there to `words`.
+            const size_t off = ((size_t)e * p.k + j) * (size_t)p.words;
+            uint4 *ga = p.unknown_bits != nullptr ? reinterpret_cast<uint4 *>(p.unknown_bits + off) : nullptr;
+            uint4 *gb = p.hit_bits != nullptr ? reinterpret_cast<uint4 *>(p.hit_bits + off) : nullptr;
+            const int row_quads = p.mask_words / 4, all_quads = p.words / 4;
+            const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
+            for (int w = tid; w < all_quads; w += nthreads) {
+                if (w < row_quads) {
+                    if (ga != nullptr) ga[w] = s_masks4[w];
+                    if (gb != nullptr) gb[w] = s_masks4[row_quads + w];
+                    s_masks4[w] = zero;
+                    s_masks4[row_quads + w] = zero;
+                } else {
+                    if (ga != nullptr) ga[w] = zero;
+                    if (gb != nullptr) gb[w] = zero;
+                }
+            }
+        } else {
+            if (j + 1 < j1 && mark)
+                for (int w = tid; w < mask_quads; w += nthreads) s_masks4[w] = make_uint4(0u, 0u, 0u, 0u);
+        }
     }
 }
 
@@ -494,12 +525,20 @@ static bool view_gain_args_ok(const GnbvViewGain &a, int max_grid)
            a.tri_row_stride >= (int64_t)a.g * a.g * a.g;
 }
 
-GNBV_API int gnbv_view_gain(const GnbvViewGain *args, void *stream)
+// gnbv_view_gain (MASKS false: the mask arguments are not looked at) and gnbv_view_gain_masks
+template <bool MASKS>
+static int view_gain_impl(const GnbvViewGain *args, int words, int32_t *unknown_bits, int32_t *hit_bits, void *stream)
 {
     GNBV_CHECK_ARG(args != nullptr);
     const GnbvViewGain a = *args;
     GNBV_CHECK_ARG(view_gain_args_ok(a, kMaxGrid));
     const int g3 = a.g * a.g * a.g;
+    if (MASKS) {
+        GNBV_CHECK_ARG(a.ablate == 0 && (unknown_bits != nullptr || hit_bits != nullptr));
+        GNBV_CHECK_ARG(words > 0 && (words & 3) == 0 && words >= (g3 + 31) / 32);
+        GNBV_CHECK_ARG((((uintptr_t)unknown_bits | (uintptr_t)hit_bits) & 15) == 0);
+        GNBV_CHECK_ARG((int64_t)a.n * a.k * words <= 0x7fffffff);
+    }
     VgParams p;
     p.n = a.n; p.k = a.k; p.g = a.g;
     // candidates per workgroup: enough workgroups for two per compute unit, but the grid is packed once per workgroup
@@ -528,6 +567,9 @@ GNBV_API int gnbv_view_gain(const GnbvViewGain *args, void *stream)
     p.grid_words = (((g3 + 15) / 16) + 3) & ~3;
     p.mask_words = (((g3 + 31) / 32) + 3) & ~3;
     p.ablate = a.ablate;
+    p.unknown_bits = MASKS ? reinterpret_cast<uint32_t *>(unknown_bits) : nullptr;
+    p.hit_bits = MASKS ? reinterpret_cast<uint32_t *>(hit_bits) : nullptr;
+    p.words = MASKS ? words : 0;
     const size_t lds = (size_t)(p.grid_words + 2 * p.mask_words) * sizeof(uint32_t);
     // one ray per lane; a workgroup whose LDS leaves room for several per compute unit stays at 256 lanes
     int threads = ((p.nrays > 0 ? p.nrays : 1) + kWave - 1) / kWave * kWave;
@@ -535,10 +577,20 @@ GNBV_API int gnbv_view_gain(const GnbvViewGain *args, void *stream)
     threads = threads > cap ? cap : threads;
     // (per call: the attribute belongs to the current device's copy of the kernel)
     if (lds > 64 * 1024 &&
-        hipFuncSetAttribute((const void *)k_view_gain, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        hipFuncSetAttribute((const void *)k_view_gain<MASKS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return (int)hipGetLastError();
-    hipLaunchKernelGGL(k_view_gain, dim3((unsigned)(a.n * p.chunks)), dim3(threads), lds, gnbv_stream(stream), p);
+    hipLaunchKernelGGL(k_view_gain<MASKS>, dim3((unsigned)(a.n * p.chunks)), dim3(threads), lds, gnbv_stream(stream), p);
     return gnbv_launch_status();
+}
+
+GNBV_API int gnbv_view_gain(const GnbvViewGain *args, void *stream)
+{
+    return view_gain_impl<false>(args, 0, nullptr, nullptr, stream);
+}
+
+GNBV_API int gnbv_view_gain_masks(const GnbvViewGain *args, int words, int32_t *unknown_bits, int32_t *hit_bits, void *stream)
+{
+    return view_gain_impl<true>(args, words, unknown_bits, hit_bits, stream);
 }
 
 GNBV_API size_t gnbv_view_gain_slab_workspace_bytes(int n, int k, int g, int h, int w, int stride)

@@ -4,7 +4,8 @@ oracle over the view coverage (ops/view_cover.py, csrc/viewcover.hip): the candi
 ground-truth voxels, and the greedy set-cover planner over a fixed pool of views whose visible ground truth is cached
 as bit masks (ops/view_pool.py, csrc/covergreedy.hip) -- online, or as the plan-then-fly baseline: the set-cover plan ordered
 into a short flight tour (ops/tour.py, csrc/tour.hip) and flown by TourPolicy.  FrontierViewPolicy is the nearest-frontier
-baseline of the pilot that knows only its own map (ops/frontier_view.py, csrc/frontview.hip).
+baseline of the pilot that knows only its own map (ops/frontier_view.py, csrc/frontview.hip); MapCoverPolicy plans several
+views ahead on that map: greedy set cover over the view gain's voxel masks (ops/gain_masks.py), optionally routed into a tour.
 
 All speak the protocol `evaluate_policy_grid_obs` uses: `.policy(obs, deterministic=True) -> (actions, None, None)`,
 and `predict(obs)`; actions are int64 [N,6] on the lattice of the task (inside clip_pose_idx_low / clip_pose_idx_up).
@@ -316,6 +317,122 @@ class MapGreedyPolicy(GreedyGainPolicy):
             cost = fl.cost(poses)
             refused |= torch.isfinite(cost) & (cost > self.max_cost_m)
         return self._contact.copy_(refused)
+
+
+class MapCoverPolicy(MapGreedyPolicy):
+    """Planning ahead on the map: `horizon` views per plan that add DIFFERENT unknown voxels, for the pilot that knows only its own
+    map -- the map-only counterpart of PoolCoverPolicy.plan_route / TourPolicy.  MapGreedyPolicy's constructor checks, candidate
+    source (with the `observe` hook) and `contact(poses)` are reused as they are: a candidate is refused iff the belief field holds
+    no route to it, tightened by `shortcut` / `max_cost_m` as documented there.  No mesh predicate is launched anywhere.
+
+    A decision:
+      1. plan: K candidates, their poses, ViewGainMasks(tri, poses) (ops/gain_masks.py: the view gain and its two voxel sets as bit
+         masks) and `plan(horizon, which=mask, contact=self.contact(poses))`, greedy set cover from an empty covered set -- the
+         masks hold only voxels that are unknown NOW;
+      2. keep the rounds with gain > 0 whose choice is not refused, in plan order (a repeat has gain 0: the kept views are
+         distinct); `views` [N] is their number; an env with none takes round 0's choice -- candidate 0 when all are refused
+         (gnbv_cover_greedy's rule), exactly MapGreedyPolicy's fallback;
+      3. order (`route`, horizon > 1): the points env.poses[:, :3] and the kept views' positions, legs from
+         env.flight.pairwise_mm, order from route_tour, as PoolCoverPolicy.plan_route; a kept view no route reaches from the start
+         is left out.  Without `route` the order is the plan's gain order;
+      4. adopt: the new plan replaces env e's stored plan (`plan_actions` [N,horizon,6], `plan_views` [N], `cursor` [N]) where
+         env.episode_length_buf[e] <= 1, where its cursor has reached min(commit, plan_views[e]), or where its stored plan is
+         empty; elsewhere the stored plan continues;
+      5. act: plan_actions[e, cursor[e]], and the cursor advances.
+    The plan is computed for ALL envs at EVERY decision and selected with torch.where: an env that restarts mid-plan must not fly
+    a tour planned on the previous episode's map, and finding out on the host which envs need a plan would synchronise.  The
+    policy's own part of a decision reads no per-env state on the host (`contact` is MapGreedyPolicy's).
+    commit = 1 is receding-horizon control: fly the first view of a plan whose views do not overlap, then plan again.
+    commit = horizon with `route` is plan-then-fly on the map.  horizon = 1 chooses what MapGreedyPolicy chooses with weights
+    (1, 0) for mask "unknown" and (0, 1) for mask "hit".
+    The last decision's plan, for every env whether adopted or not: `last_choice`, `last_gain` int32 [N,horizon] (the plan's
+    integers, gain order), `last_views` int64 [N], `last_actions` int64 [N,horizon,6] (the views in flight order; the tail repeats
+    the last), `last_length_mm` int64 [N] (the tour from env.poses; -1 without route), `last_gain3` [N,K,3] (the view gain),
+    `adopted` bool [N].  `masks_backend` (an object with ViewGainMasks' `__call__` and `plan`) and `tour_backend`
+    (`route_tour`'s signature) replace the kernels in tests only: the product path has no CPU fallback."""
+
+    def __init__(self, env, k: int = 32, horizon: int = 3, commit: int = 1, mask: str = "hit", route: bool = False, seed: int = 0,
+                 stride: int = 4, look_at_scene: bool = False, shortcut: Optional[bool] = None, max_cost_m: Optional[float] = None,
+                 candidates=None, masks_backend=None, tour_backend: Optional[Callable] = None):
+        horizon, commit = int(horizon), int(commit)
+        if not 1 <= horizon <= 16:
+            raise ValueError(f"MapCoverPolicy: horizon must be in 1..16, got {horizon}")
+        if not 1 <= commit <= horizon:
+            raise ValueError(f"MapCoverPolicy: commit must be in 1..horizon = {horizon}, got {commit}")
+        if mask not in ("hit", "unknown"):
+            raise ValueError(f"MapCoverPolicy: mask must be 'hit' or 'unknown', got {mask!r}")
+        if masks_backend is None:
+            from ..ops.gain_masks import ViewGainMasks
+            u = env.updater
+            masks_backend = ViewGainMasks(int(env.num_envs), int(k), env.cfg, u.range_gt, u.voxel_size_gt, inv_intrinsics=u.inv_intri_host,
+                                          stride=stride, device=env.device, hit=mask == "hit", unknown=mask == "unknown")
+        super().__init__(env, k=k, weights=(1, 0) if mask == "unknown" else (0, 1), seed=seed, stride=stride, look_at_scene=look_at_scene,
+                         gain_backend=masks_backend, shortcut=shortcut, max_cost_m=max_cost_m, candidates=candidates)
+        self.horizon, self.commit, self.mask, self.route = horizon, commit, mask, bool(route)
+        self.tour_backend = tour_backend
+        n, dev = self.num_envs, torch.device(env.device)
+        self.plan_actions = torch.zeros(n, horizon, 6, dtype=torch.int64, device=dev)
+        self.plan_views = torch.zeros(n, dtype=torch.int64, device=dev)
+        self.cursor = torch.zeros(n, dtype=torch.int64, device=dev)
+        self._rows = torch.arange(n, device=dev)
+        self._slots = torch.arange(horizon, device=dev)[None]
+        self._points = torch.empty(n, horizon + 1, 3, dtype=torch.float32, device=dev)
+        self._no_length = torch.full((n,), -1, dtype=torch.int64, device=dev)
+        self.last_choice = self.last_gain = self.last_views = self.last_actions = self.last_length_mm = self.last_gain3 = self.adopted = None
+
+    def __call__(self, obs, deterministic: bool = True):
+        cfg, n, t_max = self.cfg, self.num_envs, self.horizon
+        env, rows, slots = self.env, self._rows, self._slots
+        # ---- 1. plan
+        tri = obs[:, cfg.state_dim:cfg.state_dim + cfg.grid_dim]
+        cand = self._sample(tri)
+        poses = self.cands.poses(cand)
+        self.last_gain3 = self.gain_backend(tri, poses)
+        if self._contact is None:
+            self._contact = torch.zeros(n, self.k, dtype=torch.uint8, device=obs.device)
+        contact = self.contact(poses)
+        choice, gain, _ = self.gain_backend.plan(t_max, which=self.mask, contact=contact)
+        self.last_choice, self.last_gain = choice, gain
+        choice64 = choice.long()
+        # ---- 2. keep: the kept rounds to the front, in plan order (a stable sort on a 0 / 1 key)
+        keep = (gain > 0) & (contact.gather(1, choice64) == 0)
+        front = torch.sort((~keep).to(torch.uint8), dim=1, stable=True)[1]
+        kept_views = choice64.gather(1, front)  # [N, T] candidate indices; the first `views` are the kept ones
+        views = keep.sum(dim=1)
+        length = self._no_length
+        # ---- 3. order: slot t of the plan holds position `pick` of kept_views
+        if self.route and t_max > 1:
+            points = self._points
+            points[:, 0] = env.poses[:, :3]
+            points[:, 1:] = poses[..., :3].gather(1, kept_views[..., None].expand(-1, -1, 3))
+            count = (views + 1).to(torch.int32)
+            dist = env.flight.pairwise_mm(points, count)
+            if self.tour_backend is None:
+                from ..ops.tour import route_tour
+                res = route_tour(dist, count)
+            else:
+                res = self.tour_backend(dist, count)
+            routed = res.routed.long()
+            views = routed - 1  # a kept view that no route reaches from the start is left out
+            point = res.order.long().gather(1, torch.minimum(slots + 1, views[:, None]))  # (0, the start, where nothing is routed)
+            pick = (point - 1).clamp(min=0)
+            length = res.length_mm.clone()
+        else:
+            pick = torch.minimum(slots, (views - 1).clamp(min=0)[:, None])
+        view = kept_views.gather(1, pick)
+        view = torch.where((views > 0)[:, None], view, choice64[:, :1].expand(-1, t_max))  # no view: round 0's choice
+        actions = cand.gather(1, view[..., None].expand(-1, -1, 6))
+        self.last_views, self.last_actions, self.last_length_mm = views, actions, length
+        # ---- 4. adopt
+        adopt = (env.episode_length_buf <= 1) | (self.cursor >= torch.clamp(self.plan_views, max=self.commit))
+        self.plan_actions = torch.where(adopt[:, None, None], actions, self.plan_actions)
+        self.plan_views = torch.where(adopt, views, self.plan_views)
+        self.cursor = torch.where(adopt, torch.zeros_like(self.cursor), self.cursor)
+        self.adopted = adopt
+        # ---- 5. act
+        act = self.plan_actions[rows, self.cursor]
+        self.cursor = self.cursor + 1
+        return act, None, None
 
 
 class FrontierViewPolicy:

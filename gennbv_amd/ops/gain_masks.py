@@ -1,0 +1,101 @@
+"""ViewGainMasks: the view gain that keeps what it counts, and greedy set cover on it  (csrc/viewgain.hip gnbv_view_gain_masks,
+csrc/covergreedy.hip gnbv_cover_greedy).
+
+ViewGain reduces, per candidate, the set of unknown voxels its rays would cross to three integers; two candidates that would see
+the SAME unknown voxels both look good.  ViewGainMasks runs the same kernel and also stores the two sets as bit masks --
+`unknown_bits` (every ray) and `hit_bits` (the rays that meet a surface), int32 [N, K, words] in the layout of the updater's
+scanned_bits and of gnbv_cover_greedy (bit lin & 31 of word lin >> 5, lin = (x G + y) G + z) -- so that `plan(T)` can pick T views
+that add DIFFERENT voxels: the classic greedy set cover, on the map the pilot holds and nothing else.  Integers with one right
+answer (include/gennbv_hip.h has the exact definitions).  Outputs are preallocated and reused: a result is valid until the next
+call of the same method.  No host synchronisation in either call.  GPU only, no CPU fallback; grid_size <= 64.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional
+
+import torch
+
+from .. import _lib
+from ..env.config import TaskConfig
+from .view_gain import MAX_GRID, ViewGain
+
+
+class ViewGainMasks(ViewGain):
+    def __init__(self, num_envs: int, k: int, cfg: TaskConfig, range_gt: torch.Tensor, voxel_size: torch.Tensor,
+                 inv_intrinsics: Optional[torch.Tensor] = None, stride: int = 4, range_m: Optional[float] = None,
+                 device="cuda:0", hit: bool = True, unknown: bool = True, words: Optional[int] = None, max_bytes: int = 8 << 30,
+                 with_c2w: bool = False, chunk: int = 0):
+        """ViewGain's arguments, plus: `hit` / `unknown` choose the masks to keep (at least one); `words` is the row length
+        (None: gnbv_grid_bit_words(G), the updater's; any multiple of 4 that holds G^3 bits); `max_bytes` caps the masks."""
+        g = int(cfg.grid_size)
+        if g > MAX_GRID:
+            raise _lib.GennbvHipError(f"ViewGainMasks: grid_size <= {MAX_GRID}, got {g} (the masks are stored from the LDS of the "
+                                      "one-launch kernel; above, the slab kernels split the voxels by x-planes and a word of the "
+                                      "mask can straddle two slabs: no mask-emitting form exists)")
+        if not (hit or unknown):
+            raise _lib.GennbvHipError("ViewGainMasks: at least one of hit, unknown")
+        if torch.device(device).type != "cuda":
+            raise _lib.GennbvHipError("ViewGainMasks runs on the GPU only (no CPU fallback)")
+        lib = _lib.load()
+        n, k = int(num_envs), int(k)
+        self.words = int(lib.gnbv_grid_bit_words(g)) if words is None else int(words)
+        if self.words < 1 or self.words % 4 or self.words * 32 < g ** 3:
+            raise _lib.GennbvHipError(f"ViewGainMasks: words must be a multiple of 4 that holds {g}^3 bits, got {self.words}")
+        kept = int(bool(hit)) + int(bool(unknown))
+        nbytes = kept * n * k * self.words * 4
+        if nbytes > int(max_bytes):
+            raise _lib.GennbvHipError(f"ViewGainMasks: the {kept} masks of {n} envs x {k} views x {self.words} words take {nbytes} "
+                                      f"bytes, above max_bytes = {int(max_bytes)}")
+        if n * k * self.words > 2 ** 31 - 1:
+            raise _lib.GennbvHipError(f"ViewGainMasks: {n} envs x {k} views x {self.words} words exceed 2^31 - 1 words")
+        super().__init__(n, k, cfg, range_gt, voxel_size, inv_intrinsics, stride, range_m, device, with_c2w, chunk)
+        dev = self.device
+        self.unknown_bits = torch.empty(n, k, self.words, dtype=torch.int32, device=dev) if unknown else None
+        self.hit_bits = torch.empty(n, k, self.words, dtype=torch.int32, device=dev) if hit else None
+        self.gains0 = torch.empty(n, k, dtype=torch.int32, device=dev)
+        self._plans = {}  # rounds -> (choice, gain, covered)
+        c = _lib.GnbvCoverGreedy()
+        c.n, c.k, c.words = n, k, self.words
+        self._cg = c
+
+    def _launch(self, a):
+        _lib.check(self.lib.gnbv_view_gain_masks(C.byref(a), self.words, _lib.ptr(self.unknown_bits), _lib.ptr(self.hit_bits),
+                                                 _lib.stream_ptr(self.device)), "gnbv_view_gain_masks")
+
+    def plan(self, rounds: int, which: str = "hit", contact: Optional[torch.Tensor] = None, covered_bits: Optional[torch.Tensor] = None,
+             lazy: bool = True):
+        """Greedy set cover over the `which` mask ("hit" | "unknown") of the last call: `rounds` views, each the candidate that
+        adds the most voxels no earlier round covers, starting from covered_bits [N, words] int32 (None: nothing covered; not
+        modified) -> (choice [N,T], gain [N,T], covered [N, words]) int32.  `contact` uint8 [N,K]: non-zero candidates are never
+        chosen unless all of an env's are (then candidate 0).  `gains0` [N,K] holds round 0's gain of every candidate.  One
+        gnbv_cover_greedy launch; `lazy` changes the work, not the result."""
+        rounds = int(rounds)
+        if not 1 <= rounds <= 4096:
+            raise _lib.GennbvHipError(f"ViewGainMasks.plan: rounds in 1..4096, got {rounds}")
+        if which not in ("hit", "unknown"):
+            raise _lib.GennbvHipError(f"ViewGainMasks.plan: which must be 'hit' or 'unknown', got {which!r}")
+        masks = self.hit_bits if which == "hit" else self.unknown_bits
+        if masks is None:
+            raise _lib.GennbvHipError(f"ViewGainMasks.plan: the {which} mask is not kept ({which}=False)")
+        n, k = self.num_envs, self.k
+        if contact is not None:
+            _lib.require_cuda(contact)
+            if contact.dtype != torch.uint8 or contact.shape != (n, k) or not contact.is_contiguous():
+                raise _lib.GennbvHipError(f"ViewGainMasks.plan: contact must be contiguous uint8 [{n}, {k}]")
+        if covered_bits is not None:
+            _lib.require_cuda(covered_bits)
+            if covered_bits.dtype != torch.int32 or covered_bits.shape != (n, self.words) or not covered_bits.is_contiguous():
+                raise _lib.GennbvHipError(f"ViewGainMasks.plan: covered_bits must be contiguous int32 [{n}, {self.words}], "
+                                          f"got {covered_bits.dtype} {tuple(covered_bits.shape)}")
+        if rounds not in self._plans:
+            dev = self.device
+            self._plans[rounds] = (torch.empty(n, rounds, dtype=torch.int32, device=dev), torch.empty(n, rounds, dtype=torch.int32, device=dev),
+                                   torch.empty(n, self.words, dtype=torch.int32, device=dev))
+        choice, gain, covered = self._plans[rounds]
+        c = self._cg
+        c.rounds, c.mask_bits, c.covered_in, c.contact = rounds, masks.data_ptr(), _lib.ptr(covered_bits), _lib.ptr(contact)
+        c.choice, c.gain, c.covered_out, c.gains0, c.ub, c.lazy = (choice.data_ptr(), gain.data_ptr(), covered.data_ptr(),
+                                                                   self.gains0.data_ptr(), None, int(bool(lazy)))
+        _lib.check(self.lib.gnbv_cover_greedy(C.byref(c), _lib.stream_ptr(self.device)), "gnbv_cover_greedy")
+        return choice, gain, covered

@@ -987,6 +987,22 @@ typedef struct GnbvViewGain {
 } GnbvViewGain;
 int gnbv_view_gain(const GnbvViewGain *args /*[host]*/, void *stream);
 
+/* gnbv_view_gain that keeps the sets it counts (a new entry point of ABI 5).  Rays, camera, source and target voxels, walk and
+ * stop rule are gnbv_view_gain's, unchanged.  For env e and candidate j, U(e, j) = the distinct unknown voxels visited by any ray
+ * before its first occupied voxel, H(e, j) (a subset of U) the same over the blocked rays only; a voxel is lin = (x g + y) g + z.
+ *   unknown_bits[e, j, :]: bit lin & 31 of word lin >> 5 is set iff lin is in U(e, j);  hit_bits[e, j, :] holds H(e, j) the same
+ * way: rows of `words` words, unswizzled -- gnbv_cover_greedy's mask_bits layout and the updater's scanned_bits'
+ * (words = gnbv_grid_bit_words(g) is always legal).  Every word of every row of a non-NULL output is written on every call, the
+ * zero words and the pad words from ceil(g^3 / 32) up to `words` included: the caller zeroes nothing.  args->gain is required and
+ * filled exactly as gnbv_view_gain fills it, so popcount(unknown_bits[e, j]) == gain[e, j, 0] and popcount(hit_bits[e, j]) ==
+ * gain[e, j, 1]; c2w_out as there.  One launch: the workgroup of (env, chunk) owns its candidates' rows and stores them from its
+ * LDS masks with 16-byte stores before it clears them.  No global atomics, no workspace, no allocation, no host synchronisation;
+ * deterministic; the result depends neither on `chunk` nor on which outputs are requested.
+ * Returns hipErrorInvalidValue for everything gnbv_view_gain refuses (g outside 2..64 included), both outputs NULL, `words` not
+ * a multiple of 4 or < ceil(g^3 / 32), an output that is not 16-byte aligned, n k words > 2^31 - 1, and args->ablate != 0. */
+int gnbv_view_gain_masks(const GnbvViewGain *args /*[host]*/, int words, int32_t *unknown_bits /*[n, k, words] or NULL*/,
+                         int32_t *hit_bits /*[n, k, words] or NULL*/, void *stream);
+
 /* The same quantity, bit for bit, for 2 <= g <= 128 (new entry points of ABI 5).  The grid no longer fits in LDS, so the call
  * runs three kernels per batch of envs on the caller's stream: the grids packed to 2 bits per voxel and the cameras; every
  * ray's fate (where it enters the grid, where it stops; `blocked` is complete here); then workgroups (env, chunk of candidates,

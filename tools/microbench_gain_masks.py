@@ -1,0 +1,106 @@
+"""Microbenchmark of the view gain that keeps its masks (gnbv_view_gain_masks) beside the view gain it extends, and of the
+set-cover plan on the masks (ViewGainMasks.plan, one gnbv_cover_greedy launch).
+
+    python tools/microbench_gain_masks.py [--repeats 7] [--iters 5] [--cases ...] [--parent-lib PATH] [--chunk 0] [--out FILE.json]
+
+Device events around `iters` back-to-back calls, after warm-up, `repeats` times; reported: median / min / max us per call.
+Cases (N, G, camera, stride, K), each on all-unknown grids and on mid-episode grids (10 closed-loop steps of random lattice poses):
+
+  g64_k8      256, 64^3, 240x320, 4, 8
+  g64_k32     256, 64^3, 240x320, 4, 32
+  g20_k32     8, 20^3, 240x320, 4, 32
+
+Rows per grid: gnbv_view_gain of this build; the same call on the library at --parent-lib (another build of the same ABI, e.g. the
+parent commit's: _lib.activate), on the same grids and poses; gnbv_view_gain_masks with both masks, the hit mask only, the unknown
+mask only.  Beside every masks row: the bytes the call stores more than gnbv_view_gain (n k words 4 per mask), its extra time over
+this build's gnbv_view_gain, and the store rate the two imply.  Then `plan(horizon)` on the hit mask for horizon 1, 3 and 5.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+
+from gennbv_amd import _lib  # noqa: E402
+from gennbv_amd.env import synthetic as S  # noqa: E402
+from gennbv_amd.env.config import TaskConfig  # noqa: E402
+from gennbv_amd.eval.baselines import LatticeCandidates  # noqa: E402
+from gennbv_amd.ops.gain_masks import ViewGainMasks  # noqa: E402
+from gennbv_amd.ops.view_gain import ViewGain  # noqa: E402
+from tools.microbench_render import time_calls  # noqa: E402
+from tools.microbench_view_gain import mid_episode_grid, stats  # noqa: E402
+
+DEV = "cuda:0"
+
+
+def masks_case(name, n, g, h, w, stride, k, args):
+    cfg = TaskConfig(camera_width=w, camera_height=h, grid_size=g)
+    scene = S.make_scenes(n, g, seed=1)
+    lc = LatticeCandidates(cfg, k, seed=3)
+    poses = lc.poses(lc.sample(n)).to(DEV)
+    grids = {"all_unknown": torch.zeros(n, g ** 3, dtype=torch.int8, device=DEV), "mid_episode": mid_episode_grid(cfg, n, scene)}
+    kw = dict(stride=stride, device=DEV, chunk=args.chunk)
+    ops = {"view_gain": ViewGain(n, k, cfg, scene.range_gt, scene.voxel_size, **kw)}
+    if args.parent_lib:
+        _lib.activate(args.parent_lib)  # an operator keeps the library that was active when it was built
+        ops["view_gain_parent"] = ViewGain(n, k, cfg, scene.range_gt, scene.voxel_size, **kw)
+        _lib.activate()
+    ops["masks_both"] = ViewGainMasks(n, k, cfg, scene.range_gt, scene.voxel_size, **kw)
+    ops["masks_hit"] = ViewGainMasks(n, k, cfg, scene.range_gt, scene.voxel_size, unknown=False, **kw)
+    ops["masks_unknown"] = ViewGainMasks(n, k, cfg, scene.range_gt, scene.voxel_size, hit=False, **kw)
+    words = ops["masks_both"].words
+    mask_bytes = n * k * words * 4
+    out = {"case": name, "envs": n, "grid": g, "h": h, "w": w, "stride": stride, "k": k, "chunk": args.chunk, "words": words,
+           "mask_bytes": mask_bytes}
+    for gname, tri in grids.items():
+        want = ops["view_gain"](tri, poses).clone()
+        for oname, op in ops.items():
+            assert torch.equal(op(tri, poses), want), oname
+            out[f"{gname}_{oname}"] = stats(time_calls(lambda: op(tri, poses), args.iters, args.repeats))
+        base = out[f"{gname}_view_gain"]["us_median"]
+        for oname, masks in (("masks_both", 2), ("masks_hit", 1), ("masks_unknown", 1)):
+            row = out[f"{gname}_{oname}"]
+            row["extra_bytes"] = masks * mask_bytes
+            row["extra_us"] = row["us_median"] - base
+            row["implied_GB_per_s"] = masks * mask_bytes / row["extra_us"] * 1e-3 if row["extra_us"] > 0 else None
+        both = ops["masks_both"]
+        both(tri, poses)
+        for horizon in (1, 3, 5):
+            out[f"{gname}_plan_{horizon}"] = stats(time_calls(lambda: both.plan(horizon, which="hit"), args.iters, args.repeats))
+        out[gname + "_mean_gain"] = want.float().mean(dim=(0, 1)).tolist()
+        out[gname + "_mean_plan5_gain"] = both.plan(5, which="hit")[1].float().mean(dim=0).tolist()
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--cases", default="g64_k8,g64_k32,g20_k32")
+    ap.add_argument("--parent-lib", default=None, help="another build of libgennbv_hip.so (the same ABI) to time gnbv_view_gain on")
+    ap.add_argument("--chunk", type=int, default=0, help="candidates per workgroup (0 = chosen)")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("microbench_gain_masks needs a GPU")
+    table = {"g64_k8": (256, 64, 240, 320, 4, 8), "g64_k32": (256, 64, 240, 320, 4, 32), "g20_k32": (8, 20, 240, 320, 4, 32)}
+    results = []
+    for c in args.cases.split(","):
+        if c not in table:
+            raise SystemExit("unknown case " + c)
+        r = masks_case(c, *table[c], args)
+        print(json.dumps(r), flush=True)
+        results.append(r)
+        torch.cuda.empty_cache()
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(results, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
