@@ -326,6 +326,19 @@ def require_cuda(*tensors):
                                  "there is no CPU fallback" % t.device)
 
 
+def tri_args(tri, n: int, g3: int, who: str):
+    """The tri-class grid of a belief-map entry point (gnbv_flight_blocked_tri, gnbv_flight_classify_tri, gnbv_sweep_tri,
+    gnbv_frontier_tri, gnbv_frontier_viewpoints): tri int8 or float32 [n, >= g3] on the GPU, unit element stride, any row stride ->
+    the four ABI values (tri_i8, tri_i8_row_stride, tri_f32, tri_f32_row_stride), the form not given NULL and 0.  `who` names the
+    caller in the error.  (n == 1: a dimension of size 1 may carry any stride, and the library wants a row of at least g3.)"""
+    require_cuda(tri)
+    if tri.dtype not in (torch.int8, torch.float32) or tri.dim() != 2 or tri.shape[0] != n or tri.shape[1] < g3 or tri.stride(1) != 1:
+        raise GennbvHipError(f"{who}: tri must be int8 or float32 [{n}, >= {g3}] with unit element stride, got {tri.dtype} "
+                             f"{tuple(tri.shape)} strides {tuple(tri.stride())}")
+    row = int(tri.stride(0)) if n > 1 else max(int(tri.stride(0)), g3)
+    return (tri.data_ptr(), row, None, 0) if tri.dtype == torch.int8 else (None, 0, tri.data_ptr(), row)
+
+
 def require_contig(*tensors):
     for t in tensors:
         if t is not None and not t.is_contiguous():

@@ -69,6 +69,16 @@ __device__ __forceinline__ long long wave_min_all(long long v)
     return v;
 }
 
+__device__ __forceinline__ unsigned long long wave_min_all(unsigned long long v)
+{
+#pragma unroll
+    for (int d = kWave / 2; d > 0; d >>= 1) {
+        const unsigned long long o = __shfl_xor(v, d, kWave);
+        v = o < v ? o : v;
+    }
+    return v;
+}
+
 __device__ __forceinline__ long long wave_max_all(long long v)
 {
 #pragma unroll

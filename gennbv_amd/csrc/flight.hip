@@ -32,6 +32,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "map_bits.h"  // lattice_ok: the one lattice check, shared with the kernels that place the lattice on the map
 #include "../../include/gennbv_hip.h"
 
 namespace {
@@ -222,16 +223,15 @@ __global__ __launch_bounds__(kWave) void k_flight_path(const uint32_t *__restric
     len_out[e] = dc != 0u ? 0 : (count <= max_len ? count : -count);
 }
 
-// nx, ny, nz in 1..1024, a finite lattice with h > 0 on every axis that has more than one node, positive edge costs whose sum
-// over a route through every node -- with `penalty` added at every node entered -- stays below kFree
+// a lattice that passes lattice_ok (map_bits.h: shared with the kernels that place the lattice on the map), positive edge costs
+// whose sum over a route through every node -- with `penalty` added at every node entered -- stays below kFree
 bool make_lattice(int nx, int ny, int nz, const uint32_t *cost, const double *lo, const double *h, Lattice *out, uint32_t penalty = 0)
 {
     if (cost == nullptr || lo == nullptr || h == nullptr) return false;
+    if (!lattice_ok(nx, ny, nz, lo, h)) return false;
     const int n[3] = {nx, ny, nz};
     uint32_t cmax = 0;
     for (int a = 0; a < 3; ++a) {
-        if (n[a] < 1 || n[a] > 1024 || !std::isfinite(lo[a]) || !std::isfinite(h[a])) return false;
-        if (n[a] > 1 && !(h[a] > 0.0)) return false;
         out->lo[a] = lo[a];
         out->h[a] = h[a];
     }

@@ -7,7 +7,10 @@
 // the grid, the ground).  The predicate is exact -- fp64, one fixed operation order, no FMA (include/gennbv_hip.h states it; the
 // library is built with -ffp-contract=off) -- so tests compare every u32 of the output with a numpy restatement.
 //
-//   k_flight_blocked_tri<kLds, kF32>   workgroup (env, chunk of nodes), 512 lanes; a wave owns 64 consecutive nodes at a time and
+// Shared with the other kernels on the map: the grid forms, the LDS pack and swizzle, the span of a word, the LDS limit, the
+// (lds, f32) dispatch, the workgroups per env and the lattice check are map_bits.h's; the voxel frame is voxel_frame.h's.
+//
+//   k_flight_tri<kLds, kF32, kTell>   workgroup (env, chunk of nodes), 512 lanes; a wave owns 64 consecutive nodes at a time and
 //     stores their ballot as two whole words of blocked_out: one writer per word, no atomics.  Nodes at or past M (padding) count
 //     as blocked.  Per node: the per-axis voxel window [i0, i1] of the ball (clamped to the grid in fp64 before conversion, so every
 //     loop below runs at most G times whatever the device arrays hold), then x, y, z over the window with gx^2 and gx^2 + gy^2
@@ -16,20 +19,20 @@
 //     kLds (mode 1): the workgroup first packs "this voxel blocks" into one bit per voxel in LDS (64 voxels per wave ballot,
 //       coalesced reads of either grid form; G^3 / 8 bytes, 32 KiB at 64^3) and a node reads the z-run of a (x, y) column as whole
 //       words: a word with no blocking bit inside the window costs no arithmetic.  Lanes of a wave are x-neighbours, their words lie
-//       G^2 / 32 apart -- at G = 64 all on one bank -- so the words are swizzled (map_bits.h has the pack, shared with sweepmap.hip).
+//       G^2 / 32 apart -- at G = 64 all on one bank -- so the words are swizzled.
 //     !kLds (mode 2): the same decisions with the voxels read from global memory, for grids whose bits do not fit (up to 128^3).
 //     kF32: the grid is the fp32 slice of an observation row, else int8 rows.
-//   k_flight_classify_tri<kLds, kF32>   the same launch shape with two outputs (gnbv_flight_classify_tri): "blocked" as with
-//     unknown_blocks = 0, and "costly" = not blocked, but the ball touches an unknown voxel -- what two launches of the kernel above
-//     (unknown_blocks = 0 and 1) and an AND-NOT would give, from one pass over the window.  The walk still ends at the first touched
-//     occupied voxel; a touched unknown voxel only sets a flag, and from then on unknown voxels are skipped.
-//     kLds: two bit planes, occupied then unknown (map_pack_planes: every voxel read once), G^3 / 4 bytes, so the limit is lower
+//     kTell (gnbv_flight_classify_tri): unknown space is told apart.  Two outputs: "blocked" as with unknown_blocks = 0, and "costly"
+//       = not blocked, but the ball touches an unknown voxel -- what two launches without kTell (unknown_blocks = 0 and 1) and an
+//       AND-NOT would give, from one pass over the window.  The walk still ends at the first touched occupied voxel; a touched
+//       unknown voxel only sets a flag, and from then on unknown voxels are skipped.
+//       kLds: two bit planes, occupied then unknown (every voxel read once), G^3 / 4 bytes, so the limit is lower
 //       (map_planes_max_grid, 86); a word of the window is occ | unk until the flag is set, occ alone afterwards.
-#include <algorithm>
 #include <cmath>
 
 #include "common.h"
 #include "map_bits.h"
+#include "voxel_frame.h"
 #include "../../include/gennbv_hip.h"
 
 namespace {
@@ -40,7 +43,7 @@ constexpr int kMapWaves = kMapLanes / kWave;
 struct MapArgs {
     int g, nx, ny, nz, m, words;
     int chunks, chunk_waves;  // workgroups per env; 64-node groups per workgroup
-    int shift;                // the LDS swizzle
+    int shift, plane_words;   // the LDS swizzle; words of one bit plane
     int unknown_blocks, outside_blocks, ground;
     double lo[3], h[3], rho, rho2;
 };
@@ -83,56 +86,15 @@ __device__ __forceinline__ NodeWindow node_window(const MapArgs &a, int c, const
     return n;
 }
 
-template <bool kLds, bool kF32>
-__device__ __forceinline__ bool node_blocked(const MapArgs &a, int c, const double *o, const double *v, const void *__restrict__ tri,
-                                             const uint32_t *bits)
-{
-    const int g = a.g;
-    const NodeWindow n = node_window(a, c, o, v);
-    const double *p = n.p;
-    const int *i0 = n.i0, *i1 = n.i1;
-    if (a.outside_blocks && n.outside) return true;
-    if (a.ground && p[2] - a.rho <= 0.0) return true;
-    if (n.empty) return false;
-    const bool unk = a.unknown_blocks != 0;
-    for (int x = i0[0]; x <= i1[0]; ++x) {
-        const double gx2 = gap2(o[0], v[0], x, p[0]);
-        if (gx2 > a.rho2) continue;
-        for (int y = i0[1]; y <= i1[1]; ++y) {
-            const double s = gx2 + gap2(o[1], v[1], y, p[1]);
-            if (s > a.rho2) continue;
-            const int base = (x * g + y) * g;
-            if (kLds) {
-                const int b0 = base + i0[2], b1 = base + i1[2];
-                for (int w = b0 >> 5; w <= (b1 >> 5); ++w) {
-                    const int first = max(b0, w << 5), last = min(b1, (w << 5) + 31);
-                    const uint32_t span = (0xFFFFFFFFu >> (31 - (last - first))) << (first & 31);
-                    const uint32_t word = bits[map_swizzle(w, a.shift)] & span;
-                    if (word == 0u) continue;
-                    for (int b = first; b <= last; ++b) {
-                        if (((word >> (b & 31)) & 1u) == 0u) continue;
-                        if (s + gap2(o[2], v[2], b - base, p[2]) <= a.rho2) return true;
-                    }
-                }
-            } else {
-                for (int z = i0[2]; z <= i1[2]; ++z) {
-                    if (!voxel_blocks<kF32>(tri, base + z, unk)) continue;
-                    if (s + gap2(o[2], v[2], z, p[2]) <= a.rho2) return true;
-                }
-            }
-        }
-    }
-    return false;
-}
-
-// node_blocked with unknown space told apart (gnbv_flight_classify_tri): kBlocked where the ball touches an occupied voxel (or the
-// outside / the ground, by flag) -- the walk ends there as above -- else kCostly where it touches an unknown one (a flag; the walk
-// goes on, looking for occupied voxels only), else kClear.  kLds: the two planes of map_pack_planes.
+// The class of node c.  kBlocked where the ball touches a voxel that blocks (or the outside / the ground, by flag): the walk ends
+// there.  !kTell: a voxel blocks where it is occupied, or unknown with a.unknown_blocks; `blk` is that one plane and the answer is
+// kBlocked or kClear.  kTell: only an occupied voxel blocks (`blk`), and a touched unknown one (`unk`) makes the node kCostly unless
+// it turns out blocked: a flag, the walk goes on, looking for occupied voxels only.
 enum { kClear = 0, kBlocked = 1, kCostly = 2 };
 
-template <bool kLds, bool kF32>
+template <bool kLds, bool kF32, bool kTell>
 __device__ __forceinline__ int node_class(const MapArgs &a, int c, const double *o, const double *v, const void *__restrict__ tri,
-                                          const uint32_t *occ, const uint32_t *unk)
+                                          const uint32_t *blk, const uint32_t *unk)
 {
     const int g = a.g;
     const NodeWindow n = node_window(a, c, o, v);
@@ -141,6 +103,7 @@ __device__ __forceinline__ int node_class(const MapArgs &a, int c, const double 
     if (a.outside_blocks && n.outside) return kBlocked;
     if (a.ground && p[2] - a.rho <= 0.0) return kBlocked;
     if (n.empty) return kClear;
+    const bool unknown_blocks = !kTell && a.unknown_blocks != 0;
     bool costly = false;
     for (int x = i0[0]; x <= i1[0]; ++x) {
         const double gx2 = gap2(o[0], v[0], x, p[0]);
@@ -152,25 +115,26 @@ __device__ __forceinline__ int node_class(const MapArgs &a, int c, const double 
             if (kLds) {
                 const int b0 = base + i0[2], b1 = base + i1[2];
                 for (int w = b0 >> 5; w <= (b1 >> 5); ++w) {
-                    const int first = max(b0, w << 5), last = min(b1, (w << 5) + 31);
-                    const uint32_t span = (0xFFFFFFFFu >> (31 - (last - first))) << (first & 31);
+                    const uint32_t span = map_span(w, b0, b1);
                     const int at = map_swizzle(w, a.shift);
-                    const uint32_t wo = occ[at] & span;
-                    const uint32_t word = costly ? wo : (wo | (unk[at] & span));  // (once costly, unknown voxels decide nothing)
-                    if (word == 0u) continue;
-                    for (int b = first; b <= last; ++b) {
-                        if (((word >> (b & 31)) & 1u) == 0u) continue;
-                        if (s + gap2(o[2], v[2], b - base, p[2]) > a.rho2) continue;
-                        if ((wo >> (b & 31)) & 1u) return kBlocked;
+                    const uint32_t wb = blk[at] & span;
+                    uint32_t word = wb;
+                    if (kTell && !costly) word |= unk[at] & span;  // (once costly, unknown voxels decide nothing)
+                    while (word != 0u) {
+                        const int bit = __builtin_ctz(word);
+                        word &= word - 1u;
+                        if (s + gap2(o[2], v[2], (w << 5) + bit - base, p[2]) > a.rho2) continue;
+                        if (!kTell || ((wb >> bit) & 1u)) return kBlocked;
                         costly = true;
                     }
                 }
             } else {
                 for (int z = i0[2]; z <= i1[2]; ++z) {
                     const int cls = voxel_class<kF32>(tri, base + z);
-                    if (cls < 0 || (cls == 0 && costly)) continue;
+                    const bool blocks = cls > 0 || (unknown_blocks && cls == 0);
+                    if (!blocks && !(kTell && cls == 0 && !costly)) continue;
                     if (s + gap2(o[2], v[2], z, p[2]) > a.rho2) continue;
-                    if (cls > 0) return kBlocked;
+                    if (blocks) return kBlocked;
                     costly = true;
                 }
             }
@@ -179,168 +143,103 @@ __device__ __forceinline__ int node_class(const MapArgs &a, int c, const double 
     return costly ? kCostly : kClear;
 }
 
-template <bool kLds, bool kF32>
-__global__ __launch_bounds__(kMapLanes) void k_flight_blocked_tri(const void *__restrict__ tri_base, int64_t row_bytes,
-                                                                  const float *__restrict__ range_gt, const float *__restrict__ voxel_size,
-                                                                  MapArgs a, uint32_t *__restrict__ blocked_out)
+// the ballot of kBlocked (padding set) into blocked_out and, with kTell, the ballot of kCostly (padding clear) into costly_out
+template <bool kLds, bool kF32, bool kTell>
+__global__ __launch_bounds__(kMapLanes) void k_flight_tri(const void *__restrict__ tri_base, int64_t row_bytes,
+                                                          const float *__restrict__ range_gt, const float *__restrict__ voxel_size, MapArgs a,
+                                                          uint32_t *__restrict__ blocked_out, uint32_t *__restrict__ costly_out)
 {
     extern __shared__ __attribute__((aligned(16))) char map_lds[];
-    uint32_t *bits = reinterpret_cast<uint32_t *>(map_lds);
+    uint32_t *blk = reinterpret_cast<uint32_t *>(map_lds), *unk = blk + a.plane_words;
     const int e = blockIdx.x / a.chunks, chunk = blockIdx.x - e * a.chunks;
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
     const void *tri = static_cast<const char *>(tri_base) + (size_t)e * row_bytes;
 
     if (kLds) {
-        map_pack_bits<kF32, kMapWaves>(tri, a.g, a.unknown_blocks != 0, a.shift, bits);
-        __syncthreads();
-    }
-
-    // the voxel frame of gnbv_pose_to_idx: the subtraction in fp32
-    double o[3], v[3];
-#pragma unroll
-    for (int ax = 0; ax < 3; ++ax) {
-        const float vf = voxel_size[e * 3 + ax];
-        o[ax] = (double)__fsub_rn(range_gt[e * 6 + 2 * ax + 1], __fmul_rn(0.5f, vf));
-        v[ax] = (double)vf;
-    }
-
-    uint32_t *out = blocked_out + (size_t)e * a.words;
-    for (int t = wave; t < a.chunk_waves; t += kMapWaves) {
-        const int c0 = (chunk * a.chunk_waves + t) * kWave, c = c0 + lane;
-        bool blocked = true;  // padding
-        if (c < a.m) blocked = node_blocked<kLds, kF32>(a, c, o, v, tri, bits);
-        const unsigned long long mask = __ballot(blocked);
-        const int w = c0 >> 5;
-        if (lane == 0 && w < a.words) out[w] = (uint32_t)mask;
-        if (lane == 0 && w + 1 < a.words) out[w + 1] = (uint32_t)(mask >> 32);
-    }
-}
-
-template <bool kLds, bool kF32>
-int launch_map(const void *tri, int64_t row_bytes, const float *range_gt, const float *voxel_size, const MapArgs &a, int n, size_t lds,
-               uint32_t *blocked_out, hipStream_t stream)
-{
-    if (kLds && lds > 64 * 1024) {  // what a launch may ask for without the attribute
-        static bool raised = false;
-        if (!raised) {
-            const hipError_t err = hipFuncSetAttribute((const void *)k_flight_blocked_tri<kLds, kF32>,
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, kMapLdsBytes);
-            if (err != hipSuccess) return (int)err;
-            raised = true;
-        }
-    }
-    hipLaunchKernelGGL((k_flight_blocked_tri<kLds, kF32>), dim3((unsigned)(n * a.chunks)), dim3(kMapLanes), lds, stream, tri, row_bytes,
-                       range_gt, voxel_size, a, blocked_out);
-    return gnbv_launch_status();
-}
-
-// k_flight_blocked_tri with two outputs: the ballot of kBlocked (padding set) and the ballot of kCostly (padding clear)
-template <bool kLds, bool kF32>
-__global__ __launch_bounds__(kMapLanes) void k_flight_classify_tri(const void *__restrict__ tri_base, int64_t row_bytes,
-                                                                   const float *__restrict__ range_gt, const float *__restrict__ voxel_size,
-                                                                   MapArgs a, int plane_words, uint32_t *__restrict__ blocked_out,
-                                                                   uint32_t *__restrict__ costly_out)
-{
-    extern __shared__ __attribute__((aligned(16))) char map_lds[];
-    uint32_t *occ = reinterpret_cast<uint32_t *>(map_lds), *unk = occ + plane_words;
-    const int e = blockIdx.x / a.chunks, chunk = blockIdx.x - e * a.chunks;
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    const void *tri = static_cast<const char *>(tri_base) + (size_t)e * row_bytes;
-
-    if (kLds) {
-        map_pack_planes<kF32, kMapWaves>(tri, a.g, a.shift, occ, unk);
+        if (kTell) map_pack_planes<kF32, kMapWaves>(tri, a.g, a.shift, blk, unk);
+        else map_pack_bits<kF32, kMapWaves>(tri, a.g, a.unknown_blocks != 0, a.shift, blk);
         __syncthreads();
     }
 
     double o[3], v[3];
-#pragma unroll
-    for (int ax = 0; ax < 3; ++ax) {
-        const float vf = voxel_size[e * 3 + ax];
-        o[ax] = (double)__fsub_rn(range_gt[e * 6 + 2 * ax + 1], __fmul_rn(0.5f, vf));
-        v[ax] = (double)vf;
-    }
+    voxel_frame_f64(range_gt, voxel_size, e, o, v);
 
-    uint32_t *out_b = blocked_out + (size_t)e * a.words, *out_c = costly_out + (size_t)e * a.words;
+    uint32_t *out_b = blocked_out + (size_t)e * a.words, *out_c = kTell ? costly_out + (size_t)e * a.words : nullptr;
     for (int t = wave; t < a.chunk_waves; t += kMapWaves) {
         const int c0 = (chunk * a.chunk_waves + t) * kWave, c = c0 + lane;
         int cls = kBlocked;  // padding
-        if (c < a.m) cls = node_class<kLds, kF32>(a, c, o, v, tri, occ, unk);
+        if (c < a.m) cls = node_class<kLds, kF32, kTell>(a, c, o, v, tri, blk, unk);
         const unsigned long long mb = __ballot(cls == kBlocked), mc = __ballot(cls == kCostly);
         const int w = c0 >> 5;
         if (lane == 0 && w < a.words) {
             out_b[w] = (uint32_t)mb;
-            out_c[w] = (uint32_t)mc;
+            if (kTell) out_c[w] = (uint32_t)mc;
         }
         if (lane == 0 && w + 1 < a.words) {
             out_b[w + 1] = (uint32_t)(mb >> 32);
-            out_c[w + 1] = (uint32_t)(mc >> 32);
+            if (kTell) out_c[w + 1] = (uint32_t)(mc >> 32);
         }
     }
 }
 
-template <bool kLds, bool kF32>
-int launch_classify(const void *tri, int64_t row_bytes, const float *range_gt, const float *voxel_size, const MapArgs &a, int n, size_t lds,
-                    uint32_t *blocked_out, uint32_t *costly_out, hipStream_t stream)
+template <bool kLds, bool kF32, bool kTell>
+int launch_map(const MapGrid &grid, const float *range_gt, const float *voxel_size, const MapArgs &a, int n, size_t lds,
+               uint32_t *blocked_out, uint32_t *costly_out, hipStream_t stream)
 {
-    if (kLds && lds > 64 * 1024) {  // what a launch may ask for without the attribute
-        static bool raised = false;
-        if (!raised) {
-            const hipError_t err = hipFuncSetAttribute((const void *)k_flight_classify_tri<kLds, kF32>,
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, kMapLdsBytes);
-            if (err != hipSuccess) return (int)err;
-            raised = true;
-        }
-    }
-    hipLaunchKernelGGL((k_flight_classify_tri<kLds, kF32>), dim3((unsigned)(n * a.chunks)), dim3(kMapLanes), lds, stream, tri, row_bytes,
-                       range_gt, voxel_size, a, (int)(lds / 8), blocked_out, costly_out);
+    const int bad = map_raise_lds<k_flight_tri<kLds, kF32, kTell>>(lds);
+    if (bad != 0) return bad;
+    hipLaunchKernelGGL((k_flight_tri<kLds, kF32, kTell>), dim3((unsigned)(n * a.chunks)), dim3(kMapLanes), lds, stream, grid.base,
+                       grid.row_bytes, range_gt, voxel_size, a, blocked_out, costly_out);
     return gnbv_launch_status();
 }
 
-// the argument checks and the launch shape shared by the two entry points; `max_grid` the LDS limit of the caller's mode 1
-int make_map_args(const void *tri_i8, int64_t tri_i8_row_stride, const void *tri_f32, int64_t tri_f32_row_stride, int g, const float *range_gt,
-                  const float *voxel_size, int n, int nx, int ny, int nz, const double *lo, const double *h, double rho, int unknown_blocks,
-                  int outside_blocks, int ground, const void *out, int mode, int max_grid, MapArgs *args, bool *use_lds)
+// the body of the two entry points: the argument checks, the launch shape, the launch.  kTell: costly_out is written too and
+// unknown_blocks is 0; mode 1 holds two planes, so its limit is lower.
+template <bool kTell>
+int flight_tri(const int8_t *tri_i8, int64_t tri_i8_row_stride, const float *tri_f32, int64_t tri_f32_row_stride, int g, const float *range_gt,
+               const float *voxel_size, int n, int nx, int ny, int nz, const double *lo, const double *h, double rho, int unknown_blocks,
+               int outside_blocks, int ground, uint32_t *blocked_out, uint32_t *costly_out, int mode, void *stream)
 {
-    GNBV_CHECK_ARG((tri_i8 != nullptr) != (tri_f32 != nullptr));
-    GNBV_CHECK_ARG(range_gt != nullptr && voxel_size != nullptr && out != nullptr && lo != nullptr && h != nullptr);
-    GNBV_CHECK_ARG(n >= 1 && g >= 1 && g <= kMapMaxGrid && mode >= 0 && mode <= 2);
+    MapGrid grid;
+    const int bad = map_grid(tri_i8, tri_i8_row_stride, tri_f32, tri_f32_row_stride, g, &grid);
+    if (bad != 0) return bad;
+    GNBV_CHECK_ARG(range_gt != nullptr && voxel_size != nullptr && blocked_out != nullptr && lo != nullptr && h != nullptr);
+    GNBV_CHECK_ARG(!kTell || costly_out != nullptr);
+    GNBV_CHECK_ARG(n >= 1 && mode >= 0 && mode <= 2);
     GNBV_CHECK_ARG(std::isfinite(rho) && rho > 0.0);
-    const int64_t g3 = (int64_t)g * g * g;
-    GNBV_CHECK_ARG((tri_f32 != nullptr ? tri_f32_row_stride : tri_i8_row_stride) >= g3);
-    MapArgs &a = *args;
-    const int dims[3] = {nx, ny, nz};
+    GNBV_CHECK_ARG(lattice_ok(nx, ny, nz, lo, h));
+    constexpr int kPlanes = kTell ? 2 : 1;
+    const bool fits = g <= map_lds_max_grid(kPlanes);
+    GNBV_CHECK_ARG(mode != 1 || fits);
+    const bool lds = mode == 1 || (mode == 0 && fits);
+    MapArgs a;
     for (int ax = 0; ax < 3; ++ax) {
-        GNBV_CHECK_ARG(dims[ax] >= 1 && dims[ax] <= 1024 && std::isfinite(lo[ax]) && std::isfinite(h[ax]));
-        GNBV_CHECK_ARG(dims[ax] == 1 || h[ax] > 0.0);
         a.lo[ax] = lo[ax];
         a.h[ax] = h[ax];
     }
     const int64_t m = (int64_t)nx * ny * nz;
-    const bool fits = g <= max_grid;
-    GNBV_CHECK_ARG(mode != 1 || fits);
-    const bool lds = mode == 1 || (mode == 0 && fits);
     a.g = g;
     a.nx = nx;
     a.ny = ny;
     a.nz = nz;
     a.m = (int)m;
     a.words = (int)((m + 31) / 32);
-    // 64-node groups per workgroup: one per wave where the grid is read in place; with the bits in LDS every workgroup pays for
-    // packing the whole grid, so an env gets only as many workgroups as it takes to reach about two per CU over all envs
-    const int64_t groups = (m + kWave - 1) / kWave;
-    int64_t chunks = (groups + kMapWaves - 1) / kMapWaves;
-    if (lds) chunks = std::min<int64_t>(chunks, std::max<int64_t>(1, (512 + n - 1) / n));
-    a.chunk_waves = (int)((groups + chunks - 1) / chunks);
-    a.chunks = (int)((groups + a.chunk_waves - 1) / a.chunk_waves);
+    const MapChunks ch = map_chunks((m + kWave - 1) / kWave, kMapWaves, n, lds);  // the items: 64-node groups, one per wave and turn
+    a.chunks = ch.chunks;
+    a.chunk_waves = ch.per;
     GNBV_CHECK_ARG((int64_t)n * a.chunks <= 0x7fffffff);
     a.shift = map_swizzle_shift(g);
+    a.plane_words = lds ? (int)(map_lds_bytes(g) / 4) : 0;
     a.unknown_blocks = unknown_blocks != 0;
     a.outside_blocks = outside_blocks != 0;
     a.ground = ground != 0;
     a.rho = rho;
     a.rho2 = rho * rho;
-    *use_lds = lds;
-    return 0;
+    const size_t bytes = lds ? kPlanes * map_lds_bytes(g) : 0;
+    return map_dispatch(lds, grid.f32, [&](auto kLds, auto kF32) {
+        return launch_map<decltype(kLds)::value, decltype(kF32)::value, kTell>(grid, range_gt, voxel_size, a, n, bytes, blocked_out, costly_out,
+                                                                              gnbv_stream(stream));
+    });
 }
 
 }  // namespace
@@ -352,22 +251,8 @@ GNBV_API int gnbv_flight_blocked_tri(const int8_t *tri_i8, int64_t tri_i8_row_st
                                      const double *h, double rho, int unknown_blocks, int outside_blocks, int ground,
                                      uint32_t *blocked_out, int mode, void *stream)
 {
-    MapArgs a;
-    bool lds;
-    const int bad = make_map_args(tri_i8, tri_i8_row_stride, tri_f32, tri_f32_row_stride, g, range_gt, voxel_size, n, nx, ny, nz, lo, h, rho,
-                                  unknown_blocks, outside_blocks, ground, blocked_out, mode, map_lds_max_grid(), &a, &lds);
-    if (bad != 0) return bad;
-    const bool f32 = tri_f32 != nullptr;
-    const void *tri = f32 ? static_cast<const void *>(tri_f32) : static_cast<const void *>(tri_i8);
-    const int64_t row_bytes = f32 ? 4 * tri_f32_row_stride : tri_i8_row_stride;
-    const hipStream_t s = gnbv_stream(stream);
-    if (lds) {
-        const size_t bytes = map_lds_bytes(g);
-        return f32 ? launch_map<true, true>(tri, row_bytes, range_gt, voxel_size, a, n, bytes, blocked_out, s)
-                   : launch_map<true, false>(tri, row_bytes, range_gt, voxel_size, a, n, bytes, blocked_out, s);
-    }
-    return f32 ? launch_map<false, true>(tri, row_bytes, range_gt, voxel_size, a, n, 0, blocked_out, s)
-               : launch_map<false, false>(tri, row_bytes, range_gt, voxel_size, a, n, 0, blocked_out, s);
+    return flight_tri<false>(tri_i8, tri_i8_row_stride, tri_f32, tri_f32_row_stride, g, range_gt, voxel_size, n, nx, ny, nz, lo, h, rho,
+                             unknown_blocks, outside_blocks, ground, blocked_out, nullptr, mode, stream);
 }
 
 GNBV_API int gnbv_flightmap_classify_lds_max_grid(void) { return map_planes_max_grid(); }
@@ -377,21 +262,6 @@ GNBV_API int gnbv_flight_classify_tri(const int8_t *tri_i8, int64_t tri_i8_row_s
                                       const double *h, double rho, int outside_blocks, int ground, uint32_t *blocked_out,
                                       uint32_t *costly_out, int mode, void *stream)
 {
-    GNBV_CHECK_ARG(costly_out != nullptr);
-    MapArgs a;
-    bool lds;
-    const int bad = make_map_args(tri_i8, tri_i8_row_stride, tri_f32, tri_f32_row_stride, g, range_gt, voxel_size, n, nx, ny, nz, lo, h, rho,
-                                  0, outside_blocks, ground, blocked_out, mode, map_planes_max_grid(), &a, &lds);
-    if (bad != 0) return bad;
-    const bool f32 = tri_f32 != nullptr;
-    const void *tri = f32 ? static_cast<const void *>(tri_f32) : static_cast<const void *>(tri_i8);
-    const int64_t row_bytes = f32 ? 4 * tri_f32_row_stride : tri_i8_row_stride;
-    const hipStream_t s = gnbv_stream(stream);
-    if (lds) {
-        const size_t bytes = 2 * map_lds_bytes(g);
-        return f32 ? launch_classify<true, true>(tri, row_bytes, range_gt, voxel_size, a, n, bytes, blocked_out, costly_out, s)
-                   : launch_classify<true, false>(tri, row_bytes, range_gt, voxel_size, a, n, bytes, blocked_out, costly_out, s);
-    }
-    return f32 ? launch_classify<false, true>(tri, row_bytes, range_gt, voxel_size, a, n, 0, blocked_out, costly_out, s)
-               : launch_classify<false, false>(tri, row_bytes, range_gt, voxel_size, a, n, 0, blocked_out, costly_out, s);
+    return flight_tri<true>(tri_i8, tri_i8_row_stride, tri_f32, tri_f32_row_stride, g, range_gt, voxel_size, n, nx, ny, nz, lo, h, rho, 0,
+                            outside_blocks, ground, blocked_out, costly_out, mode, stream);
 }

@@ -16,6 +16,7 @@
 //        its at most B x B rows of at most B voxels in the frontier plane -- count by popcount, sum z by four masked popcounts -- and
 //        stores the four ints of the record: every record one writer, no atomics, zeros where empty.
 //   Every loop is bounded by G and constants: no loop count comes from the arrays.
+//   The grid forms, the pack loop and the LDS limit are map_bits.h's, shared with the other kernels on the map.
 #include <algorithm>
 
 #include "common.h"
@@ -138,21 +139,13 @@ __global__ __launch_bounds__(kFrontLanes) void k_frontier_tri(const void *__rest
 }
 
 template <bool kF32>
-int launch_frontier(const void *tri, int64_t row_bytes, const FrontierArgs &a, int n, uint32_t *bits_out, int32_t *blocks_out,
-                    hipStream_t stream)
+int launch_frontier(const MapGrid &grid, const FrontierArgs &a, int n, uint32_t *bits_out, int32_t *blocks_out, hipStream_t stream)
 {
     const size_t lds = 8 * (size_t)a.lds_words;
-    if (lds > 64 * 1024) {  // what a launch may ask for without the attribute
-        static bool raised = false;
-        if (!raised) {
-            const hipError_t err =
-                hipFuncSetAttribute((const void *)k_frontier_tri<kF32>, hipFuncAttributeMaxDynamicSharedMemorySize, kMapLdsBytes);
-            if (err != hipSuccess) return (int)err;
-            raised = true;
-        }
-    }
-    hipLaunchKernelGGL((k_frontier_tri<kF32>), dim3((unsigned)(n * a.chunks)), dim3(kFrontLanes), lds, stream, tri, row_bytes, a, bits_out,
-                       blocks_out);
+    const int bad = map_raise_lds<k_frontier_tri<kF32>>(lds);
+    if (bad != 0) return bad;
+    hipLaunchKernelGGL((k_frontier_tri<kF32>), dim3((unsigned)(n * a.chunks)), dim3(kFrontLanes), lds, stream, grid.base, grid.row_bytes, a,
+                       bits_out, blocks_out);
     return gnbv_launch_status();
 }
 
@@ -161,12 +154,11 @@ int launch_frontier(const void *tri, int64_t row_bytes, const FrontierArgs &a, i
 GNBV_API int gnbv_frontier_tri(const int8_t *tri_i8, int64_t tri_i8_row_stride, const float *tri_f32, int64_t tri_f32_row_stride, int g,
                                int n, int block, uint32_t *bits_out, int32_t *blocks_out, int slab, void *stream)
 {
-    GNBV_CHECK_ARG((tri_i8 != nullptr) != (tri_f32 != nullptr));
+    MapGrid grid;
+    const int bad = map_grid(tri_i8, tri_i8_row_stride, tri_f32, tri_f32_row_stride, g, &grid);
+    if (bad != 0) return bad;
     GNBV_CHECK_ARG(blocks_out != nullptr);
-    GNBV_CHECK_ARG(n >= 1 && g >= 1 && g <= kMapMaxGrid && block >= 1 && block <= kFrontMaxBlock && slab >= 0);
-    const int64_t g3 = (int64_t)g * g * g;
-    const bool f32 = tri_f32 != nullptr;
-    GNBV_CHECK_ARG((f32 ? tri_f32_row_stride : tri_i8_row_stride) >= g3);
+    GNBV_CHECK_ARG(n >= 1 && block >= 1 && block <= kFrontMaxBlock && slab >= 0);
     // the slab height: a multiple of B (a block record has one writer), at most what the two planes leave of LDS, at least B
     // (B = 16 at 128^3 is 72 KiB).  Auto: the tallest that keeps the planes small and the workgroups many.
     const int whole = (g + block - 1) / block * block;
@@ -180,17 +172,14 @@ GNBV_API int gnbv_frontier_tri(const int8_t *tri_i8, int64_t tri_i8_row_stride, 
     FrontierArgs a;
     a.g = g;
     a.g2 = g * g;
-    a.g3 = (int)g3;
+    a.g3 = g * g * g;
     a.block = block;
     a.nb = (g + block - 1) / block;
     a.slab = s;
     a.chunks = (g + s - 1) / s;
-    a.words_out = (int)((g3 + 31) / 32);
+    a.words_out = (a.g3 + 31) / 32;
     a.lds_words = (int)frontier_plane_words(g, s);
     GNBV_CHECK_ARG((int64_t)n * a.chunks <= 0x7fffffff);
-    const void *tri = f32 ? static_cast<const void *>(tri_f32) : static_cast<const void *>(tri_i8);
-    const int64_t row_bytes = f32 ? 4 * tri_f32_row_stride : tri_i8_row_stride;
-    const hipStream_t st = gnbv_stream(stream);
-    return f32 ? launch_frontier<true>(tri, row_bytes, a, n, bits_out, blocks_out, st)
-               : launch_frontier<false>(tri, row_bytes, a, n, bits_out, blocks_out, st);
+    return grid.f32 ? launch_frontier<true>(grid, a, n, bits_out, blocks_out, gnbv_stream(stream))
+                    : launch_frontier<false>(grid, a, n, bits_out, blocks_out, gnbv_stream(stream));
 }

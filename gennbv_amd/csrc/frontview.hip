@@ -18,12 +18,15 @@
 //     3. per target a 64-bit key (field << 32 | node) reduced by minimum and the two counts by integer sum: across the wave by
 //        shuffles, then across the waves through LDS in wave order; lane 0 stores the four words.  Minimum and integer sums do not
 //        depend on the order; no global atomics, one writer per output element.
+//   The grid forms, the pack, the swizzle, the LDS limit, the (lds, f32) dispatch, the workgroups per env and the lattice check are
+//   map_bits.h's, shared with the other kernels on the map; the voxel frame is voxel_frame.h's, the all-lanes minimum common.h's.
 #include <algorithm>
 #include <cmath>
 
 #include "common.h"
 #include "map_bits.h"
 #include "ray_walk.h"
+#include "voxel_frame.h"
 #include "../../include/gennbv_hip.h"
 
 namespace {
@@ -34,12 +37,7 @@ constexpr int kViewScratchBytes = kViewWaves * 16;  // per wave: the key (8 byte
 constexpr unsigned long long kNoKey = ~0ull;
 constexpr uint32_t kNoRoute = 0xFFFFFFFFu;
 
-constexpr int view_lds_max_grid()
-{
-    int g = 1;
-    while (g < kMapMaxGrid && 2 * map_lds_bytes(g + 1) + kViewScratchBytes <= (size_t)kMapLdsBytes) ++g;
-    return g;
-}
+constexpr int view_lds_max_grid() { return map_lds_max_grid(2, kViewScratchBytes); }
 
 struct ViewArgs {
     int g, t, nx, ny, nz;
@@ -49,16 +47,6 @@ struct ViewArgs {
     double lo[3], h[3];
     double r_max, r2_min, r2_max;
 };
-
-__device__ __forceinline__ unsigned long long wave_min_all_u64(unsigned long long v)
-{
-#pragma unroll
-    for (int d = kWave / 2; d > 0; d >>= 1) {
-        const unsigned long long o = __shfl_xor(v, d, kWave);
-        v = o < v ? o : v;
-    }
-    return v;
-}
 
 // the nodes [i0, i1] of one axis that may lie within r of q: the exact range of |lo + h i - q| <= r is widened by one node and by
 // 2^-48 of the magnitudes over h (the rounding of lo + h i, of r * r against d2, and of this arithmetic), clamped in fp64 (a NaN
@@ -96,15 +84,13 @@ __global__ __launch_bounds__(kViewLanes) void k_frontview(const void *__restrict
         __syncthreads();
     }
 
-    // the voxel frame of gnbv_pose_to_idx: the subtraction in fp32
-    float rmin[3], vf[3];
     double o[3], v[3];
+    voxel_frame_f64(range_gt, voxel_size, e, o, v);
+    float rmin[3], vf[3];  // what axis_to_idx takes
 #pragma unroll
     for (int ax = 0; ax < 3; ++ax) {
         rmin[ax] = range_gt[e * 6 + 2 * ax + 1];
         vf[ax] = voxel_size[e * 3 + ax];
-        o[ax] = (double)__fsub_rn(rmin[ax], __fmul_rn(0.5f, vf[ax]));
-        v[ax] = (double)vf[ax];
     }
     const size_t m = (size_t)A.nx * A.ny * A.nz;
     const uint32_t *fld = field + (size_t)e * m;
@@ -164,7 +150,7 @@ __global__ __launch_bounds__(kViewLanes) void k_frontview(const void *__restrict
             }
         }
         // ---- 3. across the wave, then across the waves in wave order
-        key = wave_min_all_u64(key);
+        key = wave_min_all(key);
         n_see = wave_reduce_sum(n_see);
         n_route = wave_reduce_sum(n_route);
         if (lane == 0) {
@@ -191,18 +177,11 @@ __global__ __launch_bounds__(kViewLanes) void k_frontview(const void *__restrict
 }
 
 template <bool kLds, bool kF32>
-int launch_view(const void *tri, int64_t row_bytes, const GnbvFrontView &a, const ViewArgs &A, size_t lds, hipStream_t stream)
+int launch_view(const MapGrid &grid, const GnbvFrontView &a, const ViewArgs &A, size_t lds, hipStream_t stream)
 {
-    if (lds > 64 * 1024) {  // what a launch may ask for without the attribute
-        static bool raised = false;
-        if (!raised) {
-            const hipError_t err = hipFuncSetAttribute((const void *)k_frontview<kLds, kF32>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                       kMapLdsBytes);
-            if (err != hipSuccess) return (int)err;
-            raised = true;
-        }
-    }
-    hipLaunchKernelGGL((k_frontview<kLds, kF32>), dim3((unsigned)(a.n * A.chunks)), dim3(kViewLanes), lds, stream, tri, row_bytes,
+    const int bad = map_raise_lds<k_frontview<kLds, kF32>>(lds);
+    if (bad != 0) return bad;
+    hipLaunchKernelGGL((k_frontview<kLds, kF32>), dim3((unsigned)(a.n * A.chunks)), dim3(kViewLanes), lds, stream, grid.base, grid.row_bytes,
                        a.range_gt, a.voxel_size, a.field, a.targets, A, a.node_out, a.cost_out, a.count_out);
     return gnbv_launch_status();
 }
@@ -215,19 +194,14 @@ GNBV_API int gnbv_frontier_viewpoints(const GnbvFrontView *args, void *stream)
 {
     GNBV_CHECK_ARG(args != nullptr);
     const GnbvFrontView a = *args;
-    GNBV_CHECK_ARG((a.tri_i8 != nullptr) != (a.tri_f32 != nullptr));
+    MapGrid grid;
+    const int bad = map_grid(a.tri_i8, a.tri_i8_row_stride, a.tri_f32, a.tri_f32_row_stride, a.g, &grid);
+    if (bad != 0) return bad;
     GNBV_CHECK_ARG(a.range_gt != nullptr && a.voxel_size != nullptr && a.field != nullptr && a.targets != nullptr);
     GNBV_CHECK_ARG(a.node_out != nullptr && a.cost_out != nullptr && a.count_out != nullptr);
     GNBV_CHECK_ARG(a.n >= 1 && a.t >= 1 && (int64_t)a.n * a.t <= 0x7fffffff);
-    GNBV_CHECK_ARG(a.g >= 1 && a.g <= kMapMaxGrid && a.mode >= 0 && a.mode <= 2 && a.chunk >= 0 && a.max_unknown >= 0);
-    const int64_t g3 = (int64_t)a.g * a.g * a.g;
-    const bool f32 = a.tri_f32 != nullptr;
-    GNBV_CHECK_ARG((f32 ? a.tri_f32_row_stride : a.tri_i8_row_stride) >= g3);
-    const int dims[3] = {a.nx, a.ny, a.nz};
-    for (int ax = 0; ax < 3; ++ax) {
-        GNBV_CHECK_ARG(dims[ax] >= 1 && dims[ax] <= 1024);
-        GNBV_CHECK_ARG(std::isfinite(a.lo[ax]) && std::isfinite(a.h[ax]) && (dims[ax] == 1 || a.h[ax] > 0.0));
-    }
+    GNBV_CHECK_ARG(a.mode >= 0 && a.mode <= 2 && a.chunk >= 0 && a.max_unknown >= 0);
+    GNBV_CHECK_ARG(lattice_ok(a.nx, a.ny, a.nz, a.lo, a.h));
     GNBV_CHECK_ARG(std::isfinite(a.r_min) && std::isfinite(a.r_max) && a.r_min >= 0.0 && a.r_max > 0.0 && a.r_min <= a.r_max);
     const bool fits = a.g <= view_lds_max_grid();
     GNBV_CHECK_ARG(a.mode != 1 || fits);
@@ -238,16 +212,13 @@ GNBV_API int gnbv_frontier_viewpoints(const GnbvFrontView *args, void *stream)
     A.g = a.g;
     A.t = a.t;
     A.nx = a.nx; A.ny = a.ny; A.nz = a.nz;
-    // targets per workgroup: one where the grid is read in place; with the planes in LDS every workgroup pays for packing the whole
-    // grid, so an env gets only as many workgroups as it takes to reach about two per CU over all envs
-    int chunk = a.chunk;
-    if (chunk == 0) {
-        const int want = lds ? std::max(1, (512 + a.n - 1) / a.n) : a.t;  // workgroups per env
-        chunk = (a.t + want - 1) / want;
+    MapChunks ch = map_chunks(a.t, 1, a.n, lds);  // the items: targets, one per workgroup and turn
+    if (a.chunk > 0) {                            // the caller's targets per workgroup
+        ch.per = std::min(a.chunk, a.t);
+        ch.chunks = (a.t + ch.per - 1) / ch.per;
     }
-    chunk = chunk < 1 ? 1 : (chunk > a.t ? a.t : chunk);
-    A.chunk_items = chunk;
-    A.chunks = (a.t + chunk - 1) / chunk;
+    A.chunk_items = ch.per;
+    A.chunks = ch.chunks;
     GNBV_CHECK_ARG((int64_t)a.n * A.chunks <= 0x7fffffff);
     A.shift = map_swizzle_shift(a.g);
     A.plane_words = lds ? (int)(map_lds_bytes(a.g) / 4) : 0;
@@ -259,11 +230,8 @@ GNBV_API int gnbv_frontier_viewpoints(const GnbvFrontView *args, void *stream)
     A.r_max = a.r_max;
     A.r2_min = a.r_min * a.r_min;
     A.r2_max = a.r_max * a.r_max;
-    const void *tri = f32 ? static_cast<const void *>(a.tri_f32) : static_cast<const void *>(a.tri_i8);
-    const int64_t row_bytes = f32 ? 4 * a.tri_f32_row_stride : a.tri_i8_row_stride;
-    const hipStream_t s = gnbv_stream(stream);
     const size_t bytes = kViewScratchBytes + (lds ? 2 * map_lds_bytes(a.g) : 0);
-    if (lds)
-        return f32 ? launch_view<true, true>(tri, row_bytes, a, A, bytes, s) : launch_view<true, false>(tri, row_bytes, a, A, bytes, s);
-    return f32 ? launch_view<false, true>(tri, row_bytes, a, A, bytes, s) : launch_view<false, false>(tri, row_bytes, a, A, bytes, s);
+    return map_dispatch(lds, grid.f32, [&](auto kLds, auto kF32) {
+        return launch_view<decltype(kLds)::value, decltype(kF32)::value>(grid, a, A, bytes, gnbv_stream(stream));
+    });
 }

@@ -8,14 +8,14 @@
 #pragma once
 
 #include "common.h"
+#include "voxel_frame.h"
 
 constexpr float kCoordClamp = 16777216.0f;  // voxel coordinates saturate at +-2^24: the 64-bit closed form stays exact
 
 // unclamped pose_to_idx of one axis (k_pose_to_idx): floor((p - (range_min - 0.5 v)) / v), IEEE division
 __device__ __forceinline__ int axis_to_idx(float p, float range_min, float v)
 {
-    const float vmin = __fsub_rn(range_min, __fmul_rn(0.5f, v));
-    const float fl = floorf(__fdiv_rn(__fsub_rn(p, vmin), v));
+    const float fl = floorf(__fdiv_rn(__fsub_rn(p, frame_min(range_min, v)), v));
     if (!(fl == fl)) return 0;
     return (int)fminf(fmaxf(fl, -kCoordClamp), kCoordClamp);
 }

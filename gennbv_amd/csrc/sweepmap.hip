@@ -10,7 +10,9 @@
 //   bit 1 (2, OUTSIDE)  outside_blocks and on some axis min(a, b) - R < o or max(a, b) + R > o + (double)G v
 //   bit 2 (4, GROUND)   ground and min(a_z, b_z) - R <= 0
 //
-// An item with a non-finite coordinate gets 0.  The voxel frame is gnbv_pose_to_idx's (o = fp32(range_min - fp32(0.5f v))).
+// An item with a non-finite coordinate gets 0.  The voxel frame is gnbv_pose_to_idx's (voxel_frame.h: voxel_frame_f64).  The grid
+// forms, the LDS pack and swizzle, the span of a word, the LDS limit, the (lds, f32) dispatch and the workgroups per env are
+// map_bits.h's, shared with the other kernels on the map.
 //
 //   k_sweep_tri<kLds, kF32>   workgroup (env, chunk of the env's K items), 512 lanes, a wave owns an item at a time; the work
 //     follows the segment, as in sweep.hip:
@@ -24,15 +26,15 @@
 //        previous piece's lanes, against the WHOLE segment;
 //     3. the bit first, then the geometry: only a voxel that blocks gets the fp64 predicate, free space costs no arithmetic;
 //     4. the whole wave leaves at the first hit (__any, once per 64 pairs); lane 0 stores the byte.  No atomics, no workspace.
-//     kLds (mode 1): the workgroup first packs "this voxel blocks" into one bit per voxel in LDS (map_bits.h: flightmap.hip's pack
-//       and bank swizzle) and amortises that over its items; a z-run is read as whole words and a zero word is skipped.
+//     kLds (mode 1): the workgroup first packs "this voxel blocks" into one bit per voxel in LDS (map_bits.h: the pack and the bank
+//       swizzle) and amortises that over its items; a z-run is read as whole words and a zero word is skipped.
 //     !kLds (mode 2): the same decisions with the voxels read from global memory (up to 128^3).
-#include <algorithm>
 #include <cmath>
 
 #include "common.h"
 #include "map_bits.h"
 #include "seg_box.h"
+#include "voxel_frame.h"
 #include "../../include/gennbv_hip.h"
 
 namespace {
@@ -153,9 +155,7 @@ __device__ __forceinline__ bool leg_touches_map(const SweepMapArgs &A, const dou
                     if (kLds) {
                         const int b0 = base + z0, b1 = base + z1;
                         for (int wd = b0 >> 5; wd <= (b1 >> 5) && !hit; ++wd) {
-                            const int first = max(b0, wd << 5), last = min(b1, (wd << 5) + 31);
-                            const uint32_t span = (0xFFFFFFFFu >> (31 - (last - first))) << (first & 31);
-                            uint32_t word = bits[map_swizzle(wd, A.shift)] & span;
+                            uint32_t word = bits[map_swizzle(wd, A.shift)] & map_span(wd, b0, b1);
                             while (word != 0u) {
                                 const int z = (wd << 5) + __builtin_ctz(word) - base;
                                 word &= word - 1u;
@@ -203,14 +203,8 @@ __global__ __launch_bounds__(kSweepLanes) void k_sweep_tri(const void *__restric
         __syncthreads();
     }
 
-    // the voxel frame of gnbv_pose_to_idx: the subtraction in fp32
     double o[3], v[3];
-#pragma unroll
-    for (int ax = 0; ax < 3; ++ax) {
-        const float vf = voxel_size[e * 3 + ax];
-        o[ax] = (double)__fsub_rn(range_gt[e * 6 + 2 * ax + 1], __fmul_rn(0.5f, vf));
-        v[ax] = (double)vf;
-    }
+    voxel_frame_f64(range_gt, voxel_size, e, o, v);
 
     for (int t = wave; t < A.chunk_items; t += kSweepWaves) {  // (no barrier below: a wave may leave alone)
         const int j = chunk * A.chunk_items + t;
@@ -235,20 +229,13 @@ __global__ __launch_bounds__(kSweepLanes) void k_sweep_tri(const void *__restric
 }
 
 template <bool kLds, bool kF32>
-int launch_sweep(const void *tri, int64_t row_bytes, const float *range_gt, const float *voxel_size, const float *from, const float *to,
-                 const SweepMapArgs &A, int n, size_t lds, uint8_t *code_out, hipStream_t stream)
+int launch_sweep(const MapGrid &grid, const float *range_gt, const float *voxel_size, const float *from, const float *to, const SweepMapArgs &A,
+                 int n, size_t lds, uint8_t *code_out, hipStream_t stream)
 {
-    if (kLds && lds > 64 * 1024) {  // what a launch may ask for without the attribute
-        static bool raised = false;
-        if (!raised) {
-            const hipError_t err = hipFuncSetAttribute((const void *)k_sweep_tri<kLds, kF32>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                       kMapLdsBytes);
-            if (err != hipSuccess) return (int)err;
-            raised = true;
-        }
-    }
-    hipLaunchKernelGGL((k_sweep_tri<kLds, kF32>), dim3((unsigned)(n * A.chunks)), dim3(kSweepLanes), lds, stream, tri, row_bytes, range_gt,
-                       voxel_size, from, to, A, code_out);
+    const int bad = map_raise_lds<k_sweep_tri<kLds, kF32>>(lds);
+    if (bad != 0) return bad;
+    hipLaunchKernelGGL((k_sweep_tri<kLds, kF32>), dim3((unsigned)(n * A.chunks)), dim3(kSweepLanes), lds, stream, grid.base, grid.row_bytes,
+                       range_gt, voxel_size, from, to, A, code_out);
     return gnbv_launch_status();
 }
 
@@ -261,13 +248,12 @@ GNBV_API int gnbv_sweep_tri(const int8_t *tri_i8, int64_t tri_i8_row_stride, con
                             int64_t from_item_stride, const float *to, int k, int64_t to_row_stride, double radius, int unknown_blocks,
                             int outside_blocks, int ground, uint8_t *code_out, int mode, void *stream)
 {
-    GNBV_CHECK_ARG((tri_i8 != nullptr) != (tri_f32 != nullptr));
+    MapGrid grid;
+    const int bad = map_grid(tri_i8, tri_i8_row_stride, tri_f32, tri_f32_row_stride, g, &grid);
+    if (bad != 0) return bad;
     GNBV_CHECK_ARG(range_gt != nullptr && voxel_size != nullptr && from != nullptr && to != nullptr && code_out != nullptr);
-    GNBV_CHECK_ARG(n >= 1 && k >= 1 && g >= 1 && g <= kMapMaxGrid && mode >= 0 && mode <= 2);
+    GNBV_CHECK_ARG(n >= 1 && k >= 1 && mode >= 0 && mode <= 2);
     GNBV_CHECK_ARG(std::isfinite(radius) && radius > 0.0);
-    const int64_t g3 = (int64_t)g * g * g;
-    const bool f32 = tri_f32 != nullptr;
-    GNBV_CHECK_ARG((f32 ? tri_f32_row_stride : tri_i8_row_stride) >= g3);
     GNBV_CHECK_ARG(to_row_stride >= 3 && from_env_stride >= 3 && (from_item_stride == 0 || from_item_stride >= 3));
     const bool fits = g <= map_lds_max_grid();
     GNBV_CHECK_ARG(mode != 1 || fits);
@@ -275,12 +261,9 @@ GNBV_API int gnbv_sweep_tri(const int8_t *tri_i8, int64_t tri_i8_row_stride, con
     SweepMapArgs A;
     A.g = g;
     A.k = k;
-    // items per workgroup: one per wave where the grid is read in place; with the bits in LDS every workgroup pays for packing the
-    // whole grid, so an env gets only as many workgroups as it takes to reach about two per CU over all envs
-    int64_t chunks = ((int64_t)k + kSweepWaves - 1) / kSweepWaves;
-    if (lds) chunks = std::min<int64_t>(chunks, std::max<int64_t>(1, (512 + n - 1) / n));
-    A.chunk_items = (int)(((int64_t)k + chunks - 1) / chunks);
-    A.chunks = (int)(((int64_t)k + A.chunk_items - 1) / A.chunk_items);
+    const MapChunks ch = map_chunks(k, kSweepWaves, n, lds);  // the items: legs, one per wave and turn
+    A.chunks = ch.chunks;
+    A.chunk_items = ch.per;
     GNBV_CHECK_ARG((int64_t)n * A.chunks <= 0x7fffffff && (int64_t)n * k <= 0x7fffffff);
     A.shift = map_swizzle_shift(g);
     A.unknown_blocks = unknown_blocks != 0;
@@ -291,14 +274,9 @@ GNBV_API int gnbv_sweep_tri(const int8_t *tri_i8, int64_t tri_i8_row_stride, con
     A.to_row_stride = to_row_stride;
     A.radius = radius;
     A.r2 = radius * radius;
-    const void *tri = f32 ? static_cast<const void *>(tri_f32) : static_cast<const void *>(tri_i8);
-    const int64_t row_bytes = f32 ? 4 * tri_f32_row_stride : tri_i8_row_stride;
-    const hipStream_t s = gnbv_stream(stream);
-    if (lds) {
-        const size_t bytes = map_lds_bytes(g);
-        return f32 ? launch_sweep<true, true>(tri, row_bytes, range_gt, voxel_size, from, to, A, n, bytes, code_out, s)
-                   : launch_sweep<true, false>(tri, row_bytes, range_gt, voxel_size, from, to, A, n, bytes, code_out, s);
-    }
-    return f32 ? launch_sweep<false, true>(tri, row_bytes, range_gt, voxel_size, from, to, A, n, 0, code_out, s)
-               : launch_sweep<false, false>(tri, row_bytes, range_gt, voxel_size, from, to, A, n, 0, code_out, s);
+    const size_t bytes = lds ? map_lds_bytes(g) : 0;
+    return map_dispatch(lds, grid.f32, [&](auto kLds, auto kF32) {
+        return launch_sweep<decltype(kLds)::value, decltype(kF32)::value>(grid, range_gt, voxel_size, from, to, A, n, bytes, code_out,
+                                                                          gnbv_stream(stream));
+    });
 }

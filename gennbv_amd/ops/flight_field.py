@@ -338,11 +338,9 @@ class BeliefFlightField(FlightField):
         and `costly_map`): tri [N, >= G^3] int8 or float32, unit element stride, any row stride (e.g.
         obs[:, state_dim:state_dim + grid_dim])."""
         n, g3 = self.num_envs, self.grid_size ** 3
-        row = self._check_tri(tri, "refresh")
-        i8 = tri.dtype == torch.int8
         nx, ny, nz = self.lattice.dims
-        head = (tri.data_ptr() if i8 else None, row if i8 else 0, None if i8 else tri.data_ptr(), 0 if i8 else row, self.grid_size,
-                self.range_gt.data_ptr(), self.voxel_size.data_ptr(), n, nx, ny, nz, self._lo, self._h, self.rho)
+        head = (*_lib.tri_args(tri, n, g3, "BeliefFlightField.refresh"), self.grid_size, self.range_gt.data_ptr(),
+                self.voxel_size.data_ptr(), n, nx, ny, nz, self._lo, self._h, self.rho)
         flags = (int(self.outside_blocks), int(bool(self.body.ground)))
         tail = (self.map_mode, _lib.stream_ptr(self.device))
         if self.costly_map is None:
@@ -353,7 +351,7 @@ class BeliefFlightField(FlightField):
                        "gnbv_flight_classify_tri")
         self.refreshes += 1
         if self.shortcut:
-            self.map_i8.copy_(tri[:, :g3] if i8 else torch.sign(tri[:, :g3]))
+            self.map_i8.copy_(tri[:, :g3] if tri.dtype == torch.int8 else torch.sign(tri[:, :g3]))
             self.has_map = True
         return self
 
@@ -374,15 +372,6 @@ class BeliefFlightField(FlightField):
         inside = torch.arange(nodes.shape[1], device=self.device)[None] < (count[:, None].long() - 1)
         return (self.costly_at(nodes) & inside).sum(dim=1)
 
-    def _check_tri(self, tri: torch.Tensor, what: str) -> int:
-        """The tensor checks of refresh() and sweep(); returns the row stride in elements."""
-        n, g3 = self.num_envs, self.grid_size ** 3
-        _lib.require_cuda(tri)
-        if tri.dtype not in (torch.int8, torch.float32) or tri.dim() != 2 or tri.shape[0] != n or tri.shape[1] < g3 or tri.stride(1) != 1:
-            raise _lib.GennbvHipError(f"BeliefFlightField.{what}: tri must be int8 or float32 [{n}, >= {g3}] with unit element stride, "
-                                      f"got {tri.dtype} {tuple(tri.shape)} strides {tuple(tri.stride())}")
-        return int(tri.stride(0)) if n > 1 else max(int(tri.stride(0)), g3)
-
     def sweep(self, from_poses: torch.Tensor, to_poses: torch.Tensor, tri: Optional[torch.Tensor] = None, radius: Optional[float] = None,
               out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One gnbv_sweep_tri launch on the current stream: uint8 [N,K], the code (1 MAP | 2 OUTSIDE | 4 GROUND) of the sphere of
@@ -395,7 +384,7 @@ class BeliefFlightField(FlightField):
             if not (self.shortcut and self.has_map):
                 raise _lib.GennbvHipError("BeliefFlightField.sweep: no map snapshot (shortcut=True and a refresh()) and no tri given")
             tri = self.map_i8
-        row = self._check_tri(tri, "sweep")
+        grid = _lib.tri_args(tri, n, self.grid_size ** 3, "BeliefFlightField.sweep")
         r = self.sweep_radius if radius is None else float(radius)
         if not (np.isfinite(r) and r > 0.0):
             raise ValueError(f"BeliefFlightField.sweep: radius must be finite and > 0, got {radius}")
@@ -414,9 +403,7 @@ class BeliefFlightField(FlightField):
             out = torch.empty(n, k, dtype=torch.uint8, device=self.device)
         _lib.require_cuda(out)
         assert out.dtype == torch.uint8 and out.shape == (n, k) and out.is_contiguous()
-        i8 = tri.dtype == torch.int8
-        _lib.check(self.lib.gnbv_sweep_tri(tri.data_ptr() if i8 else None, row if i8 else 0, None if i8 else tri.data_ptr(), 0 if i8 else row,
-                                           self.grid_size, self.range_gt.data_ptr(), self.voxel_size.data_ptr(), n, from_poses.data_ptr(),
+        _lib.check(self.lib.gnbv_sweep_tri(*grid, self.grid_size, self.range_gt.data_ptr(), self.voxel_size.data_ptr(), n, from_poses.data_ptr(),
                                            f_env, f_item, to_poses.data_ptr(), k, to_row, r, int(self.unknown_blocks),
                                            int(self.outside_blocks), int(bool(self.body.ground)), out.data_ptr(), self.map_mode,
                                            _lib.stream_ptr(self.device)), "gnbv_sweep_tri")

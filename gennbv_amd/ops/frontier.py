@@ -68,15 +68,8 @@ class Frontier:
     def __call__(self, tri: torch.Tensor) -> torch.Tensor:
         """One gnbv_frontier_tri launch on the current stream into `blocks` (and `bits`); returns `blocks`."""
         n, g3 = self.num_envs, self.grid_size ** 3
-        _lib.require_cuda(tri)
-        if tri.dtype not in (torch.int8, torch.float32) or tri.dim() != 2 or tri.shape[0] != n or tri.shape[1] < g3 or tri.stride(1) != 1:
-            raise _lib.GennbvHipError(f"Frontier: tri must be int8 or float32 [{n}, >= {g3}] with unit element stride, got {tri.dtype} "
-                                      f"{tuple(tri.shape)} strides {tuple(tri.stride())}")
-        row = int(tri.stride(0)) if n > 1 else max(int(tri.stride(0)), g3)
-        i8 = tri.dtype == torch.int8
-        _lib.check(self.lib.gnbv_frontier_tri(tri.data_ptr() if i8 else None, row if i8 else 0, None if i8 else tri.data_ptr(),
-                                              0 if i8 else row, self.grid_size, n, self.block, _lib.ptr(self.bits), self.blocks.data_ptr(),
-                                              self.slab, _lib.stream_ptr(self.device)), "gnbv_frontier_tri")
+        _lib.check(self.lib.gnbv_frontier_tri(*_lib.tri_args(tri, n, g3, "Frontier"), self.grid_size, n, self.block, _lib.ptr(self.bits),
+                                              self.blocks.data_ptr(), self.slab, _lib.stream_ptr(self.device)), "gnbv_frontier_tri")
         self.launches += 1
         return self.blocks
 

@@ -97,10 +97,7 @@ class FrontierViewpoints:
         """One gnbv_frontier_viewpoints launch on the current stream into `node`, `cost_mm`, `count`; returns the three."""
         n, g3, t = self.num_envs, self.grid_size ** 3, self.targets
         m = int(self.lattice.num_nodes)
-        _lib.require_cuda(tri)
-        if tri.dtype not in (torch.int8, torch.float32) or tri.dim() != 2 or tri.shape[0] != n or tri.shape[1] < g3 or tri.stride(1) != 1:
-            raise _lib.GennbvHipError(f"FrontierViewpoints: tri must be int8 or float32 [{n}, >= {g3}] with unit element stride, got "
-                                      f"{tri.dtype} {tuple(tri.shape)} strides {tuple(tri.stride())}")
+        tri_i8, tri_i8_row, tri_f32, tri_f32_row = _lib.tri_args(tri, n, g3, "FrontierViewpoints")
         field = getattr(field, "field", field)
         _lib.require_cuda(field)
         if field.dtype != torch.int32 or field.shape != (n, m) or not field.is_contiguous():
@@ -110,11 +107,9 @@ class FrontierViewpoints:
         if target_vox.dtype != torch.int32 or target_vox.shape != (n, t, 3) or not target_vox.is_contiguous():
             raise _lib.GennbvHipError(f"FrontierViewpoints: target_vox must be a contiguous int32 [{n}, {t}, 3] tensor, got "
                                       f"{target_vox.dtype} {tuple(target_vox.shape)}")
-        row = int(tri.stride(0)) if n > 1 else max(int(tri.stride(0)), g3)
-        i8 = tri.dtype == torch.int8
         nx, ny, nz = self.lattice.dims
-        a = _lib.GnbvFrontView(n=n, t=t, g=self.grid_size, tri_i8=tri.data_ptr() if i8 else None, tri_i8_row_stride=row if i8 else 0,
-                               tri_f32=None if i8 else tri.data_ptr(), tri_f32_row_stride=0 if i8 else row,
+        a = _lib.GnbvFrontView(n=n, t=t, g=self.grid_size, tri_i8=tri_i8, tri_i8_row_stride=tri_i8_row, tri_f32=tri_f32,
+                               tri_f32_row_stride=tri_f32_row,
                                range_gt=self.range_gt.data_ptr(), voxel_size=self.voxel_size.data_ptr(), nx=nx, ny=ny, nz=nz,
                                lo=(_lib.C.c_double * 3)(*[float(v) for v in self.lattice.lo]),
                                h=(_lib.C.c_double * 3)(*[float(v) for v in self.lattice.h]), field=field.data_ptr(),
