@@ -122,6 +122,7 @@ SIGNATURES = {
     "gnbv_view_cover": (_i, [_p, _p, _p]),
     "gnbv_view_cover_masks": (_i, [_p, _p, _p, _p]),
     "gnbv_cover_greedy": (_i, [_p, _p]),
+    "gnbv_cover_greedy_w": (_i, [_p, _p]),
     "gnbv_tour_route": (_i, [_p, _p]),
     "gnbv_gae_sb3": (_i, [_p, _p, _p, _p, _p, _i, _i, _d, _d, _p, _p, _p]),
     "gnbv_gae_rsl": (_i, [_p, _p, _p, _p, _i, _i, _d, _d, _p, _p, _p]),
@@ -193,6 +194,13 @@ class GnbvCoverGreedy(C.Structure):
     """include/gennbv_hip.h: GnbvCoverGreedy"""
     _fields_ = [("n", _i), ("k", _i), ("words", _i), ("rounds", _i), ("mask_bits", _p), ("covered_in", _p), ("contact", _p),
                 ("choice", _p), ("gain", _p), ("covered_out", _p), ("gains0", _p), ("ub", _p), ("lazy", _i)]
+
+
+class GnbvCoverGreedyW(C.Structure):
+    """include/gennbv_hip.h: GnbvCoverGreedyW"""
+    _fields_ = [("n", _i), ("k", _i), ("words", _i), ("rounds", _i), ("planes", _i), ("weight", _i * 4), ("mask_bits", _p * 4),
+                ("covered_in", _p * 4), ("covered_out", _p * 4), ("contact", _p), ("choice", _p), ("gain", _p), ("plane_gain", _p),
+                ("gains0", _p), ("ub", _p), ("lazy", _i)]
 
 
 class GnbvTourRoute(C.Structure):

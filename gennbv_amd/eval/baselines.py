@@ -345,28 +345,42 @@ class MapCoverPolicy(MapGreedyPolicy):
     commit = 1 is receding-horizon control: fly the first view of a plan whose views do not overlap, then plan again.
     commit = horizon with `route` is plan-then-fly on the map.  horizon = 1 chooses what MapGreedyPolicy chooses with weights
     (1, 0) for mask "unknown" and (0, 1) for mask "hit".
+    mask = "mixed" with `weights` = (w_unknown, w_hit) (None: (1, 4); integers >= 0; refused with the other masks) plans under
+    MapGreedyPolicy's own score: both masks are kept and step 1 is `plan_weighted(horizon, weights=weights, contact=...)`,
+    gnbv_cover_greedy_w's weighted set cover against two covered sets that grow together; `last_gain` is then the weighted score
+    and `last_plane_gain` int32 [N,horizon,2] the winners' (unknown, hit) gains (None with the other masks).  Steps 2 to 5 do not
+    change.  horizon = 1 with "mixed" and weights w chooses what MapGreedyPolicy(weights=w) chooses.
     The last decision's plan, for every env whether adopted or not: `last_choice`, `last_gain` int32 [N,horizon] (the plan's
     integers, gain order), `last_views` int64 [N], `last_actions` int64 [N,horizon,6] (the views in flight order; the tail repeats
     the last), `last_length_mm` int64 [N] (the tour from env.poses; -1 without route), `last_gain3` [N,K,3] (the view gain),
-    `adopted` bool [N].  `masks_backend` (an object with ViewGainMasks' `__call__` and `plan`) and `tour_backend`
+    `adopted` bool [N].  `masks_backend` (an object with ViewGainMasks' `__call__` and `plan`; `plan_weighted` and `plane_gain` for "mixed") and `tour_backend`
     (`route_tour`'s signature) replace the kernels in tests only: the product path has no CPU fallback."""
 
     def __init__(self, env, k: int = 32, horizon: int = 3, commit: int = 1, mask: str = "hit", route: bool = False, seed: int = 0,
                  stride: int = 4, look_at_scene: bool = False, shortcut: Optional[bool] = None, max_cost_m: Optional[float] = None,
-                 candidates=None, masks_backend=None, tour_backend: Optional[Callable] = None):
+                 candidates=None, masks_backend=None, tour_backend: Optional[Callable] = None, weights=None):
         horizon, commit = int(horizon), int(commit)
         if not 1 <= horizon <= 16:
             raise ValueError(f"MapCoverPolicy: horizon must be in 1..16, got {horizon}")
         if not 1 <= commit <= horizon:
             raise ValueError(f"MapCoverPolicy: commit must be in 1..horizon = {horizon}, got {commit}")
-        if mask not in ("hit", "unknown"):
-            raise ValueError(f"MapCoverPolicy: mask must be 'hit' or 'unknown', got {mask!r}")
+        if mask not in ("hit", "unknown", "mixed"):
+            raise ValueError(f"MapCoverPolicy: mask must be 'hit', 'unknown' or 'mixed', got {mask!r}")
+        mixed = mask == "mixed"
+        if weights is not None and not mixed:
+            raise ValueError(f"MapCoverPolicy: weights belong to mask='mixed'; mask={mask!r} is the plan of one mask")
+        if mixed:
+            weights = (1, 4) if weights is None else tuple(weights)
+            if len(weights) != 2 or any(int(w) != w or int(w) < 0 for w in weights):
+                raise ValueError(f"MapCoverPolicy: weights must be two integers >= 0 (w_unknown, w_hit), got {weights!r}")
+        else:
+            weights = (1, 0) if mask == "unknown" else (0, 1)
         if masks_backend is None:
             from ..ops.gain_masks import ViewGainMasks
             u = env.updater
             masks_backend = ViewGainMasks(int(env.num_envs), int(k), env.cfg, u.range_gt, u.voxel_size_gt, inv_intrinsics=u.inv_intri_host,
-                                          stride=stride, device=env.device, hit=mask == "hit", unknown=mask == "unknown")
-        super().__init__(env, k=k, weights=(1, 0) if mask == "unknown" else (0, 1), seed=seed, stride=stride, look_at_scene=look_at_scene,
+                                          stride=stride, device=env.device, hit=mixed or mask == "hit", unknown=mixed or mask == "unknown")
+        super().__init__(env, k=k, weights=weights, seed=seed, stride=stride, look_at_scene=look_at_scene,
                          gain_backend=masks_backend, shortcut=shortcut, max_cost_m=max_cost_m, candidates=candidates)
         self.horizon, self.commit, self.mask, self.route = horizon, commit, mask, bool(route)
         self.tour_backend = tour_backend
@@ -379,6 +393,7 @@ class MapCoverPolicy(MapGreedyPolicy):
         self._points = torch.empty(n, horizon + 1, 3, dtype=torch.float32, device=dev)
         self._no_length = torch.full((n,), -1, dtype=torch.int64, device=dev)
         self.last_choice = self.last_gain = self.last_views = self.last_actions = self.last_length_mm = self.last_gain3 = self.adopted = None
+        self.last_plane_gain = None
 
     def __call__(self, obs, deterministic: bool = True):
         cfg, n, t_max = self.cfg, self.num_envs, self.horizon
@@ -391,7 +406,11 @@ class MapCoverPolicy(MapGreedyPolicy):
         if self._contact is None:
             self._contact = torch.zeros(n, self.k, dtype=torch.uint8, device=obs.device)
         contact = self.contact(poses)
-        choice, gain, _ = self.gain_backend.plan(t_max, which=self.mask, contact=contact)
+        if self.mask == "mixed":
+            choice, gain, _ = self.gain_backend.plan_weighted(t_max, weights=self.weights, contact=contact)
+            self.last_plane_gain = self.gain_backend.plane_gain
+        else:
+            choice, gain, _ = self.gain_backend.plan(t_max, which=self.mask, contact=contact)
         self.last_choice, self.last_gain = choice, gain
         choice64 = choice.long()
         # ---- 2. keep: the kept rounds to the front, in plan order (a stable sort on a 0 / 1 key)

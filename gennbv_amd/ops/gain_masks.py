@@ -5,7 +5,9 @@ ViewGain reduces, per candidate, the set of unknown voxels its rays would cross 
 the SAME unknown voxels both look good.  ViewGainMasks runs the same kernel and also stores the two sets as bit masks --
 `unknown_bits` (every ray) and `hit_bits` (the rays that meet a surface), int32 [N, K, words] in the layout of the updater's
 scanned_bits and of gnbv_cover_greedy (bit lin & 31 of word lin >> 5, lin = (x G + y) G + z) -- so that `plan(T)` can pick T views
-that add DIFFERENT voxels: the classic greedy set cover, on the map the pilot holds and nothing else.  Integers with one right
+that add DIFFERENT voxels: the classic greedy set cover, on the map the pilot holds and nothing else; `plan_weighted(T, weights)`
+is the same under the greedy planners' score w_unknown * new unknown voxels + w_hit * new hit voxels, on both masks at once
+(csrc/covergreedy.hip gnbv_cover_greedy_w).  Integers with one right
 answer (include/gennbv_hip.h has the exact definitions).  Outputs are preallocated and reused: a result is valid until the next
 call of the same method.  No host synchronisation in either call.  GPU only, no CPU fallback; grid_size <= 64.
 """
@@ -19,6 +21,23 @@ import torch
 from .. import _lib
 from ..env.config import TaskConfig
 from .view_gain import MAX_GRID, ViewGain
+
+
+def plan_weights(weights, words: int):
+    """(w_unknown, w_hit) as two ints, or a GennbvHipError with the reason: what gnbv_cover_greedy_w refuses for its weights."""
+    try:
+        w = tuple(int(x) for x in weights)
+        whole = all(x == y for x, y in zip(w, weights))
+    except (TypeError, ValueError):
+        w, whole = (), False
+    if len(w) != 2 or not whole:
+        raise _lib.GennbvHipError(f"ViewGainMasks.plan_weighted: weights must be two integers (w_unknown, w_hit), got {weights!r}")
+    if min(w) < 0:
+        raise _lib.GennbvHipError(f"ViewGainMasks.plan_weighted: weights must be >= 0, got {w}")
+    if sum(w) * 32 * int(words) > 2 ** 31 - 1:
+        raise _lib.GennbvHipError(f"ViewGainMasks.plan_weighted: (w_unknown + w_hit) * 32 * words = {sum(w) * 32 * int(words)} exceeds "
+                                  f"2^31 - 1 (weights {w}, {int(words)} words): a score would not fit in int32")
+    return w
 
 
 class ViewGainMasks(ViewGain):
@@ -58,6 +77,11 @@ class ViewGainMasks(ViewGain):
         c = _lib.GnbvCoverGreedy()
         c.n, c.k, c.words = n, k, self.words
         self._cg = c
+        self._plans_w = {}  # rounds -> (choice, gain, (covered_unknown, covered_hit), plane_gain): plan_weighted's own
+        self.plane_gain = None
+        cw = _lib.GnbvCoverGreedyW()
+        cw.n, cw.k, cw.words, cw.planes = n, k, self.words, 2
+        self._cgw = cw
 
     def _launch(self, a):
         _lib.check(self.lib.gnbv_view_gain_masks(C.byref(a), self.words, _lib.ptr(self.unknown_bits), _lib.ptr(self.hit_bits),
@@ -98,4 +122,48 @@ class ViewGainMasks(ViewGain):
         c.choice, c.gain, c.covered_out, c.gains0, c.ub, c.lazy = (choice.data_ptr(), gain.data_ptr(), covered.data_ptr(),
                                                                    self.gains0.data_ptr(), None, int(bool(lazy)))
         _lib.check(self.lib.gnbv_cover_greedy(C.byref(c), _lib.stream_ptr(self.device)), "gnbv_cover_greedy")
+        return choice, gain, covered
+
+    def plan_weighted(self, rounds: int, weights=(1, 4), contact: Optional[torch.Tensor] = None, covered_bits=None, lazy: bool = True):
+        """Greedy set cover on BOTH masks of the last call under the score of eval.baselines.choose: each round takes the
+        candidate with the largest w_unknown * |new voxels of unknown_bits| + w_hit * |new voxels of hit_bits|, against two
+        covered sets that grow together (plane 0 = unknown_bits, plane 1 = hit_bits; weights = (w_unknown, w_hit), ints >= 0)
+        -> (choice [N,T], gain [N,T] the weighted score, (covered_unknown, covered_hit) [N, words] each) int32.
+        `covered_bits`: None, or a pair of contiguous int32 [N, words] (unknown, hit; not modified).  `contact` as in `plan`.
+        `plane_gain` int32 [N,T,2] holds the winners' gains per mask, `gains0` [N,K] the weighted round-0 score of every
+        candidate.  Outputs are cached per `rounds`, apart from `plan`'s.  One gnbv_cover_greedy_w launch, no host
+        synchronisation; `lazy` changes the work, not the result."""
+        rounds = int(rounds)
+        if not 1 <= rounds <= 4096:
+            raise _lib.GennbvHipError(f"ViewGainMasks.plan_weighted: rounds in 1..4096, got {rounds}")
+        for name, masks in (("unknown", self.unknown_bits), ("hit", self.hit_bits)):
+            if masks is None:
+                raise _lib.GennbvHipError(f"ViewGainMasks.plan_weighted needs both masks: the {name} mask is not kept ({name}=False)")
+        w = plan_weights(weights, self.words)
+        n, k = self.num_envs, self.k
+        if contact is not None:
+            _lib.require_cuda(contact)
+            if contact.dtype != torch.uint8 or contact.shape != (n, k) or not contact.is_contiguous():
+                raise _lib.GennbvHipError(f"ViewGainMasks.plan_weighted: contact must be contiguous uint8 [{n}, {k}]")
+        if covered_bits is not None:
+            if not isinstance(covered_bits, (tuple, list)) or len(covered_bits) != 2:
+                raise _lib.GennbvHipError("ViewGainMasks.plan_weighted: covered_bits must be None or a pair (unknown, hit)")
+            for cb in covered_bits:
+                _lib.require_cuda(cb)
+                if cb.dtype != torch.int32 or cb.shape != (n, self.words) or not cb.is_contiguous():
+                    raise _lib.GennbvHipError(f"ViewGainMasks.plan_weighted: covered_bits must be contiguous int32 [{n}, {self.words}], "
+                                              f"got {cb.dtype} {tuple(cb.shape)}")
+        if rounds not in self._plans_w:
+            dev = self.device
+            self._plans_w[rounds] = (torch.empty(n, rounds, dtype=torch.int32, device=dev), torch.empty(n, rounds, dtype=torch.int32, device=dev),
+                                     (torch.empty(n, self.words, dtype=torch.int32, device=dev), torch.empty(n, self.words, dtype=torch.int32, device=dev)),
+                                     torch.empty(n, rounds, 2, dtype=torch.int32, device=dev))
+        choice, gain, covered, self.plane_gain = self._plans_w[rounds]
+        c = self._cgw
+        c.rounds, c.contact, c.lazy = rounds, _lib.ptr(contact), int(bool(lazy))
+        for p, masks in enumerate((self.unknown_bits, self.hit_bits)):
+            c.weight[p], c.mask_bits[p], c.covered_out[p] = w[p], masks.data_ptr(), covered[p].data_ptr()
+            c.covered_in[p] = None if covered_bits is None else covered_bits[p].data_ptr()
+        c.choice, c.gain, c.plane_gain, c.gains0, c.ub = choice.data_ptr(), gain.data_ptr(), self.plane_gain.data_ptr(), self.gains0.data_ptr(), None
+        _lib.check(self.lib.gnbv_cover_greedy_w(C.byref(c), _lib.stream_ptr(self.device)), "gnbv_cover_greedy_w")
         return choice, gain, covered

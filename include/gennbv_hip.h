@@ -1111,6 +1111,48 @@ typedef struct GnbvCoverGreedy {
 } GnbvCoverGreedy;
 int gnbv_cover_greedy(const GnbvCoverGreedy *args /*[host]*/, void *stream);
 
+/* Weighted greedy set cover over 1..4 planes of per-candidate bit masks (a new entry point of ABI 5): the set cover whose score
+ * is a weighted sum of the planes' gains, against one covered set per plane that grow together.  With plane 0 =
+ * gnbv_view_gain_masks' unknown_bits, plane 1 = its hit_bits and weights (w0, w1) the round-0 score is the view-gain score
+ * w0 unknown + w1 unknown_hit of every candidate.  Per env, with covered_p = covered_in[p] (NULL: empty), for round
+ * t = 0 .. rounds-1:
+ *   g_pj = popcount(mask_p[j] & ~covered_p);  s_j = sum over p < planes of weight[p] g_pj;  score_j = contact[j] ? -1 : s_j;
+ *   j* = the largest score, ties to the lowest j (all candidates in contact: j* = 0);
+ *   choice[t] = j*;  gain[t] = s_j* (also of a contact winner);  plane_gain[t, p] = g_pj*;
+ *   covered_p |= mask_p[j*] for every p < planes, a plane of weight 0 included.
+ * A candidate may win again with gain 0; all weights 0 is legal (every round: the lowest candidate not in contact, gain 0).
+ * gains0[e, j] = s_j of round 0 for every candidate.  Every g_pj only shrinks while covered_p grows and the weights are not
+ * negative, so s_j only shrinks: lazy = 1 gives the same integers as lazy = 0, and `ub`, the bounds of s_j, follows
+ * gnbv_cover_greedy's contract word for word -- read at entry, written at exit, INT32_MAX = unknown, the caller promises
+ * ub[e, j] >= s_j against covered_in, which holds across calls while every covered set only grows.  With gains0 != NULL, or
+ * lazy == 0 and ub != NULL, round 0 evaluates every candidate in a wide launch (one wave each, 16 bytes per lane and plane, all
+ * planes' rows in one trip).  The rounds run in one workgroup per env, whose covered rows live in covered_out[p]; the winner's
+ * plane gains are taken in the pass that ORs its rows into them.  No global
+ * atomics, every output element written once per call, no host synchronisation, no allocation.  Deterministic.  planes = 1 with
+ * weight 1 gives gnbv_cover_greedy's outputs byte for byte.
+ * Returns hipErrorInvalidValue for everything gnbv_cover_greedy refuses (n outside 1..65535, k or rounds outside 1..4096, words
+ * not a positive multiple of 4, lazy outside 0..1, a NULL choice or gain), planes outside 1..4, and for p < planes: a negative
+ * weight[p], a NULL mask_bits[p], a mask_bits[p] / covered_in[p] / covered_out[p] that is not 16-byte aligned, rounds > 1 with a
+ * NULL covered_out[p], a covered_out[p] that is also another plane's covered_out; and for
+ * (weight[0] + .. + weight[planes-1]) * 32 * words > INT32_MAX (a score would not fit in int32).  Entries p >= planes are
+ * ignored.  [host struct]; pointers are device. */
+typedef struct GnbvCoverGreedyW {
+    int n, k, words, rounds;        /* as GnbvCoverGreedy */
+    int planes;                     /* 1..4 */
+    int weight[4];                  /* >= 0 for p < planes */
+    const int32_t *mask_bits[4];    /* [n, k, words] each */
+    const int32_t *covered_in[4];   /* [n, words] or NULL = nothing covered, per plane */
+    int32_t *covered_out[4];        /* [n, words] = covered_in[p] | the chosen rows of plane p; all planes required when
+                                     * rounds > 1, else each may be NULL; may alias its own covered_in */
+    const uint8_t *contact;         /* [n, k] or NULL; != 0: never chosen unless every candidate of the env is */
+    int32_t *choice, *gain;         /* [n, rounds]; gain = the weighted score of the winner */
+    int32_t *plane_gain;            /* [n, rounds, planes] or NULL: the winner's true gain per plane */
+    int32_t *gains0;                /* [n, k] or NULL: weighted round-0 score of every candidate */
+    int32_t *ub;                    /* [n, k] or NULL: in/out upper bounds of the weighted score */
+    int lazy;                       /* 1 = lazy evaluation, 0 = every candidate in every round; the same results */
+} GnbvCoverGreedyW;
+int gnbv_cover_greedy_w(const GnbvCoverGreedyW *args /*[host]*/, void *stream);
+
 /* ------------------------------------------------------------------------- */
 /* Plan-then-fly (a new entry point of ABI 5): order a set of points into a    */
 /* short open flight tour from a matrix of integer leg lengths.                */

@@ -1,10 +1,13 @@
 """Closed-loop table of DESIGN.md "Planning ahead on the map": MapCoverPolicy beside the map-greedy rows.
 
-    python tools/closed_loop_mapcover.py [--envs 8] [--grid 20] [--steps 20] [--k 32] [--seeds 1,2] [--stride 2] [--mask hit] [--out FILE.json]
+    python tools/closed_loop_mapcover.py [--envs 8] [--grid 20] [--steps 20] [--k 32] [--seeds 1,2] [--stride 2] [--mask hit]
+                                         [--weights 1,4] [--field free|costly] [--penalty-m 2.0] [--out FILE.json]
 
 The set-up of tools/closed_loop_frontview.py's map-greedy rows: ReplayFeedEvalEnv over RenderFeed(MeshScene.from_boxes(make_scenes(
 envs, grid, seed=1))), 60 x 80 camera, `steps`-step episodes, CollisionBody(sweep=True), BeliefFlightField(unknown="free") over the
-stride-`stride` flight lattice, one episode per env.  Rows, per seed:
+stride-`stride` flight lattice (`--field costly`: unknown="costly" with `--penalty-m` metres per unknown node entered, the cautious
+pilot), one episode per env.  `--mask` is the mask of the map-cover rows; the mixed rows below plan on both masks under
+`--weights` (w_unknown, w_hit) whatever `--mask` says, and `--mask mixed` makes every map-cover row a mixed one.  Rows, per seed:
 
   map-greedy (1,4)              MapGreedyPolicy over LatticeCandidates, K candidates, weights (1, 4)
   map-greedy (0,1)              the same with weights (0, 1): what map-cover with horizon 1 chooses on the hit mask
@@ -13,6 +16,8 @@ stride-`stride` flight lattice, one episode per env.  Rows, per seed:
   map-cover h5 c1               horizon 5, commit 1
   map-cover h5 c5               horizon 5, commit 5: plan-then-fly in the plan's gain order
   map-cover h5 c5 route         the same, ordered into a tour on the belief field
+  map-mixed h1 c1               MapCoverPolicy(mask="mixed", weights): horizon 1 chooses what map-greedy with these weights chooses
+  map-mixed h3 c1, h5 c1, h5 c5, h5 c5 route   the map-cover rows under the mixed score
 
 Columns: final coverage (mean over envs of coverage_ratio on each env's done step), mean_AUC, mean episode length, the mean of
 env.flight_length on the done step (metres flown in the episode), and the mean number of planned views per decision (1 for the
@@ -46,7 +51,10 @@ DEV = "cuda:0"
 ROWS = [("map-greedy (1,4)", dict(weights=(1, 4))), ("map-greedy (0,1)", dict(weights=(0, 1))),
         ("map-cover h1 c1", dict(horizon=1, commit=1)), ("map-cover h3 c1", dict(horizon=3, commit=1)),
         ("map-cover h5 c1", dict(horizon=5, commit=1)), ("map-cover h5 c5", dict(horizon=5, commit=5)),
-        ("map-cover h5 c5 route", dict(horizon=5, commit=5, route=True))]
+        ("map-cover h5 c5 route", dict(horizon=5, commit=5, route=True)),
+        ("map-mixed h1 c1", dict(horizon=1, commit=1, mask="mixed")), ("map-mixed h3 c1", dict(horizon=3, commit=1, mask="mixed")),
+        ("map-mixed h5 c1", dict(horizon=5, commit=1, mask="mixed")), ("map-mixed h5 c5", dict(horizon=5, commit=5, mask="mixed")),
+        ("map-mixed h5 c5 route", dict(horizon=5, commit=5, route=True, mask="mixed"))]
 
 
 class PlannedViews:
@@ -92,7 +100,10 @@ def main():
     ap.add_argument("--k", type=int, default=32)
     ap.add_argument("--seeds", default="1,2")
     ap.add_argument("--stride", type=int, default=2)
-    ap.add_argument("--mask", default="hit", choices=("hit", "unknown"))
+    ap.add_argument("--mask", default="hit", choices=("hit", "unknown", "mixed"))
+    ap.add_argument("--weights", default="1,4", help="w_unknown,w_hit of the mixed rows")
+    ap.add_argument("--field", default="free", choices=("free", "costly"), help="what unknown space is to the belief flight field")
+    ap.add_argument("--penalty-m", type=float, default=2.0, help="--field costly: metres per unknown node entered")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -103,16 +114,21 @@ def main():
     mesh = MeshScene.from_boxes(scene, device=DEV)
     body = CollisionBody(sweep=True)
     lattice = FlightLattice(cfg, stride=args.stride)
-    res = {k: getattr(args, k) for k in ("envs", "grid", "steps", "k", "stride", "mask")}
+    weights = tuple(int(w) for w in args.weights.split(","))
+    field_kw = dict(unknown="costly", unknown_penalty_m=args.penalty_m) if args.field == "costly" else dict(unknown="free")
+    res = {k: getattr(args, k) for k in ("envs", "grid", "steps", "k", "stride", "mask", "weights", "field", "penalty_m")}
     res["rows"] = []
     for seed in (int(s) for s in args.seeds.split(",")):
         for name, kw in ROWS:
-            flight = BeliefFlightField(n, lattice, body, scene.range_gt, scene.voxel_size, g, unknown="free", device=DEV)
+            flight = BeliefFlightField(n, lattice, body, scene.range_gt, scene.voxel_size, g, device=DEV, **field_kw)
             env = ReplayFeedEvalEnv(cfg, scene, RenderFeed(mesh, cfg), DEV, max_episode_length=args.steps, collision=body, flight=flight)
             if name.startswith("map-greedy"):
                 pol = MapGreedyPolicy(env, k=args.k, seed=seed, **kw)
             else:
-                pol = MapCoverPolicy(env, k=args.k, seed=seed, mask=args.mask, **kw)
+                kw = dict(kw, mask=kw.get("mask", args.mask))
+                if kw["mask"] == "mixed":
+                    kw["weights"] = weights
+                pol = MapCoverPolicy(env, k=args.k, seed=seed, **kw)
             row = {"seed": seed, "row": name}
             row.update(run(PlannedViews(pol), env))
             print(json.dumps(row), flush=True)

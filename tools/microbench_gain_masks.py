@@ -13,7 +13,10 @@ Cases (N, G, camera, stride, K), each on all-unknown grids and on mid-episode gr
 Rows per grid: gnbv_view_gain of this build; the same call on the library at --parent-lib (another build of the same ABI, e.g. the
 parent commit's: _lib.activate), on the same grids and poses; gnbv_view_gain_masks with both masks, the hit mask only, the unknown
 mask only.  Beside every masks row: the bytes the call stores more than gnbv_view_gain (n k words 4 per mask), its extra time over
-this build's gnbv_view_gain, and the store rate the two imply.  Then `plan(horizon)` on the hit mask for horizon 1, 3 and 5.
+this build's gnbv_view_gain, and the store rate the two imply.  Then, for horizon 1, 3 and 5: `plan(horizon)` on the hit mask and
+on the unknown mask, `plan_weighted(horizon, weights)` on both (one gnbv_cover_greedy_w launch; --weights, default 1,4), the sum
+of the two single-mask plans it is set against, and -- with --parent-lib -- the two single-mask plans of that build on the same
+masks (the parent has no weighted plan).
 """
 from __future__ import annotations
 
@@ -49,13 +52,15 @@ def masks_case(name, n, g, h, w, stride, k, args):
     if args.parent_lib:
         _lib.activate(args.parent_lib)  # an operator keeps the library that was active when it was built
         ops["view_gain_parent"] = ViewGain(n, k, cfg, scene.range_gt, scene.voxel_size, **kw)
+        ops["masks_both_parent"] = ViewGainMasks(n, k, cfg, scene.range_gt, scene.voxel_size, **kw)
         _lib.activate()
     ops["masks_both"] = ViewGainMasks(n, k, cfg, scene.range_gt, scene.voxel_size, **kw)
     ops["masks_hit"] = ViewGainMasks(n, k, cfg, scene.range_gt, scene.voxel_size, unknown=False, **kw)
     ops["masks_unknown"] = ViewGainMasks(n, k, cfg, scene.range_gt, scene.voxel_size, hit=False, **kw)
     words = ops["masks_both"].words
     mask_bytes = n * k * words * 4
-    out = {"case": name, "envs": n, "grid": g, "h": h, "w": w, "stride": stride, "k": k, "chunk": args.chunk, "words": words,
+    weights = tuple(int(w) for w in args.weights.split(","))
+    out = {"case": name, "weights": weights, "envs": n, "grid": g, "h": h, "w": w, "stride": stride, "k": k, "chunk": args.chunk, "words": words,
            "mask_bytes": mask_bytes}
     for gname, tri in grids.items():
         want = ops["view_gain"](tri, poses).clone()
@@ -70,8 +75,18 @@ def masks_case(name, n, g, h, w, stride, k, args):
             row["implied_GB_per_s"] = masks * mask_bytes / row["extra_us"] * 1e-3 if row["extra_us"] > 0 else None
         both = ops["masks_both"]
         both(tri, poses)
+        plans = {"": both}
+        if args.parent_lib:
+            plans["_parent"] = ops["masks_both_parent"]
+            plans["_parent"](tri, poses)
         for horizon in (1, 3, 5):
-            out[f"{gname}_plan_{horizon}"] = stats(time_calls(lambda: both.plan(horizon, which="hit"), args.iters, args.repeats))
+            for tag, op in plans.items():
+                out[f"{gname}_plan_{horizon}{tag}"] = stats(time_calls(lambda: op.plan(horizon, which="hit"), args.iters, args.repeats))
+                out[f"{gname}_plan_unknown_{horizon}{tag}"] = stats(time_calls(lambda: op.plan(horizon, which="unknown"), args.iters, args.repeats))
+            row = stats(time_calls(lambda: both.plan_weighted(horizon, weights=weights), args.iters, args.repeats))
+            row["hit_plus_unknown_us"] = out[f"{gname}_plan_{horizon}"]["us_median"] + out[f"{gname}_plan_unknown_{horizon}"]["us_median"]
+            out[f"{gname}_plan_weighted_{horizon}"] = row
+        out[gname + "_mean_plan5_weighted_plane_gain"] = both.plane_gain.float().mean(dim=0).tolist()
         out[gname + "_mean_gain"] = want.float().mean(dim=(0, 1)).tolist()
         out[gname + "_mean_plan5_gain"] = both.plan(5, which="hit")[1].float().mean(dim=0).tolist()
     return out
@@ -83,6 +98,7 @@ def main():
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--cases", default="g64_k8,g64_k32,g20_k32")
     ap.add_argument("--parent-lib", default=None, help="another build of libgennbv_hip.so (the same ABI) to time gnbv_view_gain on")
+    ap.add_argument("--weights", default="1,4", help="w_unknown,w_hit of the weighted plan")
     ap.add_argument("--chunk", type=int, default=0, help="candidates per workgroup (0 = chosen)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
