@@ -119,6 +119,7 @@ SIGNATURES = {
     "gnbv_view_gain_masks": (_i, [_p, _i, _p, _p, _p]),
     "gnbv_view_gain_slab_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
     "gnbv_view_gain_slab": (_i, [_p, _i, _p, _sz, _p]),
+    "gnbv_view_gain_slab_masks": (_i, [_p, _i, _p, _sz, _i, _p, _p, _p]),
     "gnbv_view_cover": (_i, [_p, _p, _p]),
     "gnbv_view_cover_masks": (_i, [_p, _p, _p, _p]),
     "gnbv_cover_greedy": (_i, [_p, _p]),

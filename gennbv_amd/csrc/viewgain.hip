@@ -28,8 +28,10 @@
 //     the LDS words it has just read -- store-and-clear replaces step 5 and also runs for the chunk's last candidate.  The
 //     workgroup owns its candidates' rows: no atomics.  k_view_gain<false> is the kernel gnbv_view_gain always launched.
 //
-//   k_vg_prep, k_vg_fate, k_vg_slab   the same integers for grids up to 128^3 (gnbv_view_gain_slab): further down.
+//   k_vg_prep, k_vg_fate, k_vg_slab   the same integers for grids up to 128^3 (gnbv_view_gain_slab), and in their <true> forms
+//     the same two masks (gnbv_view_gain_slab_masks): further down.
 #include <cmath>
+#include <type_traits>
 
 #include "common.h"
 #include "backproject.h"
@@ -240,6 +242,24 @@ __global__ __launch_bounds__(kMaxThreads) void k_view_gain(VgParams p)
 //
 // tests/test_view_gain_slab_cpu.py holds a Python model of the record and of the slab cut, checked against the oracle's
 // Bresenham.
+//
+// gnbv_view_gain_slab_masks launches k_vg_prep<true> and k_vg_slab<true>, which also keep the two masks (k_vg_fate is shared).
+// A candidate's row is cut by x-planes like its voxels: slab [X0, X1) holds the row's bits [X0 G^2, X1 G^2), which start and
+// end inside a word unless G^2 s is a multiple of 32.
+//   - The slab's LDS masks are biased by sh = X0 G^2 & 127: voxel `lin` of the slab is bit lin + sh, so LDS quad q IS row quad
+//     (X0 G^2 >> 7) + q -- a 16-byte LDS read and an aligned 16-byte global store, no funnel shift.  Cost: at most 16 bytes per
+//     mask, and none where G^2 s is a multiple of 128 (any s at G % 16 == 0, even s at G % 8 == 0).  s_grid and the counts
+//     do not see sh.
+//   - After the barrier "every ray of candidate j is done" a lane stores the quads it then clears (store-and-clear replaces the
+//     clear pass and also runs for the chunk's last candidate).  A quad that lies whole inside the slab's bits (the last slab
+//     owns the row up to its last quad: bits at and past G^3 are never set) is one 16-byte store.  In the at most two quads at
+//     the slab's ragged ends a word inside the slab's bits is a 4-byte store, a word of another slab is left alone, and a word
+//     the slab SHARES with a neighbour gets the slab's part by a global atomicOr.  The parts are disjoint bit sets and
+//     k_vg_prep<true> has zeroed the shared words (and the pad words from ceil(G^3 / 32) to `words`) earlier on the stream, so
+//     the word does not depend on the order.  Every other word of a row has one writer.  G^2 >= 32 bits per plane from G = 6
+//     on, so a word is then shared by two slabs at most (at G = 3, s = 1 by three; the rule is the same).
+//   - With no ray (stride / 2 >= width or height) no slab kernel runs and k_vg_prep<true> zeroes the rows whole.
+// tests/test_gain_masks_slab_cpu.py holds a numpy model of this word-ownership rule.
 constexpr int kFateThreads = 256;
 constexpr int kCamWords = 20;                      // per candidate in the workspace: c2w [16] f32, source voxel [3] i32, pad
 constexpr size_t kSlabLdsBudget = 128 * 1024;      // default slab height: grid + masks within this
@@ -265,10 +285,39 @@ struct VsParams {
     uint32_t *meta;    // [batch, k, nrays]
 };
 
-__global__ __launch_bounds__(256) void k_vg_prep(VsParams p, int e0, int ne)
+struct VsMaskParams : VsParams {        // k_vg_prep<true>, k_vg_slab<true>
+    uint32_t *unknown_bits, *hit_bits;  // [n, k, words] rows, 16-byte aligned, either may be NULL
+    int words;                          // a multiple of 4, >= ceil(g^3 / 32)
+    int zero_words;                     // words of a row k_vg_prep<true> zeroes: nslab - 1 seams + the pad, or (zero_all, no
+    int zero_all;                       // slab kernel follows) all `words`
+};
+template <bool MASKS> using VsArgs = std::conditional_t<MASKS, VsMaskParams, VsParams>;
+
+template <bool MASKS>
+__global__ __launch_bounds__(256) void k_vg_prep(VsArgs<MASKS> p, int e0, int ne)
 {
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int g3 = p.g * p.g * p.g;
+    if constexpr (MASKS) {
+        // the words no slab workgroup plain-stores: the word at each seam that is not a word boundary (the slabs OR their
+        // parts into it), the pad words; with no ray, the whole row
+        if (t < (int64_t)ne * p.k * p.zero_words) {
+            const int64_t c = t / p.zero_words;  // (el, j)
+            const int z = (int)(t - c * p.zero_words), row_words = (g3 + 31) / 32;
+            int w = z;
+            if (!p.zero_all && z < p.nslab - 1) {
+                const int seam = (z + 1) * p.slab * p.g * p.g;  // the first bit of slab z + 1
+                w = (seam & 31) != 0 ? seam >> 5 : -1;
+            } else if (!p.zero_all) {
+                w = row_words + (z - (p.nslab - 1));
+            }
+            if (w >= 0) {
+                const size_t o = ((size_t)e0 * p.k + (size_t)c) * (size_t)p.words + w;
+                if (p.unknown_bits != nullptr) p.unknown_bits[o] = 0u;
+                if (p.hit_bits != nullptr) p.hit_bits[o] = 0u;
+            }
+        }
+    }
     if (t < (int64_t)ne * p.pack_words) {
         const int el = (int)(t / p.pack_words), w = (int)(t - (int64_t)el * p.pack_words);
         p.packed[t] = pack_word(p.tri + (size_t)(e0 + el) * p.tri_row_stride, w, g3, p.tri_aligned);
@@ -393,7 +442,8 @@ __device__ __forceinline__ SlabWalk make_slab_walk(int x0, int y0, int z0, int x
     return r;
 }
 
-__global__ __launch_bounds__(kMaxThreads) void k_vg_slab(VsParams p, int e0, int ne)
+template <bool MASKS>
+__global__ __launch_bounds__(kMaxThreads) void k_vg_slab(VsArgs<MASKS> p, int e0, int ne)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t s_mem[];
     __shared__ int s_part[kMaxThreads / kWave][2];
@@ -409,6 +459,7 @@ __global__ __launch_bounds__(kMaxThreads) void k_vg_slab(VsParams p, int e0, int
     const int j0 = ch * p.chunk, j1 = min(p.k, j0 + p.chunk);
     const int X0 = sl * p.slab, X1 = min(g, X0 + p.slab);
     const unsigned svox = (unsigned)((X1 - X0) * gg);
+    const int sh = MASKS ? (X0 * gg) & 127 : 0;  // <true>: voxel `lin` of the slab is bit lin + sh of the LDS masks
     uint32_t *s_grid = s_mem, *s_a = s_mem + p.grid_words, *s_b = s_a + p.mask_words;
 
     // ---- the slab's voxels, 2 bits each, from voxel X0 g^2 of the packed grid (not a word boundary in general; the packed
@@ -444,9 +495,10 @@ __global__ __launch_bounds__(kMaxThreads) void k_vg_slab(VsParams p, int e0, int
                 if ((unsigned)w.lin < svox) {  // x inside the slab (y, z are inside the grid on every recorded step)
                     const uint32_t cls = (s_grid[w.lin >> 4] >> ((w.lin & 15) * 2)) & 3u;
                     if (cls == 0u && mark) {
-                        const uint32_t bit = 1u << (w.lin & 31);
-                        n_unknown += (atomicOr(&s_a[w.lin >> 5], bit) & bit) == 0u;
-                        if (blocked) n_unknown_hit += (atomicOr(&s_b[w.lin >> 5], bit) & bit) == 0u;
+                        const int ml = w.lin + sh;
+                        const uint32_t bit = 1u << (ml & 31);
+                        n_unknown += (atomicOr(&s_a[ml >> 5], bit) & bit) == 0u;
+                        if (blocked) n_unknown_hit += (atomicOr(&s_b[ml >> 5], bit) & bit) == 0u;
                     }
                 }
                 if (w.p1 >= 0) { w.lin += w.lb; w.p1 -= w.two_da; }
@@ -474,8 +526,42 @@ __global__ __launch_bounds__(kMaxThreads) void k_vg_slab(VsParams p, int e0, int
             if (c != 0) atomicAdd(o + 1, c);
         }
         // (ordered in front of the next candidate's rays by the barrier at the loop's head, as in k_view_gain)
-        if (j + 1 < j1 && mark)
-            for (int w = tid; w < mask_quads; w += nthreads) s_masks4[w] = make_uint4(0u, 0u, 0u, 0u);
+        if constexpr (MASKS) {
+            // store, then clear: a lane clears the quads it stored, so no barrier between the two.  The slab's bits are
+            // [lo, hi) of the LDS masks; the last slab owns the row to the end of its last quad.
+            const int base = X0 * gg, row_quads = p.mask_words / 4;
+            const int lo = sh, nq = (sh + (int)svox + 127) >> 7, hi = X1 == g ? nq * 128 : sh + (int)svox;
+            const size_t off = ((size_t)e * p.k + j) * (size_t)p.words + 4 * (size_t)(base >> 7);
+            uint32_t *ga = p.unknown_bits != nullptr ? p.unknown_bits + off : nullptr;
+            uint32_t *gb = p.hit_bits != nullptr ? p.hit_bits + off : nullptr;
+            const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
+            for (int q = tid; q < nq; q += nthreads) {
+                const uint4 a = s_masks4[q], c = s_masks4[row_quads + q];
+                if (128 * q >= lo && 128 * q + 128 <= hi) {
+                    if (ga != nullptr) reinterpret_cast<uint4 *>(ga)[q] = a;
+                    if (gb != nullptr) reinterpret_cast<uint4 *>(gb)[q] = c;
+                } else {
+                    const uint32_t aw[4] = {a.x, a.y, a.z, a.w}, cw[4] = {c.x, c.y, c.z, c.w};
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) {
+                        const int b0 = 128 * q + 32 * t, b1 = b0 + 32;
+                        if (b1 <= lo || b0 >= hi) continue;  // another slab's word
+                        if (b0 >= lo && b1 <= hi) {
+                            if (ga != nullptr) ga[4 * q + t] = aw[t];
+                            if (gb != nullptr) gb[4 * q + t] = cw[t];
+                        } else {  // shared with a neighbour: zeroed by k_vg_prep<true>, the parts are disjoint
+                            if (ga != nullptr && aw[t] != 0u) atomicOr(ga + 4 * q + t, aw[t]);
+                            if (gb != nullptr && cw[t] != 0u) atomicOr(gb + 4 * q + t, cw[t]);
+                        }
+                    }
+                }
+                s_masks4[q] = zero;
+                s_masks4[row_quads + q] = zero;
+            }
+        } else {
+            if (j + 1 < j1 && mark)
+                for (int w = tid; w < mask_quads; w += nthreads) s_masks4[w] = make_uint4(0u, 0u, 0u, 0u);
+        }
     }
 }
 
@@ -507,11 +593,12 @@ inline bool vs_plan(int n, int k, int g, int h, int w, int stride, VsPlan &pl)
     return true;
 }
 
-inline size_t slab_lds_bytes(int g, int s, int &grid_words, int &mask_words)
+// `masks`: k_vg_slab<true> biases its masks by X0 g^2 & 127 bits, which is 0 in every slab where s g^2 is a multiple of 128
+inline size_t slab_lds_bytes(int g, int s, int &grid_words, int &mask_words, bool masks = false)
 {
-    const int vox = s * g * g;
+    const int vox = s * g * g, bias = masks && (vox & 127) != 0 ? 127 : 0;
     grid_words = (((vox + 15) / 16) + 3) & ~3;
-    mask_words = (((vox + 31) / 32) + 3) & ~3;
+    mask_words = (((vox + bias + 31) / 32) + 3) & ~3;
     return (size_t)(grid_words + 2 * mask_words) * sizeof(uint32_t);
 }
 
@@ -599,7 +686,10 @@ GNBV_API size_t gnbv_view_gain_slab_workspace_bytes(int n, int k, int g, int h, 
     return vs_plan(n, k, g, h, w, stride, pl) ? pl.bytes : 0;
 }
 
-GNBV_API int gnbv_view_gain_slab(const GnbvViewGain *args, int slab, void *workspace, size_t workspace_bytes, void *stream)
+// gnbv_view_gain_slab (MASKS false: the mask arguments are not looked at) and gnbv_view_gain_slab_masks
+template <bool MASKS>
+static int view_gain_slab_impl(const GnbvViewGain *args, int slab, void *workspace, size_t workspace_bytes, int words,
+                               int32_t *unknown_bits, int32_t *hit_bits, void *stream)
 {
     GNBV_CHECK_ARG(args != nullptr);
     const GnbvViewGain a = *args;
@@ -607,17 +697,24 @@ GNBV_API int gnbv_view_gain_slab(const GnbvViewGain *args, int slab, void *works
     VsPlan pl;
     GNBV_CHECK_ARG(vs_plan(a.n, a.k, a.g, a.h, a.w, a.stride, pl));
     GNBV_CHECK_ARG(workspace != nullptr && workspace_bytes >= pl.bytes && ((uintptr_t)workspace & 15) == 0);
-    VsParams p;
+    const int row_words = (a.g * a.g * a.g + 31) / 32;
+    if (MASKS) {
+        GNBV_CHECK_ARG(a.ablate == 0 && (unknown_bits != nullptr || hit_bits != nullptr));
+        GNBV_CHECK_ARG(words > 0 && (words & 3) == 0 && words >= row_words);
+        GNBV_CHECK_ARG((((uintptr_t)unknown_bits | (uintptr_t)hit_bits) & 15) == 0);
+        GNBV_CHECK_ARG((int64_t)a.n * a.k * words <= 0x7fffffff);
+    }
+    VsArgs<MASKS> p;
     p.k = a.k; p.g = a.g;
     // slab height: the fewest slabs whose grid + masks fit the LDS budget, of equal height; a requested height is kept if it fits
     int s = slab > a.g ? a.g : slab;
     if (s == 0) {
         int ns = 1;
-        while (slab_lds_bytes(a.g, (a.g + ns - 1) / ns, p.grid_words, p.mask_words) > kSlabLdsBudget) ++ns;
+        while (slab_lds_bytes(a.g, (a.g + ns - 1) / ns, p.grid_words, p.mask_words, MASKS) > kSlabLdsBudget) ++ns;
         s = (a.g + ns - 1) / ns;
     }
-    while (slab_lds_bytes(a.g, s, p.grid_words, p.mask_words) > kSlabLdsMax) --s;  // s = 1: 2 * 8 KiB at 128^3
-    const size_t lds = slab_lds_bytes(a.g, s, p.grid_words, p.mask_words);
+    while (slab_lds_bytes(a.g, s, p.grid_words, p.mask_words, MASKS) > kSlabLdsMax) --s;  // s = 1: 2 * 8 KiB at 128^3
+    const size_t lds = slab_lds_bytes(a.g, s, p.grid_words, p.mask_words, MASKS);
     p.slab = s;
     p.nslab = (a.g + s - 1) / s;
     const int batch_pad = (pl.batch + 7) / 8 * 8;  // the XCD-aware grids are whole multiples of 8 envs
@@ -648,21 +745,41 @@ GNBV_API int gnbv_view_gain_slab(const GnbvViewGain *args, int slab, void *works
     p.cams = reinterpret_cast<float *>(ws + pl.off_cams);
     p.rec = reinterpret_cast<int4 *>(ws + pl.off_rec);
     p.meta = reinterpret_cast<uint32_t *>(ws + pl.off_meta);
+    if constexpr (MASKS) {
+        p.unknown_bits = reinterpret_cast<uint32_t *>(unknown_bits);
+        p.hit_bits = reinterpret_cast<uint32_t *>(hit_bits);
+        p.words = words;
+        p.zero_all = pl.nrays == 0;
+        p.zero_words = p.zero_all ? words : p.nslab - 1 + (words - row_words);
+    }
     int threads = ((pl.nrays > 0 ? pl.nrays : 1) + kWave - 1) / kWave * kWave;
     const int cap = lds > 32 * 1024 ? kMaxThreads : 256;
     threads = threads > cap ? cap : threads;
     hipStream_t st = gnbv_stream(stream);
     if (lds > 64 * 1024 &&
-        hipFuncSetAttribute((const void *)k_vg_slab, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        hipFuncSetAttribute((const void *)k_vg_slab<MASKS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return (int)hipGetLastError();
     for (int e0 = 0; e0 < a.n; e0 += pl.batch) {  // the workspace is reused: the stream orders the batches
         const int ne = a.n - e0 < pl.batch ? a.n - e0 : pl.batch, ne_pad = (ne + 7) / 8 * 8;
         int64_t items = (int64_t)ne * pl.pack_words;
         if ((int64_t)ne * a.k * 3 > items) items = (int64_t)ne * a.k * 3;
-        hipLaunchKernelGGL(k_vg_prep, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, p, e0, ne);
+        if constexpr (MASKS)
+            if ((int64_t)ne * a.k * p.zero_words > items) items = (int64_t)ne * a.k * p.zero_words;
+        hipLaunchKernelGGL(k_vg_prep<MASKS>, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, p, e0, ne);
         if (pl.nrays == 0) continue;
         hipLaunchKernelGGL(k_vg_fate, dim3((unsigned)(ne_pad * a.k * p.rblocks)), dim3(kFateThreads), 0, st, p, e0, ne);
-        hipLaunchKernelGGL(k_vg_slab, dim3((unsigned)(ne_pad * p.chunks * p.nslab)), dim3(threads), lds, st, p, e0, ne);
+        hipLaunchKernelGGL(k_vg_slab<MASKS>, dim3((unsigned)(ne_pad * p.chunks * p.nslab)), dim3(threads), lds, st, p, e0, ne);
     }
     return gnbv_launch_status();
+}
+
+GNBV_API int gnbv_view_gain_slab(const GnbvViewGain *args, int slab, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return view_gain_slab_impl<false>(args, slab, workspace, workspace_bytes, 0, nullptr, nullptr, stream);
+}
+
+GNBV_API int gnbv_view_gain_slab_masks(const GnbvViewGain *args, int slab, void *workspace, size_t workspace_bytes, int words,
+                                       int32_t *unknown_bits, int32_t *hit_bits, void *stream)
+{
+    return view_gain_slab_impl<true>(args, slab, workspace, workspace_bytes, words, unknown_bits, hit_bits, stream);
 }

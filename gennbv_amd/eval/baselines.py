@@ -327,8 +327,8 @@ class MapCoverPolicy(MapGreedyPolicy):
 
     A decision:
       1. plan: K candidates, their poses, ViewGainMasks(tri, poses) (ops/gain_masks.py: the view gain and its two voxel sets as bit
-         masks) and `plan(horizon, which=mask, contact=self.contact(poses))`, greedy set cover from an empty covered set -- the
-         masks hold only voxels that are unknown NOW;
+         masks; make_view_gain_masks picks ViewGainMasksSlab for grids above 64^3, up to 128^3) and
+         `plan(horizon, which=mask, contact=self.contact(poses))`, greedy set cover from an empty covered set -- the masks hold only voxels that are unknown NOW;
       2. keep the rounds with gain > 0 whose choice is not refused, in plan order (a repeat has gain 0: the kept views are
          distinct); `views` [N] is their number; an env with none takes round 0's choice -- candidate 0 when all are refused
          (gnbv_cover_greedy's rule), exactly MapGreedyPolicy's fallback;
@@ -376,10 +376,10 @@ class MapCoverPolicy(MapGreedyPolicy):
         else:
             weights = (1, 0) if mask == "unknown" else (0, 1)
         if masks_backend is None:
-            from ..ops.gain_masks import ViewGainMasks
+            from ..ops.gain_masks import make_view_gain_masks  # ViewGainMasks up to 64^3, ViewGainMasksSlab up to 128^3
             u = env.updater
-            masks_backend = ViewGainMasks(int(env.num_envs), int(k), env.cfg, u.range_gt, u.voxel_size_gt, inv_intrinsics=u.inv_intri_host,
-                                          stride=stride, device=env.device, hit=mixed or mask == "hit", unknown=mixed or mask == "unknown")
+            masks_backend = make_view_gain_masks(int(env.num_envs), int(k), env.cfg, u.range_gt, u.voxel_size_gt, inv_intrinsics=u.inv_intri_host,
+                                                 stride=stride, device=env.device, hit=mixed or mask == "hit", unknown=mixed or mask == "unknown")
         super().__init__(env, k=k, weights=weights, seed=seed, stride=stride, look_at_scene=look_at_scene,
                          gain_backend=masks_backend, shortcut=shortcut, max_cost_m=max_cost_m, candidates=candidates)
         self.horizon, self.commit, self.mask, self.route = horizon, commit, mask, bool(route)

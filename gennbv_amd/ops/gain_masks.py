@@ -1,5 +1,5 @@
-"""ViewGainMasks: the view gain that keeps what it counts, and greedy set cover on it  (csrc/viewgain.hip gnbv_view_gain_masks,
-csrc/covergreedy.hip gnbv_cover_greedy).
+"""ViewGainMasks: the view gain that keeps what it counts, and greedy set cover on it  (csrc/viewgain.hip gnbv_view_gain_masks
+and gnbv_view_gain_slab_masks, csrc/covergreedy.hip gnbv_cover_greedy).
 
 ViewGain reduces, per candidate, the set of unknown voxels its rays would cross to three integers; two candidates that would see
 the SAME unknown voxels both look good.  ViewGainMasks runs the same kernel and also stores the two sets as bit masks --
@@ -9,7 +9,11 @@ that add DIFFERENT voxels: the classic greedy set cover, on the map the pilot ho
 is the same under the greedy planners' score w_unknown * new unknown voxels + w_hit * new hit voxels, on both masks at once
 (csrc/covergreedy.hip gnbv_cover_greedy_w).  Integers with one right
 answer (include/gennbv_hip.h has the exact definitions).  Outputs are preallocated and reused: a result is valid until the next
-call of the same method.  No host synchronisation in either call.  GPU only, no CPU fallback; grid_size <= 64.
+call of the same method.  No host synchronisation in either call.  GPU only, no CPU fallback.
+
+ViewGainMasks stores the masks from the LDS of the one-launch kernel (grid_size <= 64); ViewGainMasksSlab computes the same rows
+for grid_size <= 128 through gnbv_view_gain_slab_masks (the slab kernels of ViewGainSlab, each slab storing its part of a row)
+with a preallocated workspace, and plans on them with the same `plan` / `plan_weighted`; make_view_gain_masks picks.
 """
 from __future__ import annotations
 
@@ -20,7 +24,7 @@ import torch
 
 from .. import _lib
 from ..env.config import TaskConfig
-from .view_gain import MAX_GRID, ViewGain
+from .view_gain import MAX_GRID, MAX_GRID_SLAB, ViewGain
 
 
 def plan_weights(weights, words: int):
@@ -47,27 +51,27 @@ class ViewGainMasks(ViewGain):
                  with_c2w: bool = False, chunk: int = 0):
         """ViewGain's arguments, plus: `hit` / `unknown` choose the masks to keep (at least one); `words` is the row length
         (None: gnbv_grid_bit_words(G), the updater's; any multiple of 4 that holds G^3 bits); `max_bytes` caps the masks."""
-        g = int(cfg.grid_size)
-        if g > MAX_GRID:
-            raise _lib.GennbvHipError(f"ViewGainMasks: grid_size <= {MAX_GRID}, got {g} (the masks are stored from the LDS of the "
-                                      "one-launch kernel; above, the slab kernels split the voxels by x-planes and a word of the "
-                                      "mask can straddle two slabs: no mask-emitting form exists)")
+        g, name = int(cfg.grid_size), type(self).__name__
+        if g > self._max_grid:
+            raise _lib.GennbvHipError(f"{name}: grid_size <= {self._max_grid}, got {g}" + (
+                " (the masks are stored from the LDS of the one-launch kernel; above, the slab kernels store them slab by slab: "
+                f"ViewGainMasksSlab / make_view_gain_masks go up to {MAX_GRID_SLAB})" if self._max_grid == MAX_GRID else ""))
         if not (hit or unknown):
-            raise _lib.GennbvHipError("ViewGainMasks: at least one of hit, unknown")
+            raise _lib.GennbvHipError(f"{name}: at least one of hit, unknown")
         if torch.device(device).type != "cuda":
-            raise _lib.GennbvHipError("ViewGainMasks runs on the GPU only (no CPU fallback)")
+            raise _lib.GennbvHipError(f"{name} runs on the GPU only (no CPU fallback)")
         lib = _lib.load()
         n, k = int(num_envs), int(k)
         self.words = int(lib.gnbv_grid_bit_words(g)) if words is None else int(words)
         if self.words < 1 or self.words % 4 or self.words * 32 < g ** 3:
-            raise _lib.GennbvHipError(f"ViewGainMasks: words must be a multiple of 4 that holds {g}^3 bits, got {self.words}")
+            raise _lib.GennbvHipError(f"{name}: words must be a multiple of 4 that holds {g}^3 bits, got {self.words}")
         kept = int(bool(hit)) + int(bool(unknown))
         nbytes = kept * n * k * self.words * 4
         if nbytes > int(max_bytes):
-            raise _lib.GennbvHipError(f"ViewGainMasks: the {kept} masks of {n} envs x {k} views x {self.words} words take {nbytes} "
+            raise _lib.GennbvHipError(f"{name}: the {kept} masks of {n} envs x {k} views x {self.words} words take {nbytes} "
                                       f"bytes, above max_bytes = {int(max_bytes)}")
         if n * k * self.words > 2 ** 31 - 1:
-            raise _lib.GennbvHipError(f"ViewGainMasks: {n} envs x {k} views x {self.words} words exceed 2^31 - 1 words")
+            raise _lib.GennbvHipError(f"{name}: {n} envs x {k} views x {self.words} words exceed 2^31 - 1 words")
         super().__init__(n, k, cfg, range_gt, voxel_size, inv_intrinsics, stride, range_m, device, with_c2w, chunk)
         dev = self.device
         self.unknown_bits = torch.empty(n, k, self.words, dtype=torch.int32, device=dev) if unknown else None
@@ -167,3 +171,41 @@ class ViewGainMasks(ViewGain):
         c.choice, c.gain, c.plane_gain, c.gains0, c.ub = choice.data_ptr(), gain.data_ptr(), self.plane_gain.data_ptr(), self.gains0.data_ptr(), None
         _lib.check(self.lib.gnbv_cover_greedy_w(C.byref(c), _lib.stream_ptr(self.device)), "gnbv_cover_greedy_w")
         return choice, gain, covered
+
+
+class ViewGainMasksSlab(ViewGainMasks):
+    """The same operator for grid_size <= 128 (gnbv_view_gain_slab_masks): ViewGainMasks' arguments plus `slab`, the x-planes per
+    slab (0 = chosen from the grid size; any height gives the same rows and integers).  `unknown_bits`, `hit_bits`, `words`,
+    `max_bytes`, `gains0`, `plan`, `plan_weighted` and `plane_gain` are ViewGainMasks'; the workspace (ViewGainSlab's) is
+    allocated once, here.  Sizes: at 128^3 a row is 65 536 words = 256 KiB, so 64 envs x K = 32 x both masks take 1 GiB and
+    512 envs x 32 x both exactly the default `max_bytes` of 8 GiB (n k words = 2^30 words per mask, within the 2^31 - 1 limit);
+    keep one mask (hit=False / unknown=False) to halve it."""
+    _max_grid = MAX_GRID_SLAB
+
+    def __init__(self, num_envs: int, k: int, cfg: TaskConfig, range_gt: torch.Tensor, voxel_size: torch.Tensor,
+                 inv_intrinsics: Optional[torch.Tensor] = None, stride: int = 4, range_m: Optional[float] = None,
+                 device="cuda:0", hit: bool = True, unknown: bool = True, words: Optional[int] = None, max_bytes: int = 8 << 30,
+                 with_c2w: bool = False, chunk: int = 0, slab: int = 0):
+        super().__init__(num_envs, k, cfg, range_gt, voxel_size, inv_intrinsics, stride, range_m, device, hit, unknown, words,
+                         max_bytes, with_c2w, chunk)
+        self.slab = int(slab)
+        self.workspace_bytes = int(self.lib.gnbv_view_gain_slab_workspace_bytes(self.num_envs, self.k, self.g, self.h, self.w,
+                                                                                self.stride))
+        if self.workspace_bytes == 0:
+            raise _lib.GennbvHipError(f"ViewGainMasksSlab: sizes refused (n {num_envs}, k {k}, g {self.g}, camera {self.h}x{self.w}, "
+                                      f"stride {stride})")
+        self.workspace = torch.empty(self.workspace_bytes, dtype=torch.uint8, device=self.device)
+
+    def _launch(self, a):
+        _lib.check(self.lib.gnbv_view_gain_slab_masks(C.byref(a), self.slab, self.workspace.data_ptr(), self.workspace_bytes, self.words,
+                                                      _lib.ptr(self.unknown_bits), _lib.ptr(self.hit_bits),
+                                                      _lib.stream_ptr(self.device)), "gnbv_view_gain_slab_masks")
+
+
+def make_view_gain_masks(num_envs: int, k: int, cfg: TaskConfig, *args, **kwargs) -> ViewGainMasks:
+    """ViewGainMasks for grid_size <= 64 (one launch, the grid in LDS), ViewGainMasksSlab above; `slab` is passed to the latter
+    only."""
+    if int(cfg.grid_size) <= MAX_GRID:
+        kwargs.pop("slab", None)
+        return ViewGainMasks(num_envs, k, cfg, *args, **kwargs)
+    return ViewGainMasksSlab(num_envs, k, cfg, *args, **kwargs)

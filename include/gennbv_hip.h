@@ -1019,6 +1019,25 @@ int gnbv_view_gain_masks(const GnbvViewGain *args /*[host]*/, int words, int32_t
 size_t gnbv_view_gain_slab_workspace_bytes(int n, int k, int g, int h, int w, int stride);
 int gnbv_view_gain_slab(const GnbvViewGain *args /*[host]*/, int slab, void *workspace, size_t workspace_bytes, void *stream);
 
+/* gnbv_view_gain_slab that keeps the sets it counts: gnbv_view_gain_masks for 2 <= g <= 128 (a new entry point of ABI 5).
+ * U(e, j), H(e, j), the row layout (bit lin & 31 of word lin >> 5, lin = (x g + y) g + z, rows of `words` words, unswizzled)
+ * and the rule that every word of every row of a non-NULL output is written on every call -- the zero words, the pad words from
+ * ceil(g^3 / 32) up to `words`, the rows no ray reaches and the call without any ray (stride / 2 >= w or h) included -- are
+ * gnbv_view_gain_masks'; a row belongs to env e of all n, whatever batch of the workspace computed it.  args->gain is required
+ * and filled exactly as gnbv_view_gain_slab fills it, so popcount(unknown_bits[e, j]) == gain[e, j, 0] and
+ * popcount(hit_bits[e, j]) == gain[e, j, 1]; c2w_out as there.  The same three kernels per batch of envs: a slab workgroup
+ * stores its part of both LDS masks into the candidate's rows before it clears them (16-byte stores; 4-byte stores at the slab's
+ * ragged ends); a row word that two slabs share, where slab g^2 is not a multiple of 32, is zeroed by the first kernel and
+ * gets both parts by atomicOr -- disjoint bit sets, so the result is deterministic and depends neither on `slab` (chosen and
+ * reduced as in gnbv_view_gain_slab; the LDS masks may take 16 bytes more each), nor on `chunk`, nor on which outputs are
+ * requested.  The workspace is gnbv_view_gain_slab_workspace_bytes, unchanged.  No host synchronisation, no allocation.
+ * Returns hipErrorInvalidValue, before any launch, for everything gnbv_view_gain_slab refuses (g outside 2..128 included),
+ * args->ablate != 0, both outputs NULL, `words` not a positive multiple of 4 or < ceil(g^3 / 32), an output that is not 16-byte
+ * aligned, and n k words > 2^31 - 1. */
+int gnbv_view_gain_slab_masks(const GnbvViewGain *args /*[host]*/, int slab, void *workspace, size_t workspace_bytes, int words,
+                              int32_t *unknown_bits /*[n, k, words] or NULL*/, int32_t *hit_bits /*[n, k, words] or NULL*/,
+                              void *stream);
+
 /* ------------------------------------------------------------------------- */
 /* View coverage (a new entry point of ABI 5): which ground-truth voxels would  */
 /* the voxel update mark if env e's camera stood at candidate pose j?  The      */

@@ -7,7 +7,8 @@ The set-up of tools/closed_loop_frontview.py's map-greedy rows: ReplayFeedEvalEn
 envs, grid, seed=1))), 60 x 80 camera, `steps`-step episodes, CollisionBody(sweep=True), BeliefFlightField(unknown="free") over the
 stride-`stride` flight lattice (`--field costly`: unknown="costly" with `--penalty-m` metres per unknown node entered, the cautious
 pilot), one episode per env.  `--mask` is the mask of the map-cover rows; the mixed rows below plan on both masks under
-`--weights` (w_unknown, w_hit) whatever `--mask` says, and `--mask mixed` makes every map-cover row a mixed one.  Rows, per seed:
+`--weights` (w_unknown, w_hit) whatever `--mask` says, and `--mask mixed` makes every map-cover row a mixed one.  `--grid` goes up
+to 128: the planners take their backends from make_view_gain / make_view_gain_masks, the slab kernels above 64^3.  Rows, per seed:
 
   map-greedy (1,4)              MapGreedyPolicy over LatticeCandidates, K candidates, weights (1, 4)
   map-greedy (0,1)              the same with weights (0, 1): what map-cover with horizon 1 chooses on the hit mask

@@ -1,7 +1,8 @@
-"""Microbenchmark of the view gain that keeps its masks (gnbv_view_gain_masks) beside the view gain it extends, and of the
-set-cover plan on the masks (ViewGainMasks.plan, one gnbv_cover_greedy launch).
+"""Microbenchmark of the view gain that keeps its masks (gnbv_view_gain_masks; gnbv_view_gain_slab_masks above 64^3) beside the
+view gain it extends, and of the set-cover plan on the masks (ViewGainMasks.plan, one gnbv_cover_greedy launch).
 
-    python tools/microbench_gain_masks.py [--repeats 7] [--iters 5] [--cases ...] [--parent-lib PATH] [--chunk 0] [--out FILE.json]
+    python tools/microbench_gain_masks.py [--repeats 7] [--iters 5] [--cases ...] [--parent-lib PATH] [--chunk 0] [--envs128 64]
+                                          [--out FILE.json]
 
 Device events around `iters` back-to-back calls, after warm-up, `repeats` times; reported: median / min / max us per call.
 Cases (N, G, camera, stride, K), each on all-unknown grids and on mid-episode grids (10 closed-loop steps of random lattice poses):
@@ -9,6 +10,11 @@ Cases (N, G, camera, stride, K), each on all-unknown grids and on mid-episode gr
   g64_k8      256, 64^3, 240x320, 4, 8
   g64_k32     256, 64^3, 240x320, 4, 32
   g20_k32     8, 20^3, 240x320, 4, 32
+  g128_k8     64, 128^3, 240x320, 4, 8      (not in the default list: --cases g128_k8,g128_k32; --envs128 changes the 64.  A row
+  g128_k32    64, 128^3, 240x320, 4, 32      is 256 KiB: 64 envs x 32 x both masks = 1 GiB, 512 envs = 8 GiB per operator, and three
+                                             masks operators are alive at a time.)  Above 64^3 the operators are make_view_gain's
+                                             and make_view_gain_masks': gnbv_view_gain_slab and gnbv_view_gain_slab_masks; a parent
+                                             build without the latter times gnbv_view_gain_slab only.
 
 Rows per grid: gnbv_view_gain of this build; the same call on the library at --parent-lib (another build of the same ABI, e.g. the
 parent commit's: _lib.activate), on the same grids and poses; gnbv_view_gain_masks with both masks, the hit mask only, the unknown
@@ -33,8 +39,8 @@ from gennbv_amd import _lib  # noqa: E402
 from gennbv_amd.env import synthetic as S  # noqa: E402
 from gennbv_amd.env.config import TaskConfig  # noqa: E402
 from gennbv_amd.eval.baselines import LatticeCandidates  # noqa: E402
-from gennbv_amd.ops.gain_masks import ViewGainMasks  # noqa: E402
-from gennbv_amd.ops.view_gain import ViewGain  # noqa: E402
+from gennbv_amd.ops.gain_masks import make_view_gain_masks  # noqa: E402
+from gennbv_amd.ops.view_gain import MAX_GRID, make_view_gain  # noqa: E402
 from tools.microbench_render import time_calls  # noqa: E402
 from tools.microbench_view_gain import mid_episode_grid, stats  # noqa: E402
 
@@ -48,15 +54,16 @@ def masks_case(name, n, g, h, w, stride, k, args):
     poses = lc.poses(lc.sample(n)).to(DEV)
     grids = {"all_unknown": torch.zeros(n, g ** 3, dtype=torch.int8, device=DEV), "mid_episode": mid_episode_grid(cfg, n, scene)}
     kw = dict(stride=stride, device=DEV, chunk=args.chunk)
-    ops = {"view_gain": ViewGain(n, k, cfg, scene.range_gt, scene.voxel_size, **kw)}
+    ops = {"view_gain": make_view_gain(n, k, cfg, scene.range_gt, scene.voxel_size, **kw)}
     if args.parent_lib:
         _lib.activate(args.parent_lib)  # an operator keeps the library that was active when it was built
-        ops["view_gain_parent"] = ViewGain(n, k, cfg, scene.range_gt, scene.voxel_size, **kw)
-        ops["masks_both_parent"] = ViewGainMasks(n, k, cfg, scene.range_gt, scene.voxel_size, **kw)
+        ops["view_gain_parent"] = make_view_gain(n, k, cfg, scene.range_gt, scene.voxel_size, **kw)
+        if g <= MAX_GRID or hasattr(_lib.load(), "gnbv_view_gain_slab_masks"):
+            ops["masks_both_parent"] = make_view_gain_masks(n, k, cfg, scene.range_gt, scene.voxel_size, **kw)
         _lib.activate()
-    ops["masks_both"] = ViewGainMasks(n, k, cfg, scene.range_gt, scene.voxel_size, **kw)
-    ops["masks_hit"] = ViewGainMasks(n, k, cfg, scene.range_gt, scene.voxel_size, unknown=False, **kw)
-    ops["masks_unknown"] = ViewGainMasks(n, k, cfg, scene.range_gt, scene.voxel_size, hit=False, **kw)
+    ops["masks_both"] = make_view_gain_masks(n, k, cfg, scene.range_gt, scene.voxel_size, **kw)
+    ops["masks_hit"] = make_view_gain_masks(n, k, cfg, scene.range_gt, scene.voxel_size, unknown=False, **kw)
+    ops["masks_unknown"] = make_view_gain_masks(n, k, cfg, scene.range_gt, scene.voxel_size, hit=False, **kw)
     words = ops["masks_both"].words
     mask_bytes = n * k * words * 4
     weights = tuple(int(w) for w in args.weights.split(","))
@@ -76,7 +83,7 @@ def masks_case(name, n, g, h, w, stride, k, args):
         both = ops["masks_both"]
         both(tri, poses)
         plans = {"": both}
-        if args.parent_lib:
+        if "masks_both_parent" in ops:
             plans["_parent"] = ops["masks_both_parent"]
             plans["_parent"](tri, poses)
         for horizon in (1, 3, 5):
@@ -100,11 +107,13 @@ def main():
     ap.add_argument("--parent-lib", default=None, help="another build of libgennbv_hip.so (the same ABI) to time gnbv_view_gain on")
     ap.add_argument("--weights", default="1,4", help="w_unknown,w_hit of the weighted plan")
     ap.add_argument("--chunk", type=int, default=0, help="candidates per workgroup (0 = chosen)")
+    ap.add_argument("--envs128", type=int, default=64, help="envs of the 128^3 cases")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("microbench_gain_masks needs a GPU")
-    table = {"g64_k8": (256, 64, 240, 320, 4, 8), "g64_k32": (256, 64, 240, 320, 4, 32), "g20_k32": (8, 20, 240, 320, 4, 32)}
+    table = {"g64_k8": (256, 64, 240, 320, 4, 8), "g64_k32": (256, 64, 240, 320, 4, 32), "g20_k32": (8, 20, 240, 320, 4, 32),
+             "g128_k8": (args.envs128, 128, 240, 320, 4, 8), "g128_k32": (args.envs128, 128, 240, 320, 4, 32)}
     results = []
     for c in args.cases.split(","):
         if c not in table:
