@@ -24,6 +24,7 @@ import torch
 
 from .. import _lib
 from ..env.config import TaskConfig
+from .cover_greedy import CoverGreedy, check_contact, check_covered, check_rounds
 from .view_gain import MAX_GRID, MAX_GRID_SLAB, ViewGain
 
 
@@ -77,15 +78,9 @@ class ViewGainMasks(ViewGain):
         self.unknown_bits = torch.empty(n, k, self.words, dtype=torch.int32, device=dev) if unknown else None
         self.hit_bits = torch.empty(n, k, self.words, dtype=torch.int32, device=dev) if hit else None
         self.gains0 = torch.empty(n, k, dtype=torch.int32, device=dev)
-        self._plans = {}  # rounds -> (choice, gain, covered)
-        c = _lib.GnbvCoverGreedy()
-        c.n, c.k, c.words = n, k, self.words
-        self._cg = c
-        self._plans_w = {}  # rounds -> (choice, gain, (covered_unknown, covered_hit), plane_gain): plan_weighted's own
         self.plane_gain = None
-        cw = _lib.GnbvCoverGreedyW()
-        cw.n, cw.k, cw.words, cw.planes = n, k, self.words, 2
-        self._cgw = cw
+        self._cg = CoverGreedy(lib, dev, n, k, self.words)  # plan's outputs, apart from ...
+        self._cgw = CoverGreedy(lib, dev, n, k, self.words, planes=2)  # ... plan_weighted's
 
     def _launch(self, a):
         _lib.check(self.lib.gnbv_view_gain_masks(C.byref(a), self.words, _lib.ptr(self.unknown_bits), _lib.ptr(self.hit_bits),
@@ -98,34 +93,16 @@ class ViewGainMasks(ViewGain):
         modified) -> (choice [N,T], gain [N,T], covered [N, words]) int32.  `contact` uint8 [N,K]: non-zero candidates are never
         chosen unless all of an env's are (then candidate 0).  `gains0` [N,K] holds round 0's gain of every candidate.  One
         gnbv_cover_greedy launch; `lazy` changes the work, not the result."""
-        rounds = int(rounds)
-        if not 1 <= rounds <= 4096:
-            raise _lib.GennbvHipError(f"ViewGainMasks.plan: rounds in 1..4096, got {rounds}")
+        rounds = check_rounds("ViewGainMasks.plan", rounds)
         if which not in ("hit", "unknown"):
             raise _lib.GennbvHipError(f"ViewGainMasks.plan: which must be 'hit' or 'unknown', got {which!r}")
         masks = self.hit_bits if which == "hit" else self.unknown_bits
         if masks is None:
             raise _lib.GennbvHipError(f"ViewGainMasks.plan: the {which} mask is not kept ({which}=False)")
-        n, k = self.num_envs, self.k
-        if contact is not None:
-            _lib.require_cuda(contact)
-            if contact.dtype != torch.uint8 or contact.shape != (n, k) or not contact.is_contiguous():
-                raise _lib.GennbvHipError(f"ViewGainMasks.plan: contact must be contiguous uint8 [{n}, {k}]")
-        if covered_bits is not None:
-            _lib.require_cuda(covered_bits)
-            if covered_bits.dtype != torch.int32 or covered_bits.shape != (n, self.words) or not covered_bits.is_contiguous():
-                raise _lib.GennbvHipError(f"ViewGainMasks.plan: covered_bits must be contiguous int32 [{n}, {self.words}], "
-                                          f"got {covered_bits.dtype} {tuple(covered_bits.shape)}")
-        if rounds not in self._plans:
-            dev = self.device
-            self._plans[rounds] = (torch.empty(n, rounds, dtype=torch.int32, device=dev), torch.empty(n, rounds, dtype=torch.int32, device=dev),
-                                   torch.empty(n, self.words, dtype=torch.int32, device=dev))
-        choice, gain, covered = self._plans[rounds]
-        c = self._cg
-        c.rounds, c.mask_bits, c.covered_in, c.contact = rounds, masks.data_ptr(), _lib.ptr(covered_bits), _lib.ptr(contact)
-        c.choice, c.gain, c.covered_out, c.gains0, c.ub, c.lazy = (choice.data_ptr(), gain.data_ptr(), covered.data_ptr(),
-                                                                   self.gains0.data_ptr(), None, int(bool(lazy)))
-        _lib.check(self.lib.gnbv_cover_greedy(C.byref(c), _lib.stream_ptr(self.device)), "gnbv_cover_greedy")
+        check_contact("ViewGainMasks.plan", contact, self.num_envs, self.k)
+        check_covered("ViewGainMasks.plan", covered_bits, self.num_envs, self.words)
+        choice, gain, covered, _ = self._cg.outputs(rounds)
+        self._cg.launch(rounds, masks, covered_bits, contact, choice, gain, covered, self.gains0, None, lazy)
         return choice, gain, covered
 
     def plan_weighted(self, rounds: int, weights=(1, 4), contact: Optional[torch.Tensor] = None, covered_bits=None, lazy: bool = True):
@@ -137,39 +114,20 @@ class ViewGainMasks(ViewGain):
         `plane_gain` int32 [N,T,2] holds the winners' gains per mask, `gains0` [N,K] the weighted round-0 score of every
         candidate.  Outputs are cached per `rounds`, apart from `plan`'s.  One gnbv_cover_greedy_w launch, no host
         synchronisation; `lazy` changes the work, not the result."""
-        rounds = int(rounds)
-        if not 1 <= rounds <= 4096:
-            raise _lib.GennbvHipError(f"ViewGainMasks.plan_weighted: rounds in 1..4096, got {rounds}")
+        rounds = check_rounds("ViewGainMasks.plan_weighted", rounds)
         for name, masks in (("unknown", self.unknown_bits), ("hit", self.hit_bits)):
             if masks is None:
                 raise _lib.GennbvHipError(f"ViewGainMasks.plan_weighted needs both masks: the {name} mask is not kept ({name}=False)")
         w = plan_weights(weights, self.words)
-        n, k = self.num_envs, self.k
-        if contact is not None:
-            _lib.require_cuda(contact)
-            if contact.dtype != torch.uint8 or contact.shape != (n, k) or not contact.is_contiguous():
-                raise _lib.GennbvHipError(f"ViewGainMasks.plan_weighted: contact must be contiguous uint8 [{n}, {k}]")
+        check_contact("ViewGainMasks.plan_weighted", contact, self.num_envs, self.k)
         if covered_bits is not None:
             if not isinstance(covered_bits, (tuple, list)) or len(covered_bits) != 2:
                 raise _lib.GennbvHipError("ViewGainMasks.plan_weighted: covered_bits must be None or a pair (unknown, hit)")
             for cb in covered_bits:
-                _lib.require_cuda(cb)
-                if cb.dtype != torch.int32 or cb.shape != (n, self.words) or not cb.is_contiguous():
-                    raise _lib.GennbvHipError(f"ViewGainMasks.plan_weighted: covered_bits must be contiguous int32 [{n}, {self.words}], "
-                                              f"got {cb.dtype} {tuple(cb.shape)}")
-        if rounds not in self._plans_w:
-            dev = self.device
-            self._plans_w[rounds] = (torch.empty(n, rounds, dtype=torch.int32, device=dev), torch.empty(n, rounds, dtype=torch.int32, device=dev),
-                                     (torch.empty(n, self.words, dtype=torch.int32, device=dev), torch.empty(n, self.words, dtype=torch.int32, device=dev)),
-                                     torch.empty(n, rounds, 2, dtype=torch.int32, device=dev))
-        choice, gain, covered, self.plane_gain = self._plans_w[rounds]
-        c = self._cgw
-        c.rounds, c.contact, c.lazy = rounds, _lib.ptr(contact), int(bool(lazy))
-        for p, masks in enumerate((self.unknown_bits, self.hit_bits)):
-            c.weight[p], c.mask_bits[p], c.covered_out[p] = w[p], masks.data_ptr(), covered[p].data_ptr()
-            c.covered_in[p] = None if covered_bits is None else covered_bits[p].data_ptr()
-        c.choice, c.gain, c.plane_gain, c.gains0, c.ub = choice.data_ptr(), gain.data_ptr(), self.plane_gain.data_ptr(), self.gains0.data_ptr(), None
-        _lib.check(self.lib.gnbv_cover_greedy_w(C.byref(c), _lib.stream_ptr(self.device)), "gnbv_cover_greedy_w")
+                check_covered("ViewGainMasks.plan_weighted", cb, self.num_envs, self.words)
+        choice, gain, covered, self.plane_gain = self._cgw.outputs(rounds)
+        self._cgw.launch(rounds, (self.unknown_bits, self.hit_bits), covered_bits, contact, choice, gain, covered, self.gains0, None, lazy,
+                         weights=w, plane_gain=self.plane_gain)
         return choice, gain, covered
 
 

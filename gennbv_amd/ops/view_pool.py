@@ -18,6 +18,7 @@ import torch
 from .. import _lib
 from ..env import synthetic as S
 from ..env.config import TaskConfig
+from .cover_greedy import CoverGreedy, check_contact, check_covered, check_rounds
 
 MAX_GRID = 128
 MAX_POOL = 4096
@@ -94,27 +95,15 @@ class ViewPool:
         self._gains = torch.empty(n, p, dtype=torch.int32, device=dev)
         self._choice1 = torch.empty(n, 1, dtype=torch.int32, device=dev)
         self._gain1 = torch.empty(n, 1, dtype=torch.int32, device=dev)
-        self._plans = {}  # rounds -> (choice, gain, covered)
-        c = _lib.GnbvCoverGreedy()
-        c.n, c.k, c.words = n, p, self.words
-        c.mask_bits, c.contact = self.masks.data_ptr(), _lib.ptr(self.contact)
-        self._cg = c
+        self._cg = CoverGreedy(self.lib, dev, n, p, self.words)
 
-    def _covered(self, covered_bits):
-        if covered_bits is None:
-            return None
-        _lib.require_cuda(covered_bits)
-        if covered_bits.dtype != torch.int32 or covered_bits.shape != (self.num_envs, self.words) or not covered_bits.is_contiguous():
-            raise _lib.GennbvHipError(f"ViewPool: covered_bits must be contiguous int32 [{self.num_envs}, {self.words}], "
-                                      f"got {covered_bits.dtype} {tuple(covered_bits.shape)}")
-        return covered_bits
+    def _covered(self, who, covered_bits):
+        return check_covered(who, covered_bits, self.num_envs, self.words)
 
-    def _launch(self, rounds, covered_in, choice, gain, covered_out, gains0, ub, lazy, contact=None):
-        c = self._cg
-        c.contact = _lib.ptr(self.contact if contact is None else contact)
-        c.rounds, c.covered_in, c.choice, c.gain = int(rounds), _lib.ptr(covered_in), choice.data_ptr(), gain.data_ptr()
-        c.covered_out, c.gains0, c.ub, c.lazy = _lib.ptr(covered_out), _lib.ptr(gains0), _lib.ptr(ub), int(bool(lazy))
-        _lib.check(self.lib.gnbv_cover_greedy(C.byref(c), _lib.stream_ptr(self.device)), "gnbv_cover_greedy")
+    def _round(self, covered_in, gains0, ub, lazy, contact=None):
+        """one round into _choice1 / _gain1, no covered_out"""
+        self._cg.launch(1, self.masks, covered_in, self.contact if contact is None else contact, self._choice1, self._gain1, None,
+                        gains0, ub, lazy)
 
     def select(self, covered_bits: Optional[torch.Tensor], ub: Optional[torch.Tensor] = None, contact: Optional[torch.Tensor] = None):
         """One round against covered_bits [N, words] (None = nothing covered) -> (choice [N], gain [N]) int32.  `ub` [N,P]
@@ -123,18 +112,15 @@ class ViewPool:
         `ub` every candidate is evaluated.  `contact` [N,P] u8 replaces the pool's static contact for this call only (e.g.
         the static contact | the flight from the current pose); a bound does not depend on contact -- the kernel keeps a
         contact candidate's bound as it is, still >= its gain -- so `ub` stays valid while the contact set changes."""
-        cov = self._covered(covered_bits)
-        if contact is not None:
-            _lib.require_cuda(contact)
-            if contact.dtype != torch.uint8 or contact.shape != (self.num_envs, self.pool_size) or not contact.is_contiguous():
-                raise _lib.GennbvHipError(f"ViewPool: contact must be contiguous uint8 [{self.num_envs}, {self.pool_size}]")
+        cov = self._covered("ViewPool.select", covered_bits)
+        check_contact("ViewPool.select", contact, self.num_envs, self.pool_size)
         if ub is not None:
             _lib.require_cuda(ub)
             if ub.dtype != torch.int32 or ub.shape != (self.num_envs, self.pool_size) or not ub.is_contiguous():
-                raise _lib.GennbvHipError(f"ViewPool: ub must be contiguous int32 [{self.num_envs}, {self.pool_size}]")
-            self._launch(1, cov, self._choice1, self._gain1, None, None, ub, True, contact)
+                raise _lib.GennbvHipError(f"ViewPool.select: ub must be contiguous int32 [{self.num_envs}, {self.pool_size}]")
+            self._round(cov, None, ub, True, contact)
         else:
-            self._launch(1, cov, self._choice1, self._gain1, None, self._gains, None, False, contact)
+            self._round(cov, self._gains, None, False, contact)
         return self._choice1[:, 0], self._gain1[:, 0]
 
     def plan(self, rounds: int, covered_bits: Optional[torch.Tensor] = None, lazy: bool = True):
@@ -142,21 +128,15 @@ class ViewPool:
         -> (choice [N,T], gain [N,T], covered [N, words] = covered_bits | the chosen masks).  `lazy` changes the work, not the
         result.  The plan keeps the pool's static contact (poses that collide): an offline plan has no "current pose" per
         round, so no flight is tested."""
-        rounds = int(rounds)
-        if not 1 <= rounds <= 4096:
-            raise _lib.GennbvHipError(f"ViewPool.plan: rounds in 1..4096, got {rounds}")
-        cov = self._covered(covered_bits)
-        if rounds not in self._plans:
-            n, dev = self.num_envs, self.device
-            self._plans[rounds] = (torch.empty(n, rounds, dtype=torch.int32, device=dev), torch.empty(n, rounds, dtype=torch.int32, device=dev),
-                                   torch.empty(n, self.words, dtype=torch.int32, device=dev))
-        choice, gain, covered = self._plans[rounds]
-        self._launch(rounds, cov, choice, gain, covered, self._gains, None, lazy)
+        rounds = check_rounds("ViewPool.plan", rounds)
+        cov = self._covered("ViewPool.plan", covered_bits)
+        choice, gain, covered, _ = self._cg.outputs(rounds)
+        self._cg.launch(rounds, self.masks, cov, self.contact, choice, gain, covered, self._gains, None, lazy)
         return choice, gain, covered
 
     def gains(self, covered_bits: Optional[torch.Tensor]) -> torch.Tensor:
         """[N,P] int32: popcount(mask & ~covered_bits) of every candidate."""
-        self._launch(1, self._covered(covered_bits), self._choice1, self._gain1, None, self._gains, None, False)
+        self._round(self._covered("ViewPool.gains", covered_bits), self._gains, None, False)
         return self._gains
 
     def union_bits(self) -> torch.Tensor:

@@ -24,29 +24,29 @@ def _dev(a, dtype):
     return torch.from_numpy(np.ascontiguousarray(a).view(dtype) if a.dtype != dtype else np.ascontiguousarray(a)).to(DEV)
 
 
-def _case(seed, k, words, density, cov_kind, contact_kind):
-    """masks uint32 [N, k, words] with a duplicated and an all-zero row per env where k allows, covered [N, words] or None,
-    contact u8 [N, k] or None"""
+def _case(seed, k, words, density, cov_kind, contact_kind, n=N):
+    """masks uint32 [n, k, words] with a duplicated and an all-zero row per env where k allows, covered [n, words] or None,
+    contact u8 [n, k] or None"""
     rng = np.random.default_rng(seed)
-    m = np.stack([CG.random_masks(rng, k, words, density) for _ in range(N)])
+    m = np.stack([CG.random_masks(rng, k, words, density) for _ in range(n)])
     if k > 3:
-        for e in range(N):
+        for e in range(n):
             m[e, rng.integers(k)] = m[e, rng.integers(k)]
             m[e, rng.integers(k)] = 0
-    cov = None if cov_kind == "null" else np.stack([CG.random_masks(rng, 1, words, 0.3)[0] for _ in range(N)])
-    contact = {"none": None, "random": (rng.random((N, k)) < 0.3).astype(np.uint8), "all": np.ones((N, k), np.uint8)}[contact_kind]
+    cov = None if cov_kind == "null" else np.stack([CG.random_masks(rng, 1, words, 0.3)[0] for _ in range(n)])
+    contact = {"none": None, "random": (rng.random((n, k)) < 0.3).astype(np.uint8), "all": np.ones((n, k), np.uint8)}[contact_kind]
     return m, cov, contact
 
 
 def _reference(m, cov, contact, rounds):
-    k, words = m.shape[1], m.shape[2]
-    return CG.batch_exhaustive(m, np.zeros((N, words), np.uint32) if cov is None else cov,
-                               np.zeros((N, k), np.uint8) if contact is None else contact, rounds)
+    n, k, words = m.shape
+    return CG.batch_exhaustive(m, np.zeros((n, words), np.uint32) if cov is None else cov,
+                               np.zeros((n, k), np.uint8) if contact is None else contact, rounds)
 
 
 def _covered_after(m, cov, choice):
-    out = np.zeros((N, m.shape[2]), np.uint32) if cov is None else cov.copy()
-    for e in range(N):
+    out = np.zeros((m.shape[0], m.shape[2]), np.uint32) if cov is None else cov.copy()
+    for e in range(m.shape[0]):
         for j in choice[e]:
             out[e] |= m[e, j]
     return out
@@ -84,26 +84,27 @@ class _Call:
                 None if self.gains0 is None else self.gains0.cpu().numpy())
 
 
-@pytest.mark.parametrize("g", [20, 33])
-@pytest.mark.parametrize("k", [1, 7, 70])
-def test_equals_the_reference(k, g):
-    words = _words(g)
-    kinds = list(itertools.product((0.02, 0.5), ("null", "random"), ("none", "random", "all")))
-    checked = 0
+def _compare_with_the_reference(seed, n, k, words, densities, rounds_list):
+    """Every (density, covered_in, contact) kind x rounds x lazy x the three ways round 0 is reached, outputs prefilled with
+    garbage, `==` against the reference -> the reference of the last kind at the most rounds, and per kind (density, round-0 top
+    shared by two candidates in some env, a last round at gain 0 in some env)."""
+    kinds = list(itertools.product(densities, ("null", "random"), ("none", "random", "all")))
+    checked, seen = 0, []
     for idx, (density, cov_kind, contact_kind) in enumerate(kinds):
-        m, cov, contact = _case(1000 * k + 10 * g + idx, k, words, density, cov_kind, contact_kind)
-        full = _reference(m, cov, contact, max(5, k + 3))  # k = 1: 5 rounds are more than k + 3
-        for rounds in (1, 5, k + 3):
+        m, cov, contact = _case(seed + idx, k, words, density, cov_kind, contact_kind, n)
+        full = _reference(m, cov, contact, max(rounds_list))
+        seen.append((density, bool(((full[3] == full[3].max(1, keepdims=True)).sum(1) > 1).any()), bool((full[1][:, -1] == 0).any())))
+        for rounds in rounds_list:
             want_choice, want_gain = full[0][:, :rounds], full[1][:, :rounds]
             want_cov = _covered_after(m, cov, want_choice)
             for lazy in (0, 1):
                 # the three ways round 0 is reached: wide pass into gains0; inside the workgroup; from a row of unknown bounds
                 for mode in ("gains0", "plain", "ub"):
-                    ub = torch.full((N, k), CG.UNKNOWN, dtype=torch.int32, device=DEV) if mode == "ub" else None
+                    ub = torch.full((n, k), CG.UNKNOWN, dtype=torch.int32, device=DEV) if mode == "ub" else None
                     call = _Call(m, cov, contact, rounds, lazy, gains0=mode == "gains0", ub=ub, covered_out=not (rounds == 1 and mode == "plain"))
                     assert call.run() == 0
                     choice, gain, cov_out, gains0 = call.outputs()
-                    tag = (k, g, density, cov_kind, contact_kind, rounds, lazy, mode)
+                    tag = (n, k, words, density, cov_kind, contact_kind, rounds, lazy, mode)
                     assert np.array_equal(choice, want_choice), tag
                     assert np.array_equal(gain, want_gain), tag
                     if cov_out is not None:
@@ -116,9 +117,29 @@ def test_equals_the_reference(k, g):
                         if lazy == 0:
                             assert np.array_equal(ub.cpu().numpy(), CG.popcount(m & ~_covered_after(m, cov, want_choice[:, :rounds - 1])[:, None, :])), tag
                     checked += 1
-    assert checked == len(kinds) * 3 * 2 * 3
+    assert checked == len(kinds) * len(rounds_list) * 2 * 3
+    return full, seen
+
+
+@pytest.mark.parametrize("g", [20, 33])
+@pytest.mark.parametrize("k", [1, 7, 70])
+def test_equals_the_reference(k, g):
+    full, _ = _compare_with_the_reference(1000 * k + 10 * g, N, k, _words(g), (0.02, 0.5), (1, 5, k + 3))  # k = 1: 5 rounds are more than k + 3
     if k == 70:
         assert (full[1] > 0).any() and (full[1][:, -1] == 0).all()  # k + 3 rounds: the last ones repeat a view at gain 0
+
+
+# The regimes the sizes above stop short of:
+#   n = 9        a second group of 8 envs in the gains kernel's block -> (env, candidates) mapping, e = (slot / per_env) * 8 + xcd;
+#   k = 1030     more than 16 waves x 64 lanes of candidates: the key scan j = wave + waves * lane takes a second trip, and the
+#                lazy passes have stale tops in every wave;
+#   words = 4    one 16-byte group per row: 63 lanes of a wave read nothing.
+# The sparse density leaves about four set bits among all of an env's rows: round 0's top is shared and five rounds run out of gain.
+@pytest.mark.parametrize("n,k,words", [(9, 7, 252), (N, 1030, 4), (N, 1030, 252), (N, 70, 4)])
+def test_equals_the_reference_in_a_second_env_group_a_second_key_trip_and_one_group_rows(n, k, words):
+    sparse = 4.0 / (k * words * 32)
+    _, seen = _compare_with_the_reference(100000 * n + 10 * k + words, n, k, words, (sparse, 0.5), (1, 5))
+    assert any(tie for _, tie, _ in seen) and any(zero for d, _, zero in seen if d == sparse)
 
 
 @pytest.mark.parametrize("contact_kind", ["none", "random"])

@@ -22,7 +22,9 @@ mask only.  Beside every masks row: the bytes the call stores more than gnbv_vie
 this build's gnbv_view_gain, and the store rate the two imply.  Then, for horizon 1, 3 and 5: `plan(horizon)` on the hit mask and
 on the unknown mask, `plan_weighted(horizon, weights)` on both (one gnbv_cover_greedy_w launch; --weights, default 1,4), the sum
 of the two single-mask plans it is set against, and -- with --parent-lib -- the two single-mask plans of that build on the same
-masks (the parent has no weighted plan).
+masks, then the A/B of tools/microbench_cover_greedy.py (`ab`: this build, that build, that build again, alternated in one call,
+both builds on this build's masks after asserting equal masks and outputs) for `plan("hit")`, `plan("unknown")` and, where that
+build has gnbv_cover_greedy_w, `plan_weighted`.
 """
 from __future__ import annotations
 
@@ -41,6 +43,7 @@ from gennbv_amd.env.config import TaskConfig  # noqa: E402
 from gennbv_amd.eval.baselines import LatticeCandidates  # noqa: E402
 from gennbv_amd.ops.gain_masks import make_view_gain_masks  # noqa: E402
 from gennbv_amd.ops.view_gain import MAX_GRID, make_view_gain  # noqa: E402
+from tools.microbench_cover_greedy import ab  # noqa: E402
 from tools.microbench_render import time_calls  # noqa: E402
 from tools.microbench_view_gain import mid_episode_grid, stats  # noqa: E402
 
@@ -93,6 +96,20 @@ def masks_case(name, n, g, h, w, stride, k, args):
             row = stats(time_calls(lambda: both.plan_weighted(horizon, weights=weights), args.iters, args.repeats))
             row["hit_plus_unknown_us"] = out[f"{gname}_plan_{horizon}"]["us_median"] + out[f"{gname}_plan_unknown_{horizon}"]["us_median"]
             out[f"{gname}_plan_weighted_{horizon}"] = row
+        if "_parent" in plans:
+            par = plans["_parent"]
+            own = par.unknown_bits, par.hit_bits  # the same masks for both libraries: where two rows lie changes a two-plane read
+            assert torch.equal(own[0], both.unknown_bits) and torch.equal(own[1], both.hit_bits)
+            par.unknown_bits, par.hit_bits = both.unknown_bits, both.hit_bits
+            calls = {"plan": lambda op, t: op.plan(t, which="hit"), "plan_unknown": lambda op, t: op.plan(t, which="unknown")}
+            if hasattr(par.lib, "gnbv_cover_greedy_w"):
+                calls["plan_weighted"] = lambda op, t: (lambda c, g, cov: (c, g, *cov))(*op.plan_weighted(t, weights=weights))
+            for horizon in (1, 3, 5):
+                for cname, call in calls.items():
+                    mine = [t.clone() for t in call(both, horizon)] + [both.gains0.clone()]
+                    assert all(torch.equal(x, y) for x, y in zip(mine, [*call(par, horizon), par.gains0])), (cname, horizon)
+                    ab(out, f"{gname}_{cname}_{horizon}", [lambda: call(both, horizon)] + [lambda: call(par, horizon)] * 2, args.iters, args.repeats)
+            par.unknown_bits, par.hit_bits = own
         out[gname + "_mean_plan5_weighted_plane_gain"] = both.plane_gain.float().mean(dim=0).tolist()
         out[gname + "_mean_gain"] = want.float().mean(dim=(0, 1)).tolist()
         out[gname + "_mean_plan5_gain"] = both.plan(5, which="hit")[1].float().mean(dim=0).tolist()
