@@ -43,6 +43,38 @@ __device__ __forceinline__ float wave_reduce_sum(float v)
     return v;
 }
 
+// ---- block sum of N counts per lane: wave reductions -> one partial per wave in `part` (the caller's LDS, one row per wave of
+// the block) -> barrier -> thread 0 adds the partials in wave order; v[] holds the block's sums in thread 0 only.  Every thread
+// of the block calls it (the barrier is inside).  The caller owes the barrier between thread 0's reads of `part` and the next
+// call's writes: in a loop over candidates the barrier at the loop's head is that one, since thread 0 reads before it arrives there
+// and the waves write after.
+template <int N>
+__device__ __forceinline__ void block_sum(int (&v)[N], int (*part)[N])
+{
+#pragma unroll
+    for (int q = 0; q < N; ++q) {
+        v[q] = wave_reduce_sum(v[q]);
+        if ((threadIdx.x & (kWave - 1)) == 0) part[threadIdx.x / kWave][q] = v[q];
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+#pragma unroll
+    for (int q = 0; q < N; ++q) v[q] = 0;
+    for (int w = 0; w < (int)blockDim.x / kWave; ++w)
+#pragma unroll
+        for (int q = 0; q < N; ++q) v[q] += part[w][q];
+}
+
+// ---- XCD-aware decode of blockIdx.x: consecutive workgroups go to the 8 XCDs in turn, so with env = 8 (slot / per_env) + xcd all
+// per_env workgroups of an env run on one XCD and share its L2.  The launch has ceil(n / 8) * 8 * per_env workgroups; the caller
+// drops env >= n.  rem: the workgroup's number within its env, in [0, per_env).
+__device__ __forceinline__ int xcd_env(int per_env, int &rem)
+{
+    const int b = blockIdx.x, slot = b >> 3;
+    rem = slot % per_env;
+    return (slot / per_env) * 8 + (b & 7);
+}
+
 // ---- all-lanes reductions: a butterfly, every lane ends with the same bits.  The fp64 sum adds in the order d = 1, 2, .. 32:
 // the winding number of collide.hip is these bits.  The integer ones give the same value in any order.
 __device__ __forceinline__ double wave_sum_all(double v)

@@ -113,12 +113,10 @@ __device__ __forceinline__ int wave_score(const CgParams &p, size_t row, const u
 template <int P, bool W>
 __global__ __launch_bounds__(kCgGainWaves * kWave) void k_cg_gains(CgParams p)
 {
-    // XCD-aware block -> (env, group of candidates): all workgroups of an env run on one XCD (viewcover.hip k_view_cover)
-    const int b = blockIdx.x, xcd = b & 7, slot = b >> 3;
-    const int per_env = (p.k + kCgGainWaves - 1) / kCgGainWaves;
-    const int e = (slot / per_env) * 8 + xcd;
+    int group;  // of candidates, one per wave
+    const int e = xcd_env((p.k + kCgGainWaves - 1) / kCgGainWaves, group);
     const int lane = threadIdx.x & (kWave - 1);
-    const int j = (slot % per_env) * kCgGainWaves + (int)threadIdx.x / kWave;
+    const int j = group * kCgGainWaves + (int)threadIdx.x / kWave;
     if (e >= p.n || j >= p.k) return;
     const uint32_t *cov[P];
 #pragma unroll

@@ -8,13 +8,12 @@
 // (voxel_frame.h point_to_voxel, the update's own code).  No image is ever stored.
 //
 //   k_view_cover<WIN>   workgroup (env, chunk of candidates[, window of bit-set words]):
-//     1. 16 lanes build the camera matrices of the next 16 candidates (raytrace.h camera_of_pose: fp64 trig, off the
-//        per-candidate path);
+//     1. the camera batch (view_kernels.h: 16 lanes build the matrices of the next 16 candidates, off the per-candidate path);
 //     2. one wave per 8 x 8 tile of lattice pixels (ray coherence, as the renderer), one ray per lane;
 //     3. the seen set S is a bit set in LDS (G^3 / 8 bytes: 32 KiB at 64^3, 137 KiB at 104^3): atomicOr returns the old word,
 //        and the lane that set a bit first reads the env's gt and scanned words (L2-resident: an env's workgroups run on one
 //        XCD) and counts |S & gt| and |S & gt & ~scanned|;
-//     4. wave reductions -> per-wave partials in LDS -> lane 0 sums them in wave order and stores the three integers;
+//     4. block_sum (common.h), lane 0 stores the three integers;
 //     5. seen_bits: the non-zero words of (bit set & gt) are OR-ed into global memory (device-scope atomicOr);
 //     6. the workgroup clears the bit set (16-byte stores) before the next candidate.  With cover == NULL (accumulate only)
 //        nothing is counted, the bit set is never cleared and it is flushed once, after the last candidate.
@@ -29,15 +28,14 @@
 #include "backproject.h"
 #include "raytrace.h"
 #include "scene_cells.h"
+#include "view_kernels.h"
 #include "voxel_frame.h"
 #include "../../include/gennbv_hip.h"
 
 namespace {
 
 constexpr int kTile = 8;            // 8 x 8 lattice pixels = one wave
-constexpr int kMaxThreads = 1024;
 constexpr int kMaxGrid = 128;
-constexpr int kCamBatch = 16;       // camera matrices built at a time
 constexpr size_t kLdsBitsMax = 144 * 1024;  // the bit set's share of the 160 KiB (static LDS: 1.2 KiB)
 
 struct VcParams {
@@ -60,19 +58,17 @@ __global__ __launch_bounds__(256) void k_vc_zero(int32_t *cover, int64_t count)
 }
 
 template <bool WIN, bool MASK>
-__global__ __launch_bounds__(kMaxThreads) void k_view_cover(VcParams p)
+__global__ __launch_bounds__(kViewMaxThreads) void k_view_cover(VcParams p)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t s_bits[];
     __shared__ float s_cam[kCamBatch][16];
-    __shared__ int s_part[kMaxThreads / kWave][3];
+    __shared__ int s_part[kViewMaxThreads / kWave][3];
 
     const int tid = threadIdx.x, nthreads = blockDim.x;
-    // XCD-aware block -> (env, chunk[, window]): all workgroups of an env run on one XCD (voxel.hip k_hit_mask)
-    const int b = blockIdx.x, xcd = b & 7, slot = b >> 3;
-    const int per_env = p.chunks * p.windows;
-    const int e = (slot / per_env) * 8 + xcd;
+    int rem;  // (chunk[, window])
+    const int e = xcd_env(p.chunks * p.windows, rem);
     if (e >= p.n) return;
-    const int rem = slot % per_env, ch = rem % p.chunks, win = WIN ? rem / p.chunks : 0;
+    const int ch = rem % p.chunks, win = WIN ? rem / p.chunks : 0;
     const int w0 = win * p.nw;                                  // first bit-set word of this workgroup
     const int nw = WIN ? min(p.nw, p.vwords - w0) : p.vwords;   // a multiple of 4 (nw and vwords are)
     const int j0 = ch * p.chunk, j1 = min(p.k, j0 + p.chunk);
@@ -86,7 +82,6 @@ __global__ __launch_bounds__(kMaxThreads) void k_view_cover(VcParams p)
     const uint32_t *scanned = p.scanned != nullptr ? p.scanned + (size_t)e * p.words : nullptr;
     const bool count = p.cover != nullptr;
     const int wave = tid / kWave, nwaves = nthreads / kWave, lane = tid & (kWave - 1);
-    const int half = p.stride / 2;
 
     // (bit set & gt) -> seen_bits: the non-zero words, 16 bytes at a time; `clear` also empties the words a lane flushed
     auto flush = [&](bool clear) {
@@ -103,21 +98,18 @@ __global__ __launch_bounds__(kMaxThreads) void k_view_cover(VcParams p)
     };
 
     for (int j = j0; j < j1; ++j) {
-        const int cslot = (j - j0) % kCamBatch;
-        if (cslot == 0) {
-            // ---- 1. cameras of the next kCamBatch candidates (the slots' last readers passed the barrier that ended j - 1)
-            if (tid < kCamBatch && j + tid < j1) camera_of_pose(p.poses + ((size_t)e * p.k + j + tid) * 6, s_cam[tid]);
-        }
+        // ---- 1. the camera batch (the slots' last readers passed the barrier that ended j - 1)
+        const int cslot = camera_batch(s_cam, p.poses + (size_t)e * p.k * 6, j0, j, j1, [](int, int, const float *, const float *) {});
         __syncthreads();  // cameras ready; bit set clear
 
         // ---- 2 / 3. one wave per tile of lattice pixels, one ray per lane
         const float *M = s_cam[cslot];
-        int n_new = 0, n_seen = 0, n_hits = 0;
+        int cnt[3] = {0, 0, 0};  // new gt voxels, seen gt voxels, hits
         for (int tile = wave; tile < p.tiles; tile += nwaves) {
             const int iu = (tile % p.tiles_x) * kTile + (lane & 7);
             const int iv = (tile / p.tiles_x) * kTile + (lane >> 3);
             if (iu >= p.nu || iv >= p.nv) continue;
-            const float fu = (float)(half + iu * p.stride), fv = (float)(half + iv * p.stride);
+            const float fu = (float)lattice_pixel(iu, p.stride), fv = (float)lattice_pixel(iv, p.stride);
             float best;
             int obj;
             trace_pixel(p.sc, e, M, p.kinv.k, fu, fv, best, obj);
@@ -128,49 +120,32 @@ __global__ __launch_bounds__(kMaxThreads) void k_view_cover(VcParams p)
             int ix[3];
             const int lin = point_to_voxel(wp, f, g, ix);
             if (lin < 0) continue;
-            if (!WIN || win == 0) ++n_hits;
+            if (!WIN || win == 0) ++cnt[2];
             const unsigned wi = (unsigned)((lin >> 5) - w0);
             if (wi >= (unsigned)nw) continue;  // another window's word
             const uint32_t bit = 1u << (lin & 31);
-            const uint32_t old = atomicOr(&s_bits[wi], bit);
-            if (count && (old & bit) == 0u && (gt[lin >> 5] & bit) != 0u) {
-                ++n_seen;
-                if (scanned == nullptr || (scanned[lin >> 5] & bit) == 0u) ++n_new;
+            if (mark_first(s_bits + wi, lin & 31) && count && (gt[lin >> 5] & bit) != 0u) {
+                ++cnt[1];
+                if (scanned == nullptr || (scanned[lin >> 5] & bit) == 0u) ++cnt[0];
             }
         }
 
-        // ---- 4. the three sums, in wave order
-        if (count) {
-            n_new = wave_reduce_sum(n_new);
-            n_seen = wave_reduce_sum(n_seen);
-            n_hits = wave_reduce_sum(n_hits);
-            if (lane == 0) {
-                s_part[wave][0] = n_new;
-                s_part[wave][1] = n_seen;
-                s_part[wave][2] = n_hits;
-            }
-        }
-        __syncthreads();  // every ray of candidate j is done: partials and bit set complete, camera slot free
+        // ---- 4. the three sums; without `cover` only the barrier (`count` is the same in every thread).  Either barrier: every
+        //      ray of candidate j is done, the bit set is complete, the camera slot free
+        if (count) block_sum(cnt, s_part);
+        else __syncthreads();
         if (!count && !MASK) continue;  // accumulate only: the bit set keeps growing
         if (count && tid == 0) {
-            int a = 0, c = 0, d = 0;
-            for (int w = 0; w < nwaves; ++w) {
-                a += s_part[w][0];
-                c += s_part[w][1];
-                d += s_part[w][2];
-            }
             int32_t *o = p.cover + ((size_t)e * p.k + j) * 3;
-            if (WIN) {
-                if (a != 0) atomicAdd(o, a);
-                if (c != 0) atomicAdd(o + 1, c);
-                if (d != 0) atomicAdd(o + 2, d);
-            } else {
-                o[0] = a; o[1] = c; o[2] = d;
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                if (!WIN) o[q] = cnt[q];
+                else if (cnt[q] != 0) atomicAdd(o + q, cnt[q]);
             }
         }
         // ---- 5 / 6. flush, then clear for the next candidate (a lane clears the words it flushed: no barrier between the
-        //      two; the clear is ordered in front of the next rays by the barrier at the loop's head; lane 0 reads s_part
-        //      before it arrives there, the waves write it after)
+        //      two; the clear is ordered in front of the next rays by the barrier at the loop's head, which also is the one
+        //      block_sum leaves to its caller)
         if (MASK) {
             // the candidate's mask row: this workgroup owns words [w0, w0 + nw) of it, every one is stored
             uint32_t *row = p.mask + ((size_t)e * p.k + j) * p.words;
@@ -205,10 +180,7 @@ __global__ __launch_bounds__(kMaxThreads) void k_view_cover(VcParams p)
 template <bool WIN, bool MASK>
 static int launch_view_cover(const VcParams &p, unsigned blocks, int threads, size_t lds, hipStream_t st)
 {
-    // (per call: the attribute belongs to the current device's copy of the kernel)
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute((const void *)k_view_cover<WIN, MASK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return (int)hipGetLastError();
+    if (!view_raise_lds(k_view_cover<WIN, MASK>, lds)) return (int)hipGetLastError();
     hipLaunchKernelGGL((k_view_cover<WIN, MASK>), dim3(blocks), dim3(threads), lds, st, p);
     return gnbv_launch_status();
 }
@@ -258,22 +230,15 @@ static int view_cover_impl(const GnbvMeshScene *scene, const GnbvViewCover *args
     p.nw = nw;
     p.windows = (p.vwords + nw - 1) / nw;
     // candidates per workgroup: two workgroups per compute unit when n allows it; the cameras and the frame are built per workgroup
-    int chunk = a.chunk;
-    if (chunk == 0) {
-        const int want = (512 + a.n * p.windows - 1) / (a.n * p.windows);  // chunks per env
-        chunk = (a.k + want - 1) / want;
-    }
-    chunk = chunk < 1 ? 1 : (chunk > a.k ? a.k : chunk);
-    p.chunk = chunk;
-    p.chunks = (a.k + chunk - 1) / chunk;
+    p.chunk = view_chunk(a.chunk, a.k, 512, a.n * p.windows);
+    p.chunks = (a.k + p.chunk - 1) / p.chunk;
     const int64_t blocks = (int64_t)((a.n + 7) / 8 * 8) * p.chunks * p.windows;
     GNBV_CHECK_ARG(blocks <= 0x7fffffff);
     p.poses = a.poses; p.range_gt = a.range_gt; p.voxel_size = a.voxel_size;
     for (int i = 0; i < 9; ++i) p.kinv.k[i] = a.inv_intri[i];
     p.h = a.h; p.w = a.w; p.stride = a.stride;
-    const int half = a.stride / 2;
-    p.nu = half < a.w ? (a.w - half + a.stride - 1) / a.stride : 0;
-    p.nv = half < a.h ? (a.h - half + a.stride - 1) / a.stride : 0;
+    const ViewLattice lat = view_lattice(a.h, a.w, a.stride);
+    p.nu = lat.nu; p.nv = lat.nv;
     p.tiles_x = (p.nu + kTile - 1) / kTile;
     p.tiles = p.tiles_x * ((p.nv + kTile - 1) / kTile);
     p.sense_dist = a.depth_sense_dist;
@@ -284,7 +249,7 @@ static int view_cover_impl(const GnbvMeshScene *scene, const GnbvViewCover *args
     p.mask = reinterpret_cast<uint32_t *>(mask_bits);
     const size_t lds = (size_t)nw * sizeof(uint32_t);
     int threads = (p.tiles > 0 ? p.tiles : 1) * kWave;
-    threads = threads > kMaxThreads ? kMaxThreads : threads;
+    threads = threads > kViewMaxThreads ? kViewMaxThreads : threads;
     hipStream_t st = gnbv_stream(stream);
     if (p.windows > 1) {
         if (a.cover != nullptr) {

@@ -1,32 +1,27 @@
 // viewgain.hip -- view gain of candidate camera poses against the tri-class grid an env holds now, on MI355X.
 //
 // "How much would the map change if the camera went to pose p?"  For env e, candidate j (DESIGN.md "View gain and baseline
-// policies"; include/gennbv_hip.h gnbv_view_gain has the exact definition): the rays of the pixel lattice u = s/2 + i s,
-// v = s/2 + j s end at the world point the voxel update would compute for that pixel at depth `range` (pixel_to_world of
-// backproject.h, the canonical fp32 chain); source and target voxel are the unclamped pose_to_idx; each ray visits the in-grid
-// voxels of the reference's integer Bresenham (voxel.hip bresenham_walk) in order and stops in front of the first occupied one.
-// Three int32 per candidate: DISTINCT unknown voxels visited by any ray, the same over the rays that were stopped, stopped rays.
+// policies"; include/gennbv_hip.h gnbv_view_gain has the exact definition): the rays of the pixel lattice (view_kernels.h) end at
+// the world point the voxel update would compute for that pixel at depth `range` (pixel_to_world of backproject.h, the canonical
+// fp32 chain); source and target voxel are the unclamped pose_to_idx; each ray visits the in-grid voxels of the reference's
+// integer Bresenham in order and stops in front of the first occupied one.  Three int32 per candidate: DISTINCT unknown voxels
+// visited by any ray, the same over the rays that were stopped, stopped rays.
 //
-//   k_view_gain   workgroup (env, chunk of candidates):
-//     1. the env's grid is packed to 2 bits per voxel into LDS once (unknown 0, occupied 1, free 3: 64 KiB at 64^3) and
-//        serves every candidate of the chunk;
-//     2. per candidate: 16 lanes build the camera matrices of the next 16 candidates (k_render_camera's arithmetic: fp64
-//        trig rounded to fp32, roll ignored); one ray per lane, sequential integer walk.  The walk does not start at the
-//        source: the range of steps i in [0, da] whose voxel lies in the grid comes from the closed form of the Bresenham
-//        minors, nb(i) = floor((2 db i + da) / (2 da)) (exact on the dominant axis, widened by one step on the minors and
-//        guarded by a bounds test in the loop), so a target 1 000 voxels away costs at most G steps;
-//     3. distinct counts from two visited bitmasks in LDS (all rays / stopped rays, 32 KiB each at 64^3): atomicOr returns
-//        the old word and the lane counts the bits it was first to set.  Only unknown voxels are marked.  A ray marks mask
-//        A on its way; a stopped ray walks again into mask B;
-//     4. wave reductions -> per-wave partials in LDS -> lane 0 sums them in wave order and stores the three integers.  No
-//        global atomics, every output is written once by one lane: deterministic;
+// This file holds what is the view gain's own: the grid packed to 2 bits per voxel, the two visited masks and who stores them,
+// the ray record of the slab path, the host front ends.  The walk (set-up, range of steps, step loop) is ray_walk.h's; lattice,
+// chunk and lane rules, camera batch, class lookup and first-to-set are view_kernels.h's; block sum and XCD decode common.h's.
+//
+//   k_view_gain   grids up to 64^3, workgroup (env, chunk of candidates):
+//     1. the env's grid is packed into LDS once (unknown 0, occupied 1, free 3: 64 KiB at 64^3) and serves the whole chunk;
+//     2. per candidate: the camera batch (plus c2w_out and the source voxel), then one ray per lane: make_walk / run_walk;
+//     3. distinct counts from two visited bitmasks in LDS (all rays / stopped rays, 32 KiB each at 64^3): mark_first on unknown
+//        voxels only.  A ray marks mask A on its way; a stopped ray walks again into mask B;
+//     4. block_sum, lane 0 stores the three integers.  No global atomics, one writer per output: deterministic;
 //     5. the workgroup clears both masks (16-byte stores) before the next candidate.
-//
-//   k_view_gain<true>   (gnbv_view_gain_masks) the same kernel, but the two visited masks are kept: after the barrier of step 4
-//     every lane copies 16-byte pieces of s_a / s_b to the candidate's rows of unknown_bits / hit_bits (lane i holds quad i:
-//     conflict-free 16-byte LDS reads, 1 KiB of consecutive addresses per wave store), zeroes the row's pad words and clears
-//     the LDS words it has just read -- store-and-clear replaces step 5 and also runs for the chunk's last candidate.  The
-//     workgroup owns its candidates' rows: no atomics.  k_view_gain<false> is the kernel gnbv_view_gain always launched.
+//   k_view_gain<true>   (gnbv_view_gain_masks) keeps the two masks: after step 4 every lane copies 16-byte pieces of s_a / s_b to
+//     the candidate's rows of unknown_bits / hit_bits (lane i holds quad i: conflict-free 16-byte LDS reads, 1 KiB of consecutive
+//     addresses per wave store), zeroes the row's pad words and clears the LDS words it has just read -- store-and-clear replaces
+//     step 5 and also runs for the chunk's last candidate.  The workgroup owns its candidates' rows: no atomics.
 //
 //   k_vg_prep, k_vg_fate, k_vg_slab   the same integers for grids up to 128^3 (gnbv_view_gain_slab), and in their <true> forms
 //     the same two masks (gnbv_view_gain_slab_masks): further down.
@@ -35,29 +30,30 @@
 
 #include "common.h"
 #include "backproject.h"
-#include "raytrace.h"  // camera_of_pose: k_render_camera's arithmetic (fp64 trig rounded to fp32, roll ignored)
-#include "ray_walk.h"  // axis_to_idx, floor_div, minor_range, make_walk, run_walk: shared with frontview.hip
+#include "ray_walk.h"
+#include "view_kernels.h"
 #include "../../include/gennbv_hip.h"
 
 namespace {
 
-constexpr int kMaxThreads = 1024;
 constexpr int kMaxGrid = 64;          // LDS: G^3 / 4 (grid) + 2 * G^3 / 8 (masks) bytes = 128 KiB at 64^3
 constexpr int kMaxSlabGrid = 128;     // gnbv_view_gain_slab (the ray word keeps x in 8 bits, the step count in 8)
-constexpr int kCamBatch = 16;         // camera matrices built at a time
 
-struct VgParams {
-    int n, k, g, chunk, chunks;
+struct VgBase {  // what every kernel here takes; vg_fill fills it from GnbvViewGain
+    int k, g, chunk, chunks;
     const int8_t *tri;
     int64_t tri_row_stride;
     int tri_aligned;
     const float *poses, *range_gt, *voxel_size;
     Intrinsics kinv;
-    int h, w, stride, nu, nrays;
+    int stride, nu, nrays;
     float range;
     int32_t *gain;
     float *c2w_out;
     int grid_words, mask_words, ablate;
+};
+
+struct VgParams : VgBase {
     // k_view_gain<true> only
     uint32_t *unknown_bits, *hit_bits;  // [n, k, words] rows, 16-byte aligned, either may be NULL
     int words;                          // a multiple of 4, >= mask_words
@@ -91,13 +87,43 @@ __device__ __forceinline__ uint32_t pack_word(const int8_t *row, int w, int g3, 
     return code;
 }
 
+struct VgFrame {  // env e's voxel frame as axis_to_idx takes it
+    float rmin[3], v[3];
+};
+
+__device__ __forceinline__ VgFrame vg_frame(const VgBase &p, int e)
+{
+    return {{p.range_gt[e * 6 + 1], p.range_gt[e * 6 + 3], p.range_gt[e * 6 + 5]},
+            {p.voxel_size[e * 3 + 0], p.voxel_size[e * 3 + 1], p.voxel_size[e * 3 + 2]}};
+}
+
+__device__ __forceinline__ void voxel_of(const float *pt, const VgFrame &f, int *ix)
+{
+#pragma unroll
+    for (int a = 0; a < 3; ++a) ix[a] = axis_to_idx(pt[a], f.rmin[a], f.v[a]);
+}
+
+// the end voxel of lattice ray r from the camera M
+__device__ __forceinline__ void ray_target(const VgBase &p, const float *M, const VgFrame &f, int r, int *ix)
+{
+    const int iv = r / p.nu, u = lattice_pixel(r - iv * p.nu, p.stride), v = lattice_pixel(iv, p.stride);
+    float wp[3];
+    pixel_to_world(p.range, (float)u, (float)v, p.kinv, M, wp);
+    voxel_of(wp, f, ix);
+}
+
+__device__ __forceinline__ void clear_quads(uint4 *s, int quads)
+{
+    for (int w = threadIdx.x; w < quads; w += blockDim.x) s[w] = make_uint4(0u, 0u, 0u, 0u);
+}
+
 template <bool MASKS>
-__global__ __launch_bounds__(kMaxThreads) void k_view_gain(VgParams p)
+__global__ __launch_bounds__(kViewMaxThreads) void k_view_gain(VgParams p)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t s_mem[];
     __shared__ float s_cam[kCamBatch][16];
     __shared__ int s_src[kCamBatch][3];
-    __shared__ int s_part[kMaxThreads / kWave][3];
+    __shared__ int s_part[kViewMaxThreads / kWave][3];
 
     const int tid = threadIdx.x, nthreads = blockDim.x;
     const int e = blockIdx.x / p.chunks, ch = blockIdx.x - e * p.chunks;
@@ -109,100 +135,62 @@ __global__ __launch_bounds__(kMaxThreads) void k_view_gain(VgParams p)
     const int8_t *row = p.tri + (size_t)e * p.tri_row_stride;
     for (int w = tid; w < p.grid_words; w += nthreads) s_grid[w] = pack_word(row, w, g3, p.tri_aligned);
     uint4 *s_masks4 = reinterpret_cast<uint4 *>(s_a);
-    const int mask_quads = p.mask_words / 2;  // both masks, 4 words at a time (mask_words is a multiple of 4)
-    for (int w = tid; w < mask_quads; w += nthreads) s_masks4[w] = make_uint4(0u, 0u, 0u, 0u);
+    const int row_quads = p.mask_words / 4;  // of one mask (mask_words is a multiple of 4)
+    clear_quads(s_masks4, 2 * row_quads);
 
-    const float rmin_x = p.range_gt[e * 6 + 1], rmin_y = p.range_gt[e * 6 + 3], rmin_z = p.range_gt[e * 6 + 5];
-    const float vx = p.voxel_size[e * 3 + 0], vy = p.voxel_size[e * 3 + 1], vz = p.voxel_size[e * 3 + 2];
+    const VgFrame f = vg_frame(p, e);
     const bool mark = (p.ablate & 1) == 0, second = (p.ablate & 2) == 0;
 
     for (int j = j0; j < j1; ++j) {
-        const int slot = (j - j0) % kCamBatch;
-        if (slot == 0) {
-            // ---- 2a. cameras of the next kCamBatch candidates (k_render_camera's arithmetic; -ffp-contract=off)
-            if (tid < kCamBatch && j + tid < j1) {
-                const float *q = p.poses + ((size_t)e * p.k + j + tid) * 6;
-                float *m = s_cam[tid];
-                camera_of_pose(q, m);
-                if (p.c2w_out != nullptr) {
-                    float *o = p.c2w_out + ((size_t)e * p.k + j + tid) * 16;
+        // ---- 2a. the camera batch, with c2w_out and the source voxel
+        const int slot = camera_batch(s_cam, p.poses + (size_t)e * p.k * 6, j0, j, j1, [&](int t, int jt, const float *q, const float *m) {
+            if (p.c2w_out != nullptr) {
+                float *o = p.c2w_out + ((size_t)e * p.k + jt) * 16;
 #pragma unroll
-                    for (int i = 0; i < 16; ++i) o[i] = m[i];
-                }
-                s_src[tid][0] = axis_to_idx(q[0], rmin_x, vx);
-                s_src[tid][1] = axis_to_idx(q[1], rmin_y, vy);
-                s_src[tid][2] = axis_to_idx(q[2], rmin_z, vz);
+                for (int i = 0; i < 16; ++i) o[i] = m[i];
             }
-        }
+            voxel_of(q, f, s_src[t]);
+        });
         __syncthreads();  // cameras ready; masks clear
 
         // ---- 2b / 3. one ray per lane
-        const float *M = s_cam[slot];
         const int x0 = s_src[slot][0], y0 = s_src[slot][1], z0 = s_src[slot][2];
-        int n_unknown = 0, n_unknown_hit = 0, n_blocked = 0;
+        int cnt[3] = {0, 0, 0};  // unknown voxels, those of the stopped rays, stopped rays
         for (int r = tid; r < p.nrays; r += nthreads) {
-            const int iv = r / p.nu, iu = r - iv * p.nu;
-            const int u = p.stride / 2 + iu * p.stride, v = p.stride / 2 + iv * p.stride;
-            float wp[3];
-            pixel_to_world(p.range, (float)u, (float)v, p.kinv, M, wp);
-            const int x1 = axis_to_idx(wp[0], rmin_x, vx), y1 = axis_to_idx(wp[1], rmin_y, vy), z1 = axis_to_idx(wp[2], rmin_z, vz);
-            const RayWalk rw = make_walk(x0, y0, z0, x1, y1, z1, g);
+            int t[3];
+            ray_target(p, s_cam[slot], f, r, t);
+            const RayWalk rw = make_walk(x0, y0, z0, t[0], t[1], t[2], g);
             if (rw.n == 0) continue;
-            const bool blocked = run_walk(rw, g, [&](int lin, int) {
-                const uint32_t cls = (s_grid[lin >> 4] >> ((lin & 15) * 2)) & 3u;
-                if (cls == 1u) return true;
-                if (cls == 0u && mark) {
-                    const uint32_t bit = 1u << (lin & 31);
-                    n_unknown += (atomicOr(&s_a[lin >> 5], bit) & bit) == 0u;
-                }
-                return false;
-            });
-            if (blocked) {
-                ++n_blocked;
-                if (mark && second)
-                    run_walk(rw, g, [&](int lin, int) {
-                        const uint32_t cls = (s_grid[lin >> 4] >> ((lin & 15) * 2)) & 3u;
-                        if (cls == 1u) return true;
-                        if (cls == 0u) {
-                            const uint32_t bit = 1u << (lin & 31);
-                            n_unknown_hit += (atomicOr(&s_b[lin >> 5], bit) & bit) == 0u;
-                        }
-                        return false;
-                    });
+            auto walk_into = [&](uint32_t *mask, int &count, bool marking) {
+                return run_walk(rw, g, [&](int lin, int) {
+                    const uint32_t cls = grid_class(s_grid, lin);
+                    if (cls == 1u) return true;
+                    if (cls == 0u && marking) count += mark_first(mask, lin);
+                    return false;
+                });
+            };
+            if (walk_into(s_a, cnt[0], mark)) {
+                ++cnt[2];
+                if (mark && second) walk_into(s_b, cnt[1], true);
             }
         }
 
-        // ---- 4. the three sums, in wave order
-        n_unknown = wave_reduce_sum(n_unknown);
-        n_unknown_hit = wave_reduce_sum(n_unknown_hit);
-        n_blocked = wave_reduce_sum(n_blocked);
-        if ((tid & (kWave - 1)) == 0) {
-            s_part[tid / kWave][0] = n_unknown;
-            s_part[tid / kWave][1] = n_unknown_hit;
-            s_part[tid / kWave][2] = n_blocked;
-        }
-        __syncthreads();  // every ray of candidate j is done: partials complete, masks and camera slot free
+        // ---- 4. the three sums.  block_sum's barrier: every ray of candidate j is done, masks and camera slot free
+        block_sum(cnt, s_part);
         if (tid == 0) {
-            int a = 0, b = 0, c = 0;
-            for (int w = 0; w < nthreads / kWave; ++w) {
-                a += s_part[w][0];
-                b += s_part[w][1];
-                c += s_part[w][2];
-            }
             int32_t *o = p.gain + ((size_t)e * p.k + j) * 3;
-            o[0] = a; o[1] = b; o[2] = c;
+            o[0] = cnt[0]; o[1] = cnt[1]; o[2] = cnt[2];
         }
-        // ---- 5. clear the masks for the next candidate (ordered in front of its rays by the barrier at the loop's head;
-        //         lane 0 reads s_part before it arrives there, the waves write it after)
+        // ---- 5. clear the masks for the next candidate (ordered in front of its rays by the barrier at the loop's head, which
+        //         also is the barrier block_sum leaves to its caller)
         if constexpr (MASKS) {
             // store, then clear: a lane clears the quads it stored, so no barrier between the two.  Every word of the row is
             // written: mask_words from LDS (the bits at and past g^3 were never set), zeros from there to `words`.
             const size_t off = ((size_t)e * p.k + j) * (size_t)p.words;
             uint4 *ga = p.unknown_bits != nullptr ? reinterpret_cast<uint4 *>(p.unknown_bits + off) : nullptr;
             uint4 *gb = p.hit_bits != nullptr ? reinterpret_cast<uint4 *>(p.hit_bits + off) : nullptr;
-            const int row_quads = p.mask_words / 4, all_quads = p.words / 4;
             const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
-            for (int w = tid; w < all_quads; w += nthreads) {
+            for (int w = tid; w < p.words / 4; w += nthreads) {
                 if (w < row_quads) {
                     if (ga != nullptr) ga[w] = s_masks4[w];
                     if (gb != nullptr) gb[w] = s_masks4[row_quads + w];
@@ -214,8 +202,7 @@ __global__ __launch_bounds__(kMaxThreads) void k_view_gain(VgParams p)
                 }
             }
         } else {
-            if (j + 1 < j1 && mark)
-                for (int w = tid; w < mask_quads; w += nthreads) s_masks4[w] = make_uint4(0u, 0u, 0u, 0u);
+            if (j + 1 < j1 && mark) clear_quads(s_masks4, 2 * row_quads);
         }
     }
 }
@@ -233,15 +220,13 @@ __global__ __launch_bounds__(kMaxThreads) void k_view_gain(VgParams p)
 //               `blocked` is complete after this pass (one atomicAdd per workgroup);
 //   k_vg_slab   workgroup (env, chunk of candidates, slab [X0, X1)): the slab's part of the packed grid and of both visited
 //               masks in LDS ((X1 - X0) G^2 / 2 bytes).  A ray whose marked x-extent misses the slab is rejected on its
-//               4-byte word alone.  Otherwise its steps are cut to the slab: exactly if x is the dominant axis, by the
-//               closed form of the minors (minor_range with [X0, X1 - 1]) if not, one step wide on both sides and guarded by
-//               a test of the slab-local index in the loop (y and z need none: every recorded step is in the grid).  The ray
-//               walks once: mask A, and mask B too if it is blocked.  Distinct counts as in k_view_gain; the slabs
-//               partition the voxels by x, so a candidate's counts are the sums over its slabs: int32 atomicAdd, one per
-//               workgroup, candidate and count -- integer sums, the same bits in any order.
+//               4-byte word alone.  Otherwise its recorded steps are cut to the slab (ray_walk.h make_slab_cut) and walked
+//               once with a test of the slab-local index: mask A, and mask B too if it is blocked.  Distinct counts as in
+//               k_view_gain; the slabs partition the voxels by x, so a candidate's counts are the sums over its slabs: int32
+//               atomicAdd, one per workgroup, candidate and count -- integer sums, the same bits in any order.
 //
-// tests/test_view_gain_slab_cpu.py holds a Python model of the record and of the slab cut, checked against the oracle's
-// Bresenham.
+// tests/test_ray_walk_host_cpu.py runs the record and the slab cut of ray_walk.h itself on the CPU against the oracle's
+// Bresenham; tests/test_view_gain_slab_cpu.py holds a Python model of both (and of the 32-bit bound).
 //
 // gnbv_view_gain_slab_masks launches k_vg_prep<true> and k_vg_slab<true>, which also keep the two masks (k_vg_fate is shared).
 // A candidate's row is cut by x-planes like its voxels: slab [X0, X1) holds the row's bits [X0 G^2, X1 G^2), which start and
@@ -250,14 +235,15 @@ __global__ __launch_bounds__(kMaxThreads) void k_view_gain(VgParams p)
 //     (X0 G^2 >> 7) + q -- a 16-byte LDS read and an aligned 16-byte global store, no funnel shift.  Cost: at most 16 bytes per
 //     mask, and none where G^2 s is a multiple of 128 (any s at G % 16 == 0, even s at G % 8 == 0).  s_grid and the counts
 //     do not see sh.
-//   - After the barrier "every ray of candidate j is done" a lane stores the quads it then clears (store-and-clear replaces the
-//     clear pass and also runs for the chunk's last candidate).  A quad that lies whole inside the slab's bits (the last slab
-//     owns the row up to its last quad: bits at and past G^3 are never set) is one 16-byte store.  In the at most two quads at
-//     the slab's ragged ends a word inside the slab's bits is a 4-byte store, a word of another slab is left alone, and a word
-//     the slab SHARES with a neighbour gets the slab's part by a global atomicOr.  The parts are disjoint bit sets and
-//     k_vg_prep<true> has zeroed the shared words (and the pad words from ceil(G^3 / 32) to `words`) earlier on the stream, so
-//     the word does not depend on the order.  Every other word of a row has one writer.  G^2 >= 32 bits per plane from G = 6
-//     on, so a word is then shared by two slabs at most (at G = 3, s = 1 by three; the rule is the same).
+//   - After block_sum's barrier a lane stores the quads it then clears (store-and-clear replaces the clear pass and also runs
+//     for the chunk's last candidate).  A quad that lies whole inside the slab's bits (the last slab owns the row up to its last
+//     quad: bits at and past G^3 are never set) is one 16-byte store.  In the at most two quads at the slab's ragged ends a word
+//     inside the slab's bits is a 4-byte store, a word of another slab is left alone, and a word the slab SHARES with a neighbour
+//     gets the slab's part by a global atomicOr.  The parts are disjoint bit sets and k_vg_prep<true> has zeroed the shared words
+//     (and the pad words from ceil(G^3 / 32) to `words`) earlier on the stream, so the word does not depend on the order.  Every
+//     other word of a row has one writer.  G^2 >= 32 bits per plane from G = 6 on, so a word is then shared by two slabs at most
+//     (at G = 3, s = 1 by three; the rule is the same).  k_view_gain<true>'s store-and-clear is the case X0 = 0, X1 = G of this
+//     one and stays apart: written through one shared function that kernel needs 97 VGPRs, one wave per SIMD fewer.
 //   - With no ray (stride / 2 >= width or height) no slab kernel runs and k_vg_prep<true> zeroes the rows whole.
 // tests/test_gain_masks_slab_cpu.py holds a numpy model of this word-ownership rule.
 constexpr int kFateThreads = 256;
@@ -267,18 +253,8 @@ constexpr size_t kSlabLdsMax = 160 * 1024 - 256;   // a requested height is redu
 constexpr size_t kBatchBytes = (size_t)128 << 20;  // ray records of one batch of envs
 constexpr int kSlabWorkgroups = 2560;              // k_vg_slab workgroups per batch the default chunk aims at
 
-struct VsParams {
-    int k, g, chunk, chunks, slab, nslab;
-    const int8_t *tri;
-    int64_t tri_row_stride;
-    int tri_aligned;
-    const float *poses, *range_gt, *voxel_size;
-    Intrinsics kinv;
-    int stride, nu, nrays, rblocks;
-    float range;
-    int32_t *gain;
-    float *c2w_out;
-    int pack_words, grid_words, mask_words, ablate;
+struct VsParams : VgBase {
+    int slab, nslab, rblocks, pack_words;
     uint32_t *packed;  // [batch, pack_words]
     float *cams;       // [batch, k, kCamWords]
     int4 *rec;         // [batch, k, nrays]
@@ -337,124 +313,59 @@ __global__ __launch_bounds__(256) void k_vg_prep(VsArgs<MASKS> p, int e0, int ne
             for (int i = 0; i < 16; ++i) p.c2w_out[c * 16 + i] = m[i];
         }
         int *src = reinterpret_cast<int *>(o + 16);
-        src[0] = axis_to_idx(q[0], p.range_gt[e * 6 + 1], p.voxel_size[e * 3 + 0]);
-        src[1] = axis_to_idx(q[1], p.range_gt[e * 6 + 3], p.voxel_size[e * 3 + 1]);
-        src[2] = axis_to_idx(q[2], p.range_gt[e * 6 + 5], p.voxel_size[e * 3 + 2]);
+        voxel_of(q, vg_frame(p, e), src);
         src[3] = 0;
     }
 }
 
 __global__ __launch_bounds__(kFateThreads) void k_vg_fate(VsParams p, int e0, int ne)
 {
-    __shared__ int s_blocked[kFateThreads / kWave];
-    // XCD-aware block -> (env, candidate, ray block): all workgroups of an env run on one XCD (voxel.hip k_hit_mask)
-    const int b = blockIdx.x, xcd = b & 7, slot = b >> 3;
-    const int per_env = p.k * p.rblocks;
-    const int el = (slot / per_env) * 8 + xcd;
+    __shared__ int s_part[kFateThreads / kWave][1];
+    int rem;  // (candidate, ray block)
+    const int el = xcd_env(p.k * p.rblocks, rem);
     if (el >= ne) return;
-    const int rem = slot % per_env, j = rem / p.rblocks, rb = rem - j * p.rblocks;
+    const int j = rem / p.rblocks, rb = rem - j * p.rblocks;
     const int e = e0 + el, tid = threadIdx.x, g = p.g;
     const size_t cj = (size_t)el * p.k + j;
     const float *M = p.cams + cj * kCamWords;
     const int *src = reinterpret_cast<const int *>(M + 16);
-    const int x0 = src[0], y0 = src[1], z0 = src[2];
     const uint32_t *G = p.packed + (size_t)el * p.pack_words;
     const int r = rb * kFateThreads + tid;
-    int n_blocked = 0;
+    int cnt[1] = {0};  // stopped rays
     if (r < p.nrays) {
-        const float rmin_x = p.range_gt[e * 6 + 1], rmin_y = p.range_gt[e * 6 + 3], rmin_z = p.range_gt[e * 6 + 5];
-        const float vx = p.voxel_size[e * 3 + 0], vy = p.voxel_size[e * 3 + 1], vz = p.voxel_size[e * 3 + 2];
-        const int iv = r / p.nu, iu = r - iv * p.nu;
-        const int u = p.stride / 2 + iu * p.stride, v = p.stride / 2 + iv * p.stride;
-        float wp[3];
-        pixel_to_world(p.range, (float)u, (float)v, p.kinv, M, wp);
-        const int x1 = axis_to_idx(wp[0], rmin_x, vx), y1 = axis_to_idx(wp[1], rmin_y, vy), z1 = axis_to_idx(wp[2], rmin_z, vz);
-        const RayWalk rw = make_walk(x0, y0, z0, x1, y1, z1, g);
+        int t[3];
+        ray_target(p, M, vg_frame(p, e), r, t);
+        const RayWalk rw = make_walk(src[0], src[1], src[2], t[0], t[1], t[2], g);
         int first = 0, last = -1, lin_first = 0, lin_last = 0;
         bool blocked = false;
         if (rw.n > 0)
             blocked = run_walk(rw, g, [&](int lin, int i) {
-                if (((G[lin >> 4] >> ((lin & 15) * 2)) & 3u) == 1u) return true;
+                if (grid_class(G, lin) == 1u) return true;
                 if (last < 0) { first = i; lin_first = lin; }
                 last = i; lin_last = lin;
                 return false;
             });
-        n_blocked = blocked ? 1 : 0;
+        cnt[0] = blocked ? 1 : 0;
         const int count = last < 0 ? 0 : last - first + 1;  // <= g
         const int gg = g * g, xf = lin_first / gg, xl = lin_last / gg;
-        p.rec[cj * p.nrays + r] = make_int4(x1, y1, z1, rw.n > 0 ? rw.i0 + first : 0);
+        p.rec[cj * p.nrays + r] = make_int4(t[0], t[1], t[2], rw.n > 0 ? rw.i0 + first : 0);
         p.meta[cj * p.nrays + r] = (uint32_t)count | (blocked ? 256u : 0u) | ((uint32_t)min(xf, xl) << 16) | ((uint32_t)max(xf, xl) << 24);
     }
-    n_blocked = wave_reduce_sum(n_blocked);
-    if ((tid & (kWave - 1)) == 0) s_blocked[tid / kWave] = n_blocked;
-    __syncthreads();
-    if (tid == 0) {
-        int c = 0;
-        for (int w = 0; w < kFateThreads / kWave; ++w) c += s_blocked[w];
-        if (c != 0) atomicAdd(p.gain + ((size_t)e * p.k + j) * 3 + 2, c);
-    }
-}
-
-struct SlabWalk {  // the steps of one ray inside one slab
-    int n, lin;    // lin: index inside the slab, (x - X0) g^2 + y g + z
-    int p1, p2, two_da, two_db, two_dc, la, lb, lc;
-};
-
-// The recorded steps [first, first + count) of the ray (x0, y0, z0) -> (x1, y1, z1), cut to x in [X0, X1).  Axis order,
-// decision variables and the jump to the first step are make_walk's.  T = int for rays of fewer than 2^14 steps: a recorded
-// ray meets the grid, so |x0| <= da + g, the steps are <= da, and every product below stays under 2^30.
-template <typename T>
-__device__ __forceinline__ SlabWalk make_slab_walk(int x0, int y0, int z0, int x1, int y1, int z1, int g, int first, int count,
-                                                   int X0, int X1)
-{
-    SlabWalk r;
-    r.n = 0;
-    const int dx = abs(x1 - x0), dy = abs(y1 - y0), dz = abs(z1 - z0);
-    const int sx = x0 < x1 ? 1 : -1, sy = y0 < y1 ? 1 : -1, sz = z0 < z1 ? 1 : -1;
-    const int dm = max(max(dx, dy), dz);
-    int pa, pb, pc, da, db, dc, sa, sb, sc, sta, stb, stc;
-    const int gg = g * g;
-    if (dm == dx)      { pa = x0; pb = y0; pc = z0; da = dx; db = dy; dc = dz; sa = sx; sb = sy; sc = sz; sta = gg; stb = g; stc = 1; }
-    else if (dm == dy) { pa = y0; pb = x0; pc = z0; da = dy; db = dx; dc = dz; sa = sy; sb = sx; sc = sz; sta = g; stb = gg; stc = 1; }
-    else               { pa = z0; pb = x0; pc = y0; da = dz; db = dx; dc = dy; sa = sz; sb = sx; sc = sy; sta = 1; stb = gg; stc = g; }
-    T lo = first, hi = (T)first + count - 1;
-    if (dm == dx) {  // x dominant: x0 + sx i in [X0, X1 - 1], exact
-        lo = max(lo, sa > 0 ? (T)X0 - pa : (T)pa - (X1 - 1));
-        hi = min(hi, sa > 0 ? (T)(X1 - 1) - pa : (T)pa - X0);
-    } else {         // x is the first minor (da > 0 here)
-        minor_range<T>(pb, sb, db, da, X0, X1 - 1, lo, hi);
-    }
-    if (hi < lo) return r;
-    T nb = 0, nc = 0;
-    if (da > 0 && lo > 0) {
-        nb = floor_div((T)2 * db * lo + da, (T)2 * da);
-        nc = floor_div((T)2 * dc * lo + da, (T)2 * da);
-    }
-    r.n = (int)(hi - lo + 1);
-    pa += sa * (int)lo;
-    pb += sb * (int)nb;
-    pc += sc * (int)nc;
-    r.p1 = (int)((T)2 * db * (lo + 1) - da - (T)2 * da * nb);
-    r.p2 = (int)((T)2 * dc * (lo + 1) - da - (T)2 * da * nc);
-    r.lin = pa * sta + pb * stb + pc * stc - X0 * gg;
-    r.two_da = 2 * da; r.two_db = 2 * db; r.two_dc = 2 * dc;
-    r.la = sa * sta; r.lb = sb * stb; r.lc = sc * stc;
-    return r;
+    block_sum(cnt, s_part);
+    if (tid == 0 && cnt[0] != 0) atomicAdd(p.gain + ((size_t)e * p.k + j) * 3 + 2, cnt[0]);
 }
 
 template <bool MASKS>
-__global__ __launch_bounds__(kMaxThreads) void k_vg_slab(VsArgs<MASKS> p, int e0, int ne)
+__global__ __launch_bounds__(kViewMaxThreads) void k_vg_slab(VsArgs<MASKS> p, int e0, int ne)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t s_mem[];
-    __shared__ int s_part[kMaxThreads / kWave][2];
+    __shared__ int s_part[kViewMaxThreads / kWave][2];
 
     const int tid = threadIdx.x, nthreads = blockDim.x;
-    // XCD-aware block -> (env, chunk, slab): all workgroups of an env run on one XCD, as in k_vg_fate
-    const int b = blockIdx.x, xcd = b & 7, slot = b >> 3;
-    const int per_env = p.chunks * p.nslab;
-    const int el = (slot / per_env) * 8 + xcd;
+    int rem;  // (chunk, slab)
+    const int el = xcd_env(p.chunks * p.nslab, rem);
     if (el >= ne) return;
-    const int rem = slot % per_env, ch = rem / p.nslab, sl = rem - ch * p.nslab;
+    const int ch = rem / p.nslab, sl = rem - ch * p.nslab;
     const int e = e0 + el, g = p.g, gg = g * g;
     const int j0 = ch * p.chunk, j1 = min(p.k, j0 + p.chunk);
     const int X0 = sl * p.slab, X1 = min(g, X0 + p.slab);
@@ -470,8 +381,8 @@ __global__ __launch_bounds__(kMaxThreads) void k_vg_slab(VsArgs<MASKS> p, int e0
         s_grid[w] = sh != 0 ? (G[gw] >> sh) | (G[gw + 1] << (32 - sh)) : G[gw];
     }
     uint4 *s_masks4 = reinterpret_cast<uint4 *>(s_a);
-    const int mask_quads = p.mask_words / 2;
-    for (int w = tid; w < mask_quads; w += nthreads) s_masks4[w] = make_uint4(0u, 0u, 0u, 0u);
+    const int row_quads = p.mask_words / 4;
+    clear_quads(s_masks4, 2 * row_quads);
     const bool mark = (p.ablate & 1) == 0, second = (p.ablate & 2) == 0;
 
     for (int j = j0; j < j1; ++j) {
@@ -481,57 +392,34 @@ __global__ __launch_bounds__(kMaxThreads) void k_vg_slab(VsArgs<MASKS> p, int e0
         const int x0 = src[0], y0 = src[1], z0 = src[2];
         const uint32_t *meta = p.meta + cj * p.nrays;
         const int4 *rec = p.rec + cj * p.nrays;
-        int n_unknown = 0, n_unknown_hit = 0;
+        int cnt[2] = {0, 0};  // unknown voxels, those of the stopped rays
         for (int r = tid; r < p.nrays; r += nthreads) {
             const uint32_t m = meta[r];
             const int count = (int)(m & 255u), xa = (int)((m >> 16) & 255u), xb = (int)(m >> 24);
             if (count == 0 || xb < X0 || xa >= X1) continue;  // nothing to mark, or not in this slab
             const bool blocked = (m & 256u) != 0u && second;
             const int4 q = rec[r];
-            const int reach = max(max(abs(q.x - x0), abs(q.y - y0)), abs(q.z - z0));
-            SlabWalk w = reach < (1 << 14) ? make_slab_walk<int>(x0, y0, z0, q.x, q.y, q.z, g, q.w, count, X0, X1)
-                                           : make_slab_walk<long long>(x0, y0, z0, q.x, q.y, q.z, g, q.w, count, X0, X1);
-            for (int i = 0; i < w.n; ++i) {
-                if ((unsigned)w.lin < svox) {  // x inside the slab (y, z are inside the grid on every recorded step)
-                    const uint32_t cls = (s_grid[w.lin >> 4] >> ((w.lin & 15) * 2)) & 3u;
-                    if (cls == 0u && mark) {
-                        const int ml = w.lin + sh;
-                        const uint32_t bit = 1u << (ml & 31);
-                        n_unknown += (atomicOr(&s_a[ml >> 5], bit) & bit) == 0u;
-                        if (blocked) n_unknown_hit += (atomicOr(&s_b[ml >> 5], bit) & bit) == 0u;
-                    }
+            const RayWalk w = make_slab_cut(x0, y0, z0, q.x, q.y, q.z, g, q.w, count, X0, X1);
+            walk_steps(w, [svox](const RayWalk &s) { return (unsigned)s.lin < svox; }, [&](int lin, int) {
+                if (grid_class(s_grid, lin) == 0u && mark) {
+                    cnt[0] += mark_first(s_a, lin + sh);
+                    if (blocked) cnt[1] += mark_first(s_b, lin + sh);
                 }
-                if (w.p1 >= 0) { w.lin += w.lb; w.p1 -= w.two_da; }
-                if (w.p2 >= 0) { w.lin += w.lc; w.p2 -= w.two_da; }
-                w.lin += w.la;
-                w.p1 += w.two_db;
-                w.p2 += w.two_dc;
-            }
+                return false;
+            });
         }
-        n_unknown = wave_reduce_sum(n_unknown);
-        n_unknown_hit = wave_reduce_sum(n_unknown_hit);
-        if ((tid & (kWave - 1)) == 0) {
-            s_part[tid / kWave][0] = n_unknown;
-            s_part[tid / kWave][1] = n_unknown_hit;
-        }
-        __syncthreads();  // every ray of candidate j is done: partials complete, masks free
+        block_sum(cnt, s_part);  // its barrier: every ray of candidate j is done, masks free
         if (tid == 0) {
-            int a = 0, c = 0;
-            for (int w = 0; w < nthreads / kWave; ++w) {
-                a += s_part[w][0];
-                c += s_part[w][1];
-            }
             int32_t *o = p.gain + ((size_t)e * p.k + j) * 3;
-            if (a != 0) atomicAdd(o, a);
-            if (c != 0) atomicAdd(o + 1, c);
+            if (cnt[0] != 0) atomicAdd(o, cnt[0]);
+            if (cnt[1] != 0) atomicAdd(o + 1, cnt[1]);
         }
         // (ordered in front of the next candidate's rays by the barrier at the loop's head, as in k_view_gain)
         if constexpr (MASKS) {
             // store, then clear: a lane clears the quads it stored, so no barrier between the two.  The slab's bits are
             // [lo, hi) of the LDS masks; the last slab owns the row to the end of its last quad.
-            const int base = X0 * gg, row_quads = p.mask_words / 4;
             const int lo = sh, nq = (sh + (int)svox + 127) >> 7, hi = X1 == g ? nq * 128 : sh + (int)svox;
-            const size_t off = ((size_t)e * p.k + j) * (size_t)p.words + 4 * (size_t)(base >> 7);
+            const size_t off = ((size_t)e * p.k + j) * (size_t)p.words + 4 * (size_t)((X0 * gg) >> 7);
             uint32_t *ga = p.unknown_bits != nullptr ? p.unknown_bits + off : nullptr;
             uint32_t *gb = p.hit_bits != nullptr ? p.hit_bits + off : nullptr;
             const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
@@ -559,33 +447,30 @@ __global__ __launch_bounds__(kMaxThreads) void k_vg_slab(VsArgs<MASKS> p, int e0
                 s_masks4[row_quads + q] = zero;
             }
         } else {
-            if (j + 1 < j1 && mark)
-                for (int w = tid; w < mask_quads; w += nthreads) s_masks4[w] = make_uint4(0u, 0u, 0u, 0u);
+            if (j + 1 < j1 && mark) clear_quads(s_masks4, 2 * row_quads);
         }
     }
 }
 
 // what both host entry points of the slab path derive from the sizes
 struct VsPlan {
-    int nu, nrays, pack_words, batch;
+    ViewLattice lat;
+    int pack_words, batch;
     size_t off_cams, off_rec, off_meta, bytes;
 };
 
 inline bool vs_plan(int n, int k, int g, int h, int w, int stride, VsPlan &pl)
 {
     if (!(n > 0 && k > 0 && g >= 2 && g <= kMaxSlabGrid && h > 0 && w > 0 && stride >= 1 && h <= 32768 && w <= 32768)) return false;
-    const int half = stride / 2;
-    pl.nu = half < w ? (w - half + stride - 1) / stride : 0;
-    const int nv = half < h ? (h - half + stride - 1) / stride : 0;
-    pl.nrays = pl.nu * nv;
-    const int g3 = g * g * g;
+    pl.lat = view_lattice(h, w, stride);
+    const int g3 = g * g * g, nrays = pl.lat.nrays;
     pl.pack_words = (((g3 + 15) / 16) + 1 + 3) & ~3;  // + 1: k_vg_slab reads one word past an unaligned slab
     // envs per batch: the ray records of a batch stay near kBatchBytes, so that the slab pass finds them in the last-level cache
-    const size_t per_env = (size_t)k * (size_t)(pl.nrays > 0 ? pl.nrays : 1) * 20;
+    const size_t per_env = (size_t)k * (size_t)(nrays > 0 ? nrays : 1) * 20;
     size_t batch = kBatchBytes / per_env;
     batch = batch < 8 ? 8 : batch;
     pl.batch = batch > (size_t)n ? n : (int)batch;
-    const size_t bn = (size_t)pl.batch, rays = bn * k * pl.nrays;
+    const size_t bn = (size_t)pl.batch, rays = bn * k * nrays;
     pl.off_cams = align256(bn * pl.pack_words * sizeof(uint32_t));
     pl.off_rec = align256(pl.off_cams + bn * k * kCamWords * sizeof(float));
     pl.off_meta = align256(pl.off_rec + rays * sizeof(int4));
@@ -602,9 +487,7 @@ inline size_t slab_lds_bytes(int g, int s, int &grid_words, int &mask_words, boo
     return (size_t)(grid_words + 2 * mask_words) * sizeof(uint32_t);
 }
 
-}  // namespace
-
-static bool view_gain_args_ok(const GnbvViewGain &a, int max_grid)
+bool view_gain_args_ok(const GnbvViewGain &a, int max_grid)
 {
     return a.n > 0 && a.k > 0 && a.g >= 2 && a.g <= max_grid && a.h > 0 && a.w > 0 && a.stride >= 1 && a.h <= 32768 && a.w <= 32768 &&
            std::isfinite(a.range) && a.range > 0.0f && a.chunk >= 0 && a.ablate >= 0 && a.ablate <= 3 && a.tri_i8 != nullptr &&
@@ -612,63 +495,117 @@ static bool view_gain_args_ok(const GnbvViewGain &a, int max_grid)
            a.tri_row_stride >= (int64_t)a.g * a.g * a.g;
 }
 
-// gnbv_view_gain (MASKS false: the mask arguments are not looked at) and gnbv_view_gain_masks
-template <bool MASKS>
-static int view_gain_impl(const GnbvViewGain *args, int words, int32_t *unknown_bits, int32_t *hit_bits, void *stream)
+// the mask arguments of gnbv_view_gain_masks and gnbv_view_gain_slab_masks
+bool mask_args_ok(const GnbvViewGain &a, int words, const int32_t *unknown_bits, const int32_t *hit_bits)
 {
-    GNBV_CHECK_ARG(args != nullptr);
-    const GnbvViewGain a = *args;
-    GNBV_CHECK_ARG(view_gain_args_ok(a, kMaxGrid));
-    const int g3 = a.g * a.g * a.g;
-    if (MASKS) {
-        GNBV_CHECK_ARG(a.ablate == 0 && (unknown_bits != nullptr || hit_bits != nullptr));
-        GNBV_CHECK_ARG(words > 0 && (words & 3) == 0 && words >= (g3 + 31) / 32);
-        GNBV_CHECK_ARG((((uintptr_t)unknown_bits | (uintptr_t)hit_bits) & 15) == 0);
-        GNBV_CHECK_ARG((int64_t)a.n * a.k * words <= 0x7fffffff);
-    }
-    VgParams p;
-    p.n = a.n; p.k = a.k; p.g = a.g;
-    // candidates per workgroup: enough workgroups for two per compute unit, but the grid is packed once per workgroup
-    int chunk = a.chunk;
-    if (chunk == 0) {
-        const int want = (512 + a.n - 1) / a.n;  // chunks per env
-        chunk = (a.k + want - 1) / want;
-    }
-    chunk = chunk < 1 ? 1 : (chunk > a.k ? a.k : chunk);
+    return a.ablate == 0 && (unknown_bits != nullptr || hit_bits != nullptr) && words > 0 && (words & 3) == 0 &&
+           words >= (a.g * a.g * a.g + 31) / 32 && (((uintptr_t)unknown_bits | (uintptr_t)hit_bits) & 15) == 0 &&
+           (int64_t)a.n * a.k * words <= 0x7fffffff;
+}
+
+// the common parameters, but grid_words / mask_words (the LDS layout is the caller's)
+void vg_fill(VgBase &p, const GnbvViewGain &a, const ViewLattice &lat, int chunk)
+{
+    p.k = a.k; p.g = a.g;
     p.chunk = chunk;
     p.chunks = (a.k + chunk - 1) / chunk;
-    GNBV_CHECK_ARG((int64_t)a.n * p.chunks <= 0x7fffffff);
     p.tri = a.tri_i8;
     p.tri_row_stride = a.tri_row_stride;
     p.tri_aligned = (((uintptr_t)a.tri_i8 | (uintptr_t)a.tri_row_stride) & 15) == 0;
     p.poses = a.poses; p.range_gt = a.range_gt; p.voxel_size = a.voxel_size;
     for (int i = 0; i < 9; ++i) p.kinv.k[i] = a.inv_intri[i];
-    p.h = a.h; p.w = a.w; p.stride = a.stride;
-    const int half = a.stride / 2;
-    p.nu = half < a.w ? (a.w - half + a.stride - 1) / a.stride : 0;
-    const int nv = half < a.h ? (a.h - half + a.stride - 1) / a.stride : 0;
-    p.nrays = p.nu * nv;
+    p.stride = a.stride; p.nu = lat.nu; p.nrays = lat.nrays;
     p.range = a.range;
     p.gain = a.gain;
     p.c2w_out = a.c2w_out;
+    p.ablate = a.ablate;
+}
+
+// gnbv_view_gain (MASKS false: the mask arguments are not looked at) and gnbv_view_gain_masks
+template <bool MASKS>
+int view_gain_impl(const GnbvViewGain *args, int words, int32_t *unknown_bits, int32_t *hit_bits, void *stream)
+{
+    GNBV_CHECK_ARG(args != nullptr);
+    const GnbvViewGain a = *args;
+    GNBV_CHECK_ARG(view_gain_args_ok(a, kMaxGrid));
+    if (MASKS) GNBV_CHECK_ARG(mask_args_ok(a, words, unknown_bits, hit_bits));
+    VgParams p;
+    // candidates per workgroup: enough workgroups for two per compute unit, but the grid is packed once per workgroup
+    vg_fill(p, a, view_lattice(a.h, a.w, a.stride), view_chunk(a.chunk, a.k, 512, a.n));
+    GNBV_CHECK_ARG((int64_t)a.n * p.chunks <= 0x7fffffff);
+    const int g3 = a.g * a.g * a.g;
     p.grid_words = (((g3 + 15) / 16) + 3) & ~3;
     p.mask_words = (((g3 + 31) / 32) + 3) & ~3;
-    p.ablate = a.ablate;
     p.unknown_bits = MASKS ? reinterpret_cast<uint32_t *>(unknown_bits) : nullptr;
     p.hit_bits = MASKS ? reinterpret_cast<uint32_t *>(hit_bits) : nullptr;
     p.words = MASKS ? words : 0;
     const size_t lds = (size_t)(p.grid_words + 2 * p.mask_words) * sizeof(uint32_t);
-    // one ray per lane; a workgroup whose LDS leaves room for several per compute unit stays at 256 lanes
-    int threads = ((p.nrays > 0 ? p.nrays : 1) + kWave - 1) / kWave * kWave;
-    const int cap = lds > 32 * 1024 ? kMaxThreads : 256;
-    threads = threads > cap ? cap : threads;
-    // (per call: the attribute belongs to the current device's copy of the kernel)
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute((const void *)k_view_gain<MASKS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return (int)hipGetLastError();
-    hipLaunchKernelGGL(k_view_gain<MASKS>, dim3((unsigned)(a.n * p.chunks)), dim3(threads), lds, gnbv_stream(stream), p);
+    if (!view_raise_lds(k_view_gain<MASKS>, lds)) return (int)hipGetLastError();
+    hipLaunchKernelGGL(k_view_gain<MASKS>, dim3((unsigned)(a.n * p.chunks)), dim3(view_threads(p.nrays, lds)), lds, gnbv_stream(stream), p);
     return gnbv_launch_status();
 }
+
+// gnbv_view_gain_slab (MASKS false: the mask arguments are not looked at) and gnbv_view_gain_slab_masks
+template <bool MASKS>
+int view_gain_slab_impl(const GnbvViewGain *args, int slab, void *workspace, size_t workspace_bytes, int words,
+                        int32_t *unknown_bits, int32_t *hit_bits, void *stream)
+{
+    GNBV_CHECK_ARG(args != nullptr);
+    const GnbvViewGain a = *args;
+    GNBV_CHECK_ARG(view_gain_args_ok(a, kMaxSlabGrid) && slab >= 0);
+    VsPlan pl;
+    GNBV_CHECK_ARG(vs_plan(a.n, a.k, a.g, a.h, a.w, a.stride, pl));
+    GNBV_CHECK_ARG(workspace != nullptr && workspace_bytes >= pl.bytes && ((uintptr_t)workspace & 15) == 0);
+    if (MASKS) GNBV_CHECK_ARG(mask_args_ok(a, words, unknown_bits, hit_bits));
+    VsArgs<MASKS> p;
+    // slab height: the fewest slabs whose grid + masks fit the LDS budget, of equal height; a requested height is kept if it fits
+    int s = slab > a.g ? a.g : slab;
+    if (s == 0) {
+        int ns = 1;
+        while (slab_lds_bytes(a.g, (a.g + ns - 1) / ns, p.grid_words, p.mask_words, MASKS) > kSlabLdsBudget) ++ns;
+        s = (a.g + ns - 1) / ns;
+    }
+    while (slab_lds_bytes(a.g, s, p.grid_words, p.mask_words, MASKS) > kSlabLdsMax) --s;  // s = 1: 2 * 8 KiB at 128^3
+    const size_t lds = slab_lds_bytes(a.g, s, p.grid_words, p.mask_words, MASKS);
+    p.slab = s;
+    p.nslab = (a.g + s - 1) / s;
+    const int batch_pad = (pl.batch + 7) / 8 * 8;  // the XCD-aware grids are whole multiples of 8 envs
+    // ten workgroups per compute unit even out the slabs' unequal shares of the rays (512 envs x 128^3, K = 32: 24.5 / 23.2 /
+    // 22.8 ms at 16 / 8 / 4 candidates per workgroup; the slab's grid is re-read per workgroup)
+    vg_fill(p, a, pl.lat, view_chunk(a.chunk, a.k, kSlabWorkgroups, pl.batch * p.nslab));
+    p.rblocks = (p.nrays + kFateThreads - 1) / kFateThreads;
+    GNBV_CHECK_ARG((int64_t)batch_pad * p.chunks * p.nslab <= 0x7fffffff && (int64_t)batch_pad * a.k * p.rblocks <= 0x7fffffff);
+    p.pack_words = pl.pack_words;
+    char *ws = static_cast<char *>(workspace);
+    p.packed = reinterpret_cast<uint32_t *>(ws);
+    p.cams = reinterpret_cast<float *>(ws + pl.off_cams);
+    p.rec = reinterpret_cast<int4 *>(ws + pl.off_rec);
+    p.meta = reinterpret_cast<uint32_t *>(ws + pl.off_meta);
+    if constexpr (MASKS) {
+        p.unknown_bits = reinterpret_cast<uint32_t *>(unknown_bits);
+        p.hit_bits = reinterpret_cast<uint32_t *>(hit_bits);
+        p.words = words;
+        p.zero_all = p.nrays == 0;
+        p.zero_words = p.zero_all ? words : p.nslab - 1 + (words - (a.g * a.g * a.g + 31) / 32);
+    }
+    const int threads = view_threads(p.nrays, lds);
+    hipStream_t st = gnbv_stream(stream);
+    if (!view_raise_lds(k_vg_slab<MASKS>, lds)) return (int)hipGetLastError();
+    for (int e0 = 0; e0 < a.n; e0 += pl.batch) {  // the workspace is reused: the stream orders the batches
+        const int ne = a.n - e0 < pl.batch ? a.n - e0 : pl.batch, ne_pad = (ne + 7) / 8 * 8;
+        int64_t items = (int64_t)ne * pl.pack_words;
+        if ((int64_t)ne * a.k * 3 > items) items = (int64_t)ne * a.k * 3;
+        if constexpr (MASKS)
+            if ((int64_t)ne * a.k * p.zero_words > items) items = (int64_t)ne * a.k * p.zero_words;
+        hipLaunchKernelGGL(k_vg_prep<MASKS>, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, p, e0, ne);
+        if (p.nrays == 0) continue;
+        hipLaunchKernelGGL(k_vg_fate, dim3((unsigned)(ne_pad * a.k * p.rblocks)), dim3(kFateThreads), 0, st, p, e0, ne);
+        hipLaunchKernelGGL(k_vg_slab<MASKS>, dim3((unsigned)(ne_pad * p.chunks * p.nslab)), dim3(threads), lds, st, p, e0, ne);
+    }
+    return gnbv_launch_status();
+}
+
+}  // namespace
 
 GNBV_API int gnbv_view_gain(const GnbvViewGain *args, void *stream)
 {
@@ -684,93 +621,6 @@ GNBV_API size_t gnbv_view_gain_slab_workspace_bytes(int n, int k, int g, int h, 
 {
     VsPlan pl;
     return vs_plan(n, k, g, h, w, stride, pl) ? pl.bytes : 0;
-}
-
-// gnbv_view_gain_slab (MASKS false: the mask arguments are not looked at) and gnbv_view_gain_slab_masks
-template <bool MASKS>
-static int view_gain_slab_impl(const GnbvViewGain *args, int slab, void *workspace, size_t workspace_bytes, int words,
-                               int32_t *unknown_bits, int32_t *hit_bits, void *stream)
-{
-    GNBV_CHECK_ARG(args != nullptr);
-    const GnbvViewGain a = *args;
-    GNBV_CHECK_ARG(view_gain_args_ok(a, kMaxSlabGrid) && slab >= 0);
-    VsPlan pl;
-    GNBV_CHECK_ARG(vs_plan(a.n, a.k, a.g, a.h, a.w, a.stride, pl));
-    GNBV_CHECK_ARG(workspace != nullptr && workspace_bytes >= pl.bytes && ((uintptr_t)workspace & 15) == 0);
-    const int row_words = (a.g * a.g * a.g + 31) / 32;
-    if (MASKS) {
-        GNBV_CHECK_ARG(a.ablate == 0 && (unknown_bits != nullptr || hit_bits != nullptr));
-        GNBV_CHECK_ARG(words > 0 && (words & 3) == 0 && words >= row_words);
-        GNBV_CHECK_ARG((((uintptr_t)unknown_bits | (uintptr_t)hit_bits) & 15) == 0);
-        GNBV_CHECK_ARG((int64_t)a.n * a.k * words <= 0x7fffffff);
-    }
-    VsArgs<MASKS> p;
-    p.k = a.k; p.g = a.g;
-    // slab height: the fewest slabs whose grid + masks fit the LDS budget, of equal height; a requested height is kept if it fits
-    int s = slab > a.g ? a.g : slab;
-    if (s == 0) {
-        int ns = 1;
-        while (slab_lds_bytes(a.g, (a.g + ns - 1) / ns, p.grid_words, p.mask_words, MASKS) > kSlabLdsBudget) ++ns;
-        s = (a.g + ns - 1) / ns;
-    }
-    while (slab_lds_bytes(a.g, s, p.grid_words, p.mask_words, MASKS) > kSlabLdsMax) --s;  // s = 1: 2 * 8 KiB at 128^3
-    const size_t lds = slab_lds_bytes(a.g, s, p.grid_words, p.mask_words, MASKS);
-    p.slab = s;
-    p.nslab = (a.g + s - 1) / s;
-    const int batch_pad = (pl.batch + 7) / 8 * 8;  // the XCD-aware grids are whole multiples of 8 envs
-    int chunk = a.chunk;
-    if (chunk == 0) {  // ten workgroups per compute unit even out the slabs' unequal shares of the rays (512 envs x 128^3, K = 32:
-                       // 24.5 / 23.2 / 22.8 ms at 16 / 8 / 4 candidates per workgroup; the slab's grid is re-read per workgroup)
-        const int want = (kSlabWorkgroups + pl.batch * p.nslab - 1) / (pl.batch * p.nslab);
-        chunk = (a.k + want - 1) / want;
-    }
-    chunk = chunk < 1 ? 1 : (chunk > a.k ? a.k : chunk);
-    p.chunk = chunk;
-    p.chunks = (a.k + chunk - 1) / chunk;
-    p.rblocks = (pl.nrays + kFateThreads - 1) / kFateThreads;
-    GNBV_CHECK_ARG((int64_t)batch_pad * p.chunks * p.nslab <= 0x7fffffff && (int64_t)batch_pad * a.k * p.rblocks <= 0x7fffffff);
-    p.tri = a.tri_i8;
-    p.tri_row_stride = a.tri_row_stride;
-    p.tri_aligned = (((uintptr_t)a.tri_i8 | (uintptr_t)a.tri_row_stride) & 15) == 0;
-    p.poses = a.poses; p.range_gt = a.range_gt; p.voxel_size = a.voxel_size;
-    for (int i = 0; i < 9; ++i) p.kinv.k[i] = a.inv_intri[i];
-    p.stride = a.stride; p.nu = pl.nu; p.nrays = pl.nrays;
-    p.range = a.range;
-    p.gain = a.gain;
-    p.c2w_out = a.c2w_out;
-    p.pack_words = pl.pack_words;
-    p.ablate = a.ablate;
-    char *ws = static_cast<char *>(workspace);
-    p.packed = reinterpret_cast<uint32_t *>(ws);
-    p.cams = reinterpret_cast<float *>(ws + pl.off_cams);
-    p.rec = reinterpret_cast<int4 *>(ws + pl.off_rec);
-    p.meta = reinterpret_cast<uint32_t *>(ws + pl.off_meta);
-    if constexpr (MASKS) {
-        p.unknown_bits = reinterpret_cast<uint32_t *>(unknown_bits);
-        p.hit_bits = reinterpret_cast<uint32_t *>(hit_bits);
-        p.words = words;
-        p.zero_all = pl.nrays == 0;
-        p.zero_words = p.zero_all ? words : p.nslab - 1 + (words - row_words);
-    }
-    int threads = ((pl.nrays > 0 ? pl.nrays : 1) + kWave - 1) / kWave * kWave;
-    const int cap = lds > 32 * 1024 ? kMaxThreads : 256;
-    threads = threads > cap ? cap : threads;
-    hipStream_t st = gnbv_stream(stream);
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute((const void *)k_vg_slab<MASKS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return (int)hipGetLastError();
-    for (int e0 = 0; e0 < a.n; e0 += pl.batch) {  // the workspace is reused: the stream orders the batches
-        const int ne = a.n - e0 < pl.batch ? a.n - e0 : pl.batch, ne_pad = (ne + 7) / 8 * 8;
-        int64_t items = (int64_t)ne * pl.pack_words;
-        if ((int64_t)ne * a.k * 3 > items) items = (int64_t)ne * a.k * 3;
-        if constexpr (MASKS)
-            if ((int64_t)ne * a.k * p.zero_words > items) items = (int64_t)ne * a.k * p.zero_words;
-        hipLaunchKernelGGL(k_vg_prep<MASKS>, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, p, e0, ne);
-        if (pl.nrays == 0) continue;
-        hipLaunchKernelGGL(k_vg_fate, dim3((unsigned)(ne_pad * a.k * p.rblocks)), dim3(kFateThreads), 0, st, p, e0, ne);
-        hipLaunchKernelGGL(k_vg_slab<MASKS>, dim3((unsigned)(ne_pad * p.chunks * p.nslab)), dim3(threads), lds, st, p, e0, ne);
-    }
-    return gnbv_launch_status();
 }
 
 GNBV_API int gnbv_view_gain_slab(const GnbvViewGain *args, int slab, void *workspace, size_t workspace_bytes, void *stream)

@@ -25,7 +25,7 @@ import torch
 from .. import _lib
 from ..env.config import TaskConfig
 from .cover_greedy import CoverGreedy, check_contact, check_covered, check_rounds
-from .view_gain import MAX_GRID, MAX_GRID_SLAB, ViewGain
+from .view_gain import MAX_GRID, MAX_GRID_SLAB, ViewGain, slab_workspace
 
 
 def plan_weights(weights, words: int):
@@ -147,12 +147,7 @@ class ViewGainMasksSlab(ViewGainMasks):
         super().__init__(num_envs, k, cfg, range_gt, voxel_size, inv_intrinsics, stride, range_m, device, hit, unknown, words,
                          max_bytes, with_c2w, chunk)
         self.slab = int(slab)
-        self.workspace_bytes = int(self.lib.gnbv_view_gain_slab_workspace_bytes(self.num_envs, self.k, self.g, self.h, self.w,
-                                                                                self.stride))
-        if self.workspace_bytes == 0:
-            raise _lib.GennbvHipError(f"ViewGainMasksSlab: sizes refused (n {num_envs}, k {k}, g {self.g}, camera {self.h}x{self.w}, "
-                                      f"stride {stride})")
-        self.workspace = torch.empty(self.workspace_bytes, dtype=torch.uint8, device=self.device)
+        slab_workspace(self, "ViewGainMasksSlab")
 
     def _launch(self, a):
         _lib.check(self.lib.gnbv_view_gain_slab_masks(C.byref(a), self.slab, self.workspace.data_ptr(), self.workspace_bytes, self.words,

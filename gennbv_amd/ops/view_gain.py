@@ -86,6 +86,15 @@ class ViewGain:
         _lib.check(self.lib.gnbv_view_gain(C.byref(a), _lib.stream_ptr(self.device)), "gnbv_view_gain")
 
 
+def slab_workspace(op, name: str) -> None:
+    """The workspace of the slab path for operator `op` (ViewGainSlab, ViewGainMasksSlab): the library's size for the operator's
+    shapes, its refusal under `name`, and the allocation, once; sets op.workspace_bytes and op.workspace."""
+    op.workspace_bytes = int(op.lib.gnbv_view_gain_slab_workspace_bytes(op.num_envs, op.k, op.g, op.h, op.w, op.stride))
+    if op.workspace_bytes == 0:
+        raise _lib.GennbvHipError(f"{name}: sizes refused (n {op.num_envs}, k {op.k}, g {op.g}, camera {op.h}x{op.w}, stride {op.stride})")
+    op.workspace = torch.empty(op.workspace_bytes, dtype=torch.uint8, device=op.device)
+
+
 class ViewGainSlab(ViewGain):
     """The same operator for grid_size <= 128 (gnbv_view_gain_slab): ViewGain's arguments plus `slab`, the x-planes per
     slab (0 = chosen from the grid size; any height gives the same integers).  The workspace is allocated once, here."""
@@ -96,12 +105,7 @@ class ViewGainSlab(ViewGain):
                  device="cuda:0", with_c2w: bool = False, chunk: int = 0, slab: int = 0):
         super().__init__(num_envs, k, cfg, range_gt, voxel_size, inv_intrinsics, stride, range_m, device, with_c2w, chunk)
         self.slab = int(slab)
-        self.workspace_bytes = int(self.lib.gnbv_view_gain_slab_workspace_bytes(self.num_envs, self.k, self.g, self.h, self.w,
-                                                                                self.stride))
-        if self.workspace_bytes == 0:
-            raise _lib.GennbvHipError(f"ViewGainSlab: sizes refused (n {num_envs}, k {k}, g {self.g}, camera {self.h}x{self.w}, "
-                                      f"stride {stride})")
-        self.workspace = torch.empty(self.workspace_bytes, dtype=torch.uint8, device=self.device)
+        slab_workspace(self, "ViewGainSlab")
 
     def _launch(self, a):
         _lib.check(self.lib.gnbv_view_gain_slab(C.byref(a), self.slab, self.workspace.data_ptr(), self.workspace_bytes,

@@ -55,6 +55,9 @@ CASES = [  # g, (h, w), stride, range, n, k, chunk, occupied density (None: all 
     (33, (60, 80), 4, 2.0, 1, 5, 0, 0.10, "lattice"),  # 33^3 is not a multiple of 32: the last word is partial
     (64, (60, 80), 4, 2.0, 3, 3, 2, 0.05, "lattice"),
     (20, (60, 80), 4, 50.0, 2, 5, 0, None, "lattice"),
+    # a lattice of exactly one wave (64 rays), and one of 4 800 rays: no whole number of waves, more than one turn of 1 024 lanes
+    (20, (8, 8), 1, 50.0, 1, 5, 2, 0.05, "lattice"),
+    (20, (60, 80), 1, 50.0, 1, 5, 2, 0.05, "lattice"),
 ]
 
 

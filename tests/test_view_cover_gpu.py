@@ -167,6 +167,17 @@ def _oracle_cover(mesh, cfg, rng, vox, poses, stride, gt, scanned):
 @pytest.mark.parametrize("stride", [2, 3, 4])
 @pytest.mark.parametrize("kind,g,cam", [("boxes", 20, (60, 80)), ("mixed", 33, (240, 320)), ("boxes", 64, (240, 320))])
 def test_lattice_strides_equal_the_oracle_on_the_rendered_image(kind, g, cam, stride):
+    _lattice_equals_the_oracle(kind, g, cam, stride)
+
+
+# a lattice of exactly one wave (64 rays, one tile), and one of 4 800 rays: 8 x 10 tiles with ragged ones, more than one turn of
+# the workgroup's 16 waves
+@pytest.mark.parametrize("cam", [(8, 8), (60, 80)])
+def test_lattice_of_one_wave_and_of_several_turns_equals_the_oracle(cam):
+    _lattice_equals_the_oracle("boxes", 20, cam, 1)
+
+
+def _lattice_equals_the_oracle(kind, g, cam, stride):
     from gennbv_amd.ops.view_cover import ViewCover
     cfg = _cfg(cam[0], cam[1], g)
     mesh, rng, vox = _mesh_and_frame(kind, 4, g)

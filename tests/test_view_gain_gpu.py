@@ -75,6 +75,9 @@ CASES = [  # g, (h, w), stride, range, n, k, chunk, occupied density (None: all 
     (64, (400, 400), 8, 50.0, 1, 3, 2, None, "lattice"),
     (64, (60, 80), 4, 2.0, 37, 3, 2, 0.05, "lattice"),
     (64, (240, 320), 8, 50.0, 1, 7, 3, 0.02, "outside"),
+    # a lattice of exactly one wave (64 rays), and one of 4 800 rays: no whole number of waves, more than one turn of 1 024 lanes
+    (20, (8, 8), 1, 50.0, 1, 5, 2, 0.05, "lattice"),
+    (20, (60, 80), 1, 50.0, 1, 5, 2, 0.05, "lattice"),
 ]
 
 

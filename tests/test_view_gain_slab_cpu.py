@@ -1,14 +1,16 @@
-"""CPU: the ray record and the slab cut of gnbv_view_gain_slab (gennbv_amd/csrc/viewgain.hip: k_vg_fate, make_slab_walk,
-k_vg_slab) as a Python model, against the oracle's sequential Bresenham.
+"""CPU: the ray record and the slab cut of gnbv_view_gain_slab (gennbv_amd/csrc/viewgain.hip: k_vg_fate, k_vg_slab; the walk
+is gennbv_amd/csrc/ray_walk.h: walk_axes, minor_range, walk_at, make_walk / run_walk, make_slab_cut / walk_steps) as a Python
+model, against the oracle's sequential Bresenham.  tests/test_ray_walk_host_cpu.py runs the C++ itself on the same rays; this
+model stays for what the C++ cannot show: that every 32-bit intermediate fits.
 
 k_vg_fate walks a ray once against the whole grid (make_walk's closed-form entry, then the reference's decision variables)
 and records the first in-grid step, the number of steps up to the voxel in front of the first occupied one, and the x-extent
-of those steps.  k_vg_slab rejects a ray on that extent, cuts the recorded steps to its x-planes [X0, X1) -- exactly if x is
-the dominant axis, by the closed form of the minors (one step wide on both sides, guarded by a test of the slab-local index)
-if not -- and walks them.  Here the same arithmetic, line by line, with Python integers (the kernel's floor_div is exact, so
-`//` stands for it): every in-grid voxel before the stop must be visited exactly once, by the slab that owns its x, in order.
-The slab set-up of a ray of fewer than 2^14 steps runs in 32-bit integers in the kernel: the model asserts that every
-intermediate of such a ray fits.
+of those steps.  k_vg_slab rejects a ray on that extent, cuts the recorded steps to its x-planes [X0, X1) (make_slab_cut)
+-- exactly if x is the dominant axis, by the closed form of the minors (one step wide on both sides, guarded by a test of the
+slab-local index) if not -- and walks them.  Here the same arithmetic, line by line, with Python integers (the header's
+floor_div is exact, so `//` stands for it): every in-grid voxel before the stop must be visited exactly once, by the slab that
+owns its x, in order.  The slab set-up of a ray of fewer than 2^14 steps runs in 32-bit integers (walk_at<int>): the model
+asserts that every intermediate of such a ray fits.
 """
 import numpy as np
 import pytest

@@ -39,6 +39,9 @@ CASES = [  # g, (h, w), stride, range, n, k, occupied density (None: all unknown
     (128, (240, 320), 8, 50.0, 1, 7, 0.01, "outside", 5),
     # rays of more than 2^14 steps: the slab set-up's 64-bit form (shorter rays take the 32-bit one)
     (72, (60, 80), 4, 3000.0, 2, 4, 0.02, "lattice", 5),
+    # a lattice of exactly one wave (64 rays), and one of 4 800 rays: no whole number of waves, more than one turn of 1 024 lanes
+    (65, (8, 8), 1, 50.0, 2, 5, 0.05, "lattice", 24),
+    (65, (60, 80), 1, 50.0, 2, 5, 0.05, "lattice", 24),
 ]
 
 

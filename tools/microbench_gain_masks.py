@@ -24,7 +24,8 @@ on the unknown mask, `plan_weighted(horizon, weights)` on both (one gnbv_cover_g
 of the two single-mask plans it is set against, and -- with --parent-lib -- the two single-mask plans of that build on the same
 masks, then the A/B of tools/microbench_cover_greedy.py (`ab`: this build, that build, that build again, alternated in one call,
 both builds on this build's masks after asserting equal masks and outputs) for `plan("hit")`, `plan("unknown")` and, where that
-build has gnbv_cover_greedy_w, `plan_weighted`.
+build has gnbv_cover_greedy_w, `plan_weighted`.  With --parent-lib the kernel calls themselves get the same A/B, after the same
+assertion: `view_gain_ab` (gnbv_view_gain, or gnbv_view_gain_slab above 64^3) and `masks_both_ab`.
 """
 from __future__ import annotations
 
@@ -77,6 +78,12 @@ def masks_case(name, n, g, h, w, stride, k, args):
         for oname, op in ops.items():
             assert torch.equal(op(tri, poses), want), oname
             out[f"{gname}_{oname}"] = stats(time_calls(lambda: op(tri, poses), args.iters, args.repeats))
+        for oname in ("view_gain", "masks_both"):  # the kernel calls themselves, this build against that build
+            if oname + "_parent" in ops:
+                mine, par = ops[oname], ops[oname + "_parent"]
+                if oname == "masks_both":
+                    assert torch.equal(mine.unknown_bits, par.unknown_bits) and torch.equal(mine.hit_bits, par.hit_bits)
+                ab(out, f"{gname}_{oname}", [lambda: mine(tri, poses)] + [lambda: par(tri, poses)] * 2, args.iters, args.repeats)
         base = out[f"{gname}_view_gain"]["us_median"]
         for oname, masks in (("masks_both", 2), ("masks_hit", 1), ("masks_unknown", 1)):
             row = out[f"{gname}_{oname}"]

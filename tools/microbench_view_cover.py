@@ -1,6 +1,7 @@
 """Microbenchmark of the view coverage (gnbv_view_cover) beside the composed path it replaces.
 
-    python tools/microbench_view_cover.py [--repeats 7] [--iters 2] [--cases ...] [--chunk 0] [--window 0] [--out FILE.json]
+    python tools/microbench_view_cover.py [--repeats 7] [--iters 2] [--cases ...] [--chunk 0] [--window 0] [--parent-lib PATH]
+                                          [--out FILE.json]
 
 Device events around `iters` back-to-back calls, after warm-up, `repeats` times; reported: median / min / max us per call.
 The fused call and the composed path run in the same process, alternated repeat by repeat, on the same mid-episode state
@@ -14,6 +15,10 @@ The fused call and the composed path run in the same process, alternated repeat 
 The composed path, per candidate column j: restore the updater's state (scanned bits and probability codes), gnbv_render_depth
 at poses[:, j], OccupancyGridUpdater.update, read coverage_count.  Its parts are also timed alone (`render_us`, `update_us`,
 `restore_us`: one column each).  Each case checks once that the composed increments equal the fused new_gt.
+
+--parent-lib PATH (another build of libgennbv_hip.so with the same ABI, e.g. the parent commit's: _lib.activate) adds `fused_ab`, the
+A/B of tools/microbench_cover_greedy.py (`ab`: this build, that build, that build again, alternated in one call) for the ViewCover
+call, after asserting that both builds give equal outputs.
 
 Kernel times come from a separate `rocprofv3 --kernel-trace --stats -- python tools/microbench_view_cover.py` run.
 """
@@ -29,6 +34,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+from gennbv_amd import _lib  # noqa: E402
 from gennbv_amd.env import synthetic as S  # noqa: E402
 from gennbv_amd.env.config import TaskConfig  # noqa: E402
 from gennbv_amd.env.mesh_scene import MeshScene  # noqa: E402
@@ -114,6 +120,13 @@ def cover_case(name, mesh, scene, n, g, h, w, stride, k, args, composed=True):
         restore()
     else:
         out["fused"] = stats(alternate([fused_call], args.iters, args.repeats)[0])
+    if args.parent_lib:
+        from tools.microbench_cover_greedy import ab  # (that module imports this one)
+        _lib.activate(args.parent_lib)  # an operator keeps the library that was active when it was built
+        par = ViewCover(mesh, cfg, scene.range_gt, scene.voxel_size, k, stride=stride, chunk=args.chunk, window=args.window)
+        _lib.activate()
+        assert torch.equal(par(poses, upd.gt_bits, scanned0), vc(poses, upd.gt_bits, scanned0))
+        ab(out, "fused", [fused_call] + [lambda: par(poses, upd.gt_bits, scanned0)] * 2, args.iters, args.repeats)
     out["mean_cover"] = vc(poses, upd.gt_bits, scanned0).float().mean(dim=(0, 1)).tolist()
     return out
 
@@ -125,6 +138,7 @@ def main():
     ap.add_argument("--cases", default="g64_s1,g64_s4,dense_s1,g128_s1")
     ap.add_argument("--chunk", type=int, default=0, help="candidates per workgroup (0 = chosen)")
     ap.add_argument("--window", type=int, default=0, help="bit-set words per workgroup (0 = chosen)")
+    ap.add_argument("--parent-lib", default=None, help="another build of libgennbv_hip.so (the same ABI) to set the ViewCover call against")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
