@@ -582,7 +582,12 @@ __global__ __launch_bounds__(split::kThreads) void k_conv2_wgrad_split_dma(
     // 256 workgroups for the 512 items of a 128-sample minibatch every CU starts ONE workgroup instead of two in a row -- the second one's
     // launch, scale loads and first round trip were dead time on the CU (the x-tiled kernels showed it: 90.7 -> 80.6 us from 512 to 256
     // workgroups, profiles/r06_splitx_at_g64_trace.txt).  With gridDim.x >= nitems it is the one-item kernel, bit-identical to
-    // k_conv2_wgrad_split; with fewer workgroups a partial row sums two items in fp32 before the fp64 reduction.
+    // k_conv2_wgrad_split; with fewer workgroups a partial row sums the walk's items in fp32 before the fp64 reduction.
+    // The walk is ONE continuous ring: an item is S = O2 + 1 steps (its iterations -1 .. O2 - 1: conv2's last output row reads layer-1 rows
+    // up to 2 O2), and the next item's iterations -1, 0, 1 are issued in the steps where this item's iterations S - 1 .. S + 1 -- clamped
+    // duplicates, needed only because the compute waves lag by a step -- used to be.  Ring slots and dy2 buffers are indexed by the walk's
+    // running iteration (2 S rows / S steps of offset per item), source rows by the iteration within the item.  Only the first item has a
+    // prologue, only the last the clamped tail and the final drain; each accumulator receives the same products in the same order.
     using namespace split;
     extern __shared__ __attribute__((aligned(16))) char split_lds[];
     char *stage = split_lds, *dyst = split_lds + wdma::kStageBytes + kPadBytes;
@@ -595,7 +600,7 @@ __global__ __launch_bounds__(split::kThreads) void k_conv2_wgrad_split_dma(
     // before anything else of the workgroup's start-up (no clear of 138 KiB + barrier in front of them, no round trip for the scales).
     if (tid < kPadBytes / 16) reinterpret_cast<uint4 *>(split_lds + wdma::kStageBytes)[tid] = make_uint4(0, 0, 0, 0);
     const int P2 = O2 * O2 * O2;
-    const int nsteps = (O2 + 1) & ~1;
+    const int S = O2 + 1;  // steps (= iterations -1 .. O2 - 1) per item: O2 output rows + one step in which the compute waves rest
     if (wv >= kConsWaves) {
         // ---- staging waves: chunk k of wave pw is half row h = pw + 8 k of the iteration (plane h >> 2, row parity (h >> 1) & 1, x parity
         // h & 1) for h < 36; the fifth chunk of waves 4-7 is the dy2 row of plane pw - 4 ----
@@ -605,99 +610,123 @@ __global__ __launch_bounds__(split::kThreads) void k_conv2_wgrad_split_dma(
         const int dpl = pw - 4;
         const uint32_t stage_a = lds_addr(stage), dy_a = lds_addr(dyst);
         float gs = 1.0f, sc[4] = {0.f, 0.f, 0.f, 0.f}, sh[4] = {0.f, 0.f, 0.f, 0.f};
-        bool first = true;
-        for (int item = (int)blockIdx.x; item < nitems; item += (int)gridDim.x) {
+        // What an iteration takes from its item: the sample's y1 / dy2 bases, the plane count, and the running iteration of its own
+        // iteration 0.  All wave-uniform (scalar registers); the lane parts of the addresses never change.
+        struct Item {
+            const float *ybase, *dbase;
+            int np, j0;
+        };
+        const uint32_t ylane = lane * 4, dlane = (uint32_t)(min(vx, O2 - 1) * kC + 4 * q);
+        auto take = [&](Item &it, int item, int j0) {  // false: not a live item (then every later item of the walk is none either)
             int b, oz0, oz1;
-            if (!sample_plane_group(B, O2, kNP, b, oz0, oz1, item)) continue;  // (workgroup-uniform: both roles skip it)
-            const int np = oz1 - oz0, npl = 2 * np + 1;
-            const float *ybase = y1 + ((size_t)b * O1 + 2 * oz0) * planeC + lane * 4;
-            const bool dvalid = dy_wave && dpl < np && vx < O2;
-            const float *dsrc = dy2 + ((size_t)b * P2 + (size_t)(oz0 + min(max(dpl, 0), np - 1)) * O2 * O2 + min(vx, O2 - 1)) * kC + 4 * q;
-            auto issue = [&](int j) {
+            if (item >= nitems || !sample_plane_group(B, O2, kNP, b, oz0, oz1, item)) return false;
+            it.np = oz1 - oz0, it.j0 = j0;
+            it.ybase = y1 + ((size_t)b * O1 + 2 * oz0) * planeC;
+            it.dbase = dy2 + ((size_t)b * P2 + (size_t)(oz0 + min(max(dpl, 0), it.np - 1)) * O2 * O2) * kC;
+            return true;
+        };
+        // iteration J of the WALK (ring slots, dy2 buffers) = iteration J - it.j0 of item `it` (source rows)
+        auto issue = [&](const Item &it, int J) {
 #ifdef WDMA_ABL_NODMA  // (measurement build: no requests -- conversion + contraction alone)
-                return;
+            return;
 #endif
+            const int j = J - it.j0, npl = 2 * it.np + 1;
 #pragma unroll
-                for (int k = 0; k < wdma::kChunks; ++k) {
-                    if (k == wdma::kChunks - 1 && dy_wave) {
-                        glds16_nt(dsrc + (size_t)min(max(j, 0), O2 - 1) * O2 * kC, __builtin_amdgcn_readfirstlane(dy_a + (uint32_t)((((j + 3) % wdma::kDyBufs) * kNP + dpl) * 1024)));
-                    } else {
-                        const int h = pw + 8 * k, pi = h >> 2, row = 2 * j + 1 + ((h >> 1) & 1), slot = (row + 2 * R) % R;
-                        const float *src = ybase + (uint32_t)min(pi, npl - 1) * planeC + (uint32_t)min(max(row, 0), O1 - 1) * rowC + (h & 1) * (16 * kC);
-                        glds16_nt(src, __builtin_amdgcn_readfirstlane(stage_a + (uint32_t)((pi * R + slot) * kRowBytes + (h & 1) * 1024)));
-                    }
+            for (int k = 0; k < wdma::kChunks; ++k) {
+                if (k == wdma::kChunks - 1 && dy_wave) {
+                    glds16_nt(it.dbase + dlane + (size_t)min(max(j, 0), O2 - 1) * O2 * kC, __builtin_amdgcn_readfirstlane(dy_a + (uint32_t)((((J + 3) % wdma::kDyBufs) * kNP + dpl) * 1024)));
+                } else {
+                    const int h = pw + 8 * k, pi = h >> 2, rpar = (h >> 1) & 1, row = 2 * j + 1 + rpar, slot = (2 * J + 1 + rpar + 2 * R) % R;
+                    const float *src = it.ybase + ylane + (uint32_t)min(pi, npl - 1) * planeC + (uint32_t)min(max(row, 0), O1 - 1) * rowC + (h & 1) * (16 * kC);
+                    glds16_nt(src, __builtin_amdgcn_readfirstlane(stage_a + (uint32_t)((pi * R + slot) * kRowBytes + (h & 1) * 1024)));
                 }
-            };
-            auto convert = [&](int j) {
+            }
+        };
+        auto convert = [&](int np, int J) {
 #ifdef WDMA_ABL_NOCONV  // (measurement build: the chunks stay raw -- transport + contraction alone, results meaningless)
-                return;
+            return;
 #endif
-                char *cp[wdma::kChunks];
-                float4 raw[wdma::kChunks];
+            const bool dvalid = dy_wave && dpl < np && vx < O2;
+            char *cp[wdma::kChunks];
+            float4 raw[wdma::kChunks];
 #pragma unroll
-                for (int k = 0; k < wdma::kChunks; ++k) {
-                    if (k == wdma::kChunks - 1 && dy_wave) {
-                        cp[k] = dyst + (((j + 3) % wdma::kDyBufs) * kNP + dpl) * 1024;
-                    } else {
-                        const int h = pw + 8 * k, pi = h >> 2, row = 2 * j + 1 + ((h >> 1) & 1), slot = (row + 2 * R) % R;
-                        cp[k] = stage + (pi * R + slot) * kRowBytes + (h & 1) * 1024;
-                    }
-                    raw[k] = *reinterpret_cast<const float4 *>(cp[k] + lane * 16);
+            for (int k = 0; k < wdma::kChunks; ++k) {
+                if (k == wdma::kChunks - 1 && dy_wave) {
+                    cp[k] = dyst + (((J + 3) % wdma::kDyBufs) * kNP + dpl) * 1024;
+                } else {
+                    const int h = pw + 8 * k, pi = h >> 2, slot = (2 * J + 1 + ((h >> 1) & 1) + 2 * R) % R;
+                    cp[k] = stage + (pi * R + slot) * kRowBytes + (h & 1) * 1024;
                 }
+                raw[k] = *reinterpret_cast<const float4 *>(cp[k] + lane * 16);
+            }
+            asm volatile("" ::: "memory");  // (every read of the chunks before the first write: the images overwrite them in place)
 #pragma unroll
-                for (int k = 0; k < wdma::kChunks; ++k) {
-                    float z[4];
-                    const float v[4] = {raw[k].x, raw[k].y, raw[k].z, raw[k].w};
-                    if (k == wdma::kChunks - 1 && dy_wave) {
+            for (int k = 0; k < wdma::kChunks; ++k) {
+                float z[4];
+                const float v[4] = {raw[k].x, raw[k].y, raw[k].z, raw[k].w};
+                if (k == wdma::kChunks - 1 && dy_wave) {
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) z[e] = dvalid ? v[e] * gs : 0.0f;
-                    } else {
-                        const bool pad_voxel = ((pw + 8 * k) & 1) == 1 && vx == 15;  // (x parity 1, slot 15: meets dy2's zero padding)
+                    for (int e = 0; e < 4; ++e) z[e] = dvalid ? v[e] * gs : 0.0f;
+                } else {
+                    const bool pad_voxel = ((pw + 8 * k) & 1) == 1 && vx == 15;  // (x parity 1, slot 15: meets dy2's zero padding)
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) z[e] = pad_voxel ? 0.0f : __builtin_amdgcn_fmed3f(fmaf(sc[e], v[e], sh[e]), 0.f, kZMax);
-                    }
-                    h4 hi, lo;
+                    for (int e = 0; e < 4; ++e) z[e] = pad_voxel ? 0.0f : __builtin_amdgcn_fmed3f(fmaf(sc[e], v[e], sh[e]), 0.f, kZMax);
+                }
+                h4 hi, lo;
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        _Float16 a, c2;
-                        split2(z[e], a, c2);
-                        hi[e] = a;
-                        lo[e] = c2;
-                    }
-                    char *dst = cp[k] + vx * 32 + q * 8;
-                    *reinterpret_cast<h4 *>(dst) = hi;
+                for (int e = 0; e < 4; ++e) {
+                    _Float16 a, c2;
+                    split2(z[e], a, c2);
+                    hi[e] = a;
+                    lo[e] = c2;
+                }
+                char *dst = cp[k] + vx * 32 + q * 8;
+                *reinterpret_cast<h4 *>(dst) = hi;
 #ifndef SPLIT_HI_ONLY
-                    *reinterpret_cast<h4 *>(dst + 512) = lo;
+                *reinterpret_cast<h4 *>(dst + 512) = lo;
 #endif
-                }
-            };
-            issue(-1);
-            issue(0);
-            if (first) {
-                // the scales, requested BEHIND the first ten chunks: the compiler's wait for them (it does not count the requests above) also
-                // retires those -- which the first conversion needs anyway
-                gs = grad_scale(absmax);
+            }
+        };
+        Item cur;
+        if (take(cur, (int)blockIdx.x, 0)) {  // (workgroup-uniform: both roles skip a walk without a live item)
+            issue(cur, -1);
+            issue(cur, 0);
+            // the scales, requested BEHIND the first ten chunks: the compiler's wait for them (it does not count the requests above) also
+            // retires those -- which the first conversion needs anyway
+            gs = grad_scale(absmax);
 #pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    sc[s] = scale1[4 * q + s] * kZScale;
-                    sh[s] = shift1[4 * q + s] * kZScale;
-                }
-                first = false;
+            for (int s = 0; s < 4; ++s) {
+                sc[s] = scale1[4 * q + s] * kZScale;
+                sh[s] = shift1[4 * q + s] * kZScale;
             }
 #pragma unroll
             for (int s = 0; s < 4; ++s) asm volatile("" : "+v"(sc[s]), "+v"(sh[s]));  // (computed HERE: a use sunk behind later requests would make the compiler wait for them)
             wait_vm_keep<0>();
-            convert(-1);
-            issue(1);
-            convert(0);  // (iteration 0 landed with iteration -1: the wait above was for everything)
+            convert(cur.np, -1);
+            issue(cur, 1);
+            convert(cur.np, 0);  // (iteration 0 landed with iteration -1: the wait above was for everything)
             split_step_barrier();
-            for (int t = 1; t <= nsteps; ++t) {
-                issue(t + 1);  // rows 2t+3, 2t+4: their slots held rows 2t-4, 2t-3, last read before the previous barrier
-                wait_vm_keep<wdma::kChunks>();  // everything but the five just issued: iteration t has landed
-                convert(t);
-                split_step_barrier();
+            for (int item = (int)blockIdx.x;;) {
+                // The walk is ONE ring: the next item's iterations -1, 0, 1 are requested in the steps tt = S - 2, S - 1, S, where this item
+                // has nothing left to request (its iterations S - 1 .. S + 1 lie outside the volume), and converted one step later.  Only
+                // the walk's last item runs that tail against itself: clamped duplicates into slots nobody reads any more.
+                Item nxt = cur;
+                const bool more = take(nxt, item + (int)gridDim.x, cur.j0 + S);
+                for (int tt = 1; tt <= S; ++tt) {
+                    const int T = cur.j0 + tt;
+                    // rows 2T+3, 2T+4: their slots held rows 2T-4, 2T-3, last read before the previous barrier
+                    // (selected field by field: scalar selects, no branch around the requests)
+                    const bool in = tt >= S - 2, cn = tt >= S - 1;
+                    const Item is = {in ? nxt.ybase : cur.ybase, in ? nxt.dbase : cur.dbase, in ? nxt.np : cur.np, in ? nxt.j0 : cur.j0};
+                    issue(is, T + 1);
+                    wait_vm_keep<wdma::kChunks>();  // everything but the five just issued: iteration T has landed
+                    convert(cn ? nxt.np : cur.np, T);
+                    split_step_barrier();
+                }
+                if (!more) break;
+                cur = nxt, item += (int)gridDim.x;
             }
-            wait_vm_keep<0>();  // (nothing may land in a slot the next item's first requests target, or after the workgroup has ended)
+            wait_vm_keep<0>();  // (nothing may land after the workgroup has ended)
         }
     } else {
         // ---- compute waves: k_conv2_wgrad_split's, on the seven-row ring and the three dy2 buffers ----
@@ -718,13 +747,15 @@ __global__ __launch_bounds__(split::kThreads) void k_conv2_wgrad_split_dma(
         h8 ones;
 #pragma unroll
         for (int e = 0; e < 8; ++e) ones[e] = (_Float16)1.0f;
-        for (int item = (int)blockIdx.x; item < nitems; item += (int)gridDim.x) {
-            int b, oz0, oz1;
-            if (!sample_plane_group(B, O2, kNP, b, oz0, oz1, item)) continue;
-            const int np = oz1 - oz0;
-            split_step_barrier();
-            for (int t = 1; t <= nsteps; ++t) {
-                const int oy = t - 1;
+        // the staging waves' walk: S steps per item on one continuous ring, row 2 S and step S of offset per item
+        int b, oz0, oz1, j0 = 0;
+        bool more = (int)blockIdx.x < nitems && sample_plane_group(B, O2, kNP, b, oz0, oz1, (int)blockIdx.x);
+        if (more) split_step_barrier();
+        for (int item = (int)blockIdx.x; more; item += (int)gridDim.x, j0 += S) {
+            const int np = __builtin_amdgcn_readfirstlane(oz1 - oz0);
+            more = item + (int)gridDim.x < nitems && sample_plane_group(B, O2, kNP, b, oz0, oz1, item + (int)gridDim.x);
+            for (int tt = 1; tt <= S; ++tt) {
+                const int oy = tt - 1, roy = j0 + oy;  // output row of the item / of the walk
 #ifdef WDMA_ABL_NOCOMP  // (measurement build: the compute waves only keep the barriers -- transport + conversion alone)
                 if (false) {
 #else
@@ -732,8 +763,8 @@ __global__ __launch_bounds__(split::kThreads) void k_conv2_wgrad_split_dma(
 #endif
                     uint32_t rowoff[3];
 #pragma unroll
-                    for (int dy = 0; dy < 3; ++dy) rowoff[dy] = (uint32_t)(((2 * oy + dy) % R) * kRowBytes);
-                    const char *dybuf = dyst + (oy % wdma::kDyBufs) * kNP * 1024 + lane * 8;
+                    for (int dy = 0; dy < 3; ++dy) rowoff[dy] = (uint32_t)(((2 * roy + dy) % R) * kRowBytes);
+                    const char *dybuf = dyst + (roy % wdma::kDyBufs) * kNP * 1024 + lane * 8;
                     // Every operand of a k-block is requested before its first MFMA, and the MFMAs run tap-interleaved (hh of every tap, then
                     // lh, then hl).  Each accumulator still receives its products in the same order as in k_conv2_wgrad_split.
 #pragma unroll
@@ -1367,26 +1398,45 @@ __global__ void k_prep_w2_split_only(const float *__restrict__ W2, float *__rest
 template <bool TRAIN>
 __global__ __launch_bounds__(split::kThreads) void k_conv12_fwd_split(
     const int8_t *__restrict__ grid_i8, const int64_t *__restrict__ rows, int64_t grid_row_stride, const float *__restrict__ W1 /*[16][27]*/,
-    const float *__restrict__ b1, const float *__restrict__ scale1, const float *__restrict__ shift1, int B, int G, int O1, int O2,
+    const float *__restrict__ b1, const float *__restrict__ scale1, const float *__restrict__ shift1, int B, int G, int O1, int O2, int nitems,
     const uint4 *__restrict__ w2img, const float *__restrict__ b2, float *__restrict__ y2, float *__restrict__ y1 /*TRAIN: stored for the backward*/,
-    float *__restrict__ partials /*TRAIN: BN2 partial sums, one row per workgroup*/)
+    float *__restrict__ partials /*TRAIN: BN2 partial sums, one row per ITEM*/)
 {
+    // A workgroup walks the items (sample, plane group) blockIdx.x, + gridDim.x, ... on ONE continuous ring: an item is `nsteps` steps, and
+    // the staging waves compute the next item's iterations -1 and 0 in the two steps where the compute waves finish this item's last output
+    // row (iterations nsteps - 1 and nsteps of an item lie outside the volume; only the walk's last item still runs them, as clamped
+    // duplicates).  Ring rows, slab parity and the `red` buffers are indexed by the walk's running step, 2 nsteps rows of offset per item.
+    // The start-up (W1 split, weight fragments, scales, first round trip) is paid once per workgroup.  With gridDim.x >= nitems it is the
+    // one-item kernel; the results do not depend on the grid.
     using namespace split;
     using namespace fsplit;
     extern __shared__ __attribute__((aligned(16))) char split_lds[];
+    __shared__ float bn2x[2][2 * kC];  // TRAIN: an item's BN2 sums of the two even compute waves, on their way to wave 0
     char *stage = split_lds;
     float *red = reinterpret_cast<float *>(split_lds + split::kStageBytes + kPadBytes);
     char *inbuf = split_lds + split::kStageBytes + kPadBytes + kRedBytes;
-    int b, oz0, oz1;
-    const bool live = sample_plane_group(B, O2, kNP, b, oz0, oz1);
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = __builtin_amdgcn_readfirstlane(tid / kWave);
-    if (!live) {
-        if (TRAIN) write_partials(partials, kWaves, wv, 0.f, 0.f);
+    const int nsteps = (O2 + 2) & ~1;  // steps per item: O2 compute steps + the deferred epilogue of the last row, rounded up to even
+    const int stride = (int)gridDim.x;
+    // an item of the walk, as the staging waves need it: wave-uniform values (scalar registers); j0 = the running iteration of its iteration 0
+    struct Item {
+        const int8_t *in;
+        int b, oz0, np, top, j0;
+    };
+    auto take = [&](Item &it, int item, int j0) {  // false: not a live item (then every later item of the walk is none either)
+        int b, oz0, oz1;
+        if (item >= nitems || !sample_plane_group(B, O2, kNP, b, oz0, oz1, item)) return false;
+        it.b = b, it.oz0 = oz0, it.np = oz1 - oz0, it.top = (int)(oz1 == O2), it.j0 = j0;
+        it.in = grid_i8 + (rows ? rows[b] : (int64_t)b) * grid_row_stride;
+        return true;
+    };
+    Item cur;
+    if (!take(cur, (int)blockIdx.x, 0)) {
+        // (a non-live item still has its zero row)
+        if (TRAIN && tid < 2 * kC)
+            for (int item = (int)blockIdx.x; item < nitems; item += stride) partials[(size_t)item * 2 * kC + tid] = 0.0f;
         return;
     }
-    const int np = oz1 - oz0;
-    const int nsteps = (O2 + 2) & ~1;
-    float s_sum = 0.0f, s_sq = 0.0f;
     if (wv >= kCompWaves) {
         // ---- staging waves: conv1 + BN1 + ReLU on the fly ----
         const int ptid = tid - kCompWaves * kWave, pw = min(max(wv - kCompWaves, 0), kStageWaves - 1);
@@ -1432,11 +1482,11 @@ __global__ __launch_bounds__(split::kThreads) void k_conv12_fwd_split(
         }
         // input staging: piece f = ptid < 380 -> (plane f / 20, row (f / 4) % 5, 16-byte quarter f % 4)
         const int f = min(ptid, kInPieces - 1), fpl = f / (kInRows * 4), frow = (f >> 2) % kInRows, fq = f & 3;
-        const int8_t *in = grid_i8 + (rows ? rows[b] : (int64_t)b) * grid_row_stride;
-        const int plane_g = min(4 * oz0 + fpl, G - 1);
-        auto in_req = [&](int j) {  // input rows 4j+2 .. 4j+6 (clamped; UNCONDITIONAL)
+        // iteration J of the walk = iteration J - j0 of the item whose sample row `in` and first plane 4 oz0 are given
+        auto in_req = [&](const int8_t *in, int oz0, int j0, int J) {  // input rows 4j+2 .. 4j+6 (clamped; UNCONDITIONAL)
+            const int j = J - j0, plane_g = min(4 * oz0 + fpl, G - 1);
             const int row_g = min(max(4 * j + 2 + frow, 0), G - 1);
-            const int8_t *src = in + ((size_t)plane_g * G + row_g) * G + 16 * fq;
+            const int8_t *src = in + (uint32_t)((plane_g * G + row_g) * G + 16 * fq);  // (inside one sample: G^3 bytes)
             if constexpr (TRAIN) {  // (opaque request: the caller waits with wait_vm_keep1, see st4_nt_masked)
                 u4v_t v;
                 ldu4_nt_async(v, src);
@@ -1469,7 +1519,8 @@ __global__ __launch_bounds__(split::kThreads) void k_conv12_fwd_split(
         // y1 store (TRAIN): lane part of the address -- voxel x = 2n + par of a row, channels 4g .. 4g+3.  x = 31 IS the padding slot of
         // the odd half row (which no kernel reads as data); tiles outside the volume / of the neighbour's plane go there as well.
         const uint32_t y1_lane = (uint32_t)((par * 16 + n) * kC + 4 * g), y1_pad = (uint32_t)((16 + 15) * kC + 4 * g);
-        auto compute = [&](int j, const int jp /* = j & 1, a literal at every call */) {
+        // iteration J of the walk (ring slot, slab parity) = iteration J - it.j0 of item `it` (TRAIN: whose y1 rows it stores)
+        auto compute = [&](const Item &it, int J, const int jp /* = J & 1, a literal at every call */) {
             auto gather = [&](int k, h8 &xa, h8 &xc) {
                 uint32_t d[6];
 #pragma unroll
@@ -1484,7 +1535,7 @@ __global__ __launch_bounds__(split::kThreads) void k_conv12_fwd_split(
             };
             // software pipeline: the input bytes of tile k + 1 are requested between the MFMAs of tile k and its epilogue -- the
             // compiler cannot move an LDS read above the previous tile's ring stores itself (same LDS array)
-            const int row = 2 * j + 1 + rsel, slot = (row + kRing) % kRing;
+            const int row = 2 * (J - it.j0) + 1 + rsel, slot = (2 * J + 1 + rsel + kRing) % kRing;
             // (opaque once per step, in place: otherwise the 3 x 3 x 2 sums base + distance are hoisted out of the step loop as values
             // of their own and spill, instead of being folded into the reads' offset fields)
 #pragma unroll
@@ -1517,8 +1568,8 @@ __global__ __launch_bounds__(split::kThreads) void k_conv12_fwd_split(
                     // BRANCH-FREE: a conditional store makes the compiler's wait-count merge wait for the stores just issued when
                     // the next input piece is taken from its registers.  Row base in scalar registers, lane part precomputed.
                     // (bitwise, not && / ||: the short-circuit form becomes control flow with the two addresses in a stack array)
-                    const int own = __builtin_amdgcn_readfirstlane((int)(row >= 0) & (int)(row < O1) & ((int)(pi < 2 * np) | ((int)(pi == 2 * np) & (int)(oz1 == O2))));
-                    const uint32_t rowbase = vox1(b, min(2 * oz0 + pi, O1 - 1), min(max(row, 0), O1 - 1), 0, O1) * kC;
+                    const int own = __builtin_amdgcn_readfirstlane((int)(row >= 0) & (int)(row < O1) & ((int)(pi < 2 * it.np) | ((int)(pi == 2 * it.np) & it.top)));
+                    const uint32_t rowbase = vox1(it.b, min(2 * it.oz0 + pi, O1 - 1), min(max(row, 0), O1 - 1), 0, O1) * kC;
                     char *dst1 = reinterpret_cast<char *>(y1 + __builtin_amdgcn_readfirstlane(rowbase));
                     // all 64 lanes where the workgroup owns the tile; lane 0 alone, into the row's padding slot, where it does not
                     // (the first 32 / 64 samples' y1 stored WITHOUT the non-temporal hint, so that the backward finds a part of it in the
@@ -1545,34 +1596,44 @@ __global__ __launch_bounds__(split::kThreads) void k_conv12_fwd_split(
         constexpr int kVmHalf = kTilesPerWave + 1, kVmFull = 2 * kTilesPerWave + 1;
         static_assert(kTilesPerWave == 3 && kVmHalf == 4 && kVmFull == 7, "the explicit vmcnt waits of the training forward's staging waves assume "
                       "kTilesPerWave y1 stores + one input request per half step (re-derive them when kNPl / kStageWaves change)");
-        u4v_t ra = in_req(-1), rb = in_req(0);
+        u4v_t ra = in_req(cur.in, cur.oz0, 0, -1), rb = in_req(cur.in, cur.oz0, 0, 0);
         if constexpr (TRAIN) wait_vm_keep1<1>(ra);
         in_store(-1, ra);
-        ra = in_req(1);
+        ra = in_req(cur.in, cur.oz0, 0, 1);
         split_step_barrier();
-        compute(-1, 1);
+        compute(cur, -1, 1);
         if constexpr (TRAIN) wait_vm_keep1<kVmHalf>(rb);  // ra's request + 3 stores
         in_store(0, rb);
-        rb = in_req(2);
+        rb = in_req(cur.in, cur.oz0, 0, 2);
         split_step_barrier();
-        compute(0, 0);
+        compute(cur, 0, 0);
         if constexpr (TRAIN) wait_vm_keep1<kVmFull>(ra);  // 3 stores + rb's request + 3 stores: the steady state
         in_store(1, ra);
-        ra = in_req(3);
+        ra = in_req(cur.in, cur.oz0, 0, 3);
         split_step_barrier();
-        // step t: compute iteration t (slab t & 1), store iteration t + 1 (requested at step t - 1), request t + 3.  rb holds
-        // even iterations, ra odd ones.  Branch-free around the requests.
-        for (int t = 1; t <= nsteps; t += 2) {
-            compute(t, 1);
-            if constexpr (TRAIN) wait_vm_keep1<kVmFull>(rb);
-            in_store(t + 1, rb);
-            rb = in_req(t + 3);
-            split_step_barrier();
-            compute(t + 1, 0);
-            if constexpr (TRAIN) wait_vm_keep1<kVmFull>(ra);
-            in_store(t + 2, ra);
-            ra = in_req(t + 4);
-            split_step_barrier();
+        // step T = j0 + tt: compute iteration T (slab T & 1), store iteration T + 1 (requested at step T - 1), request T + 3.  rb holds
+        // even iterations, ra odd ones.  Branch-free around the requests.  Iterations nsteps - 1 and later of an item ARE the next item's
+        // iterations -1 and later (selected field by field: scalar selects); the walk's last item runs them against itself.
+        for (int item = (int)blockIdx.x;;) {
+            Item nxt = cur;
+            const bool more = take(nxt, item + stride, cur.j0 + nsteps);
+            for (int tt = 1; tt <= nsteps; tt += 2) {
+                const int T = cur.j0 + tt;
+                const bool cn = tt >= nsteps - 1, rbn = tt + 3 >= nsteps - 1, ran = tt + 4 >= nsteps - 1;
+                const Item ci = {nullptr, cn ? nxt.b : cur.b, cn ? nxt.oz0 : cur.oz0, cn ? nxt.np : cur.np, cn ? nxt.top : cur.top, cn ? nxt.j0 : cur.j0};
+                compute(ci, T, 1);
+                if constexpr (TRAIN) wait_vm_keep1<kVmFull>(rb);
+                in_store(T + 1, rb);
+                rb = in_req(rbn ? nxt.in : cur.in, rbn ? nxt.oz0 : cur.oz0, rbn ? nxt.j0 : cur.j0, T + 3);
+                split_step_barrier();
+                compute(ci, T + 1, 0);
+                if constexpr (TRAIN) wait_vm_keep1<kVmFull>(ra);
+                in_store(T + 2, ra);
+                ra = in_req(ran ? nxt.in : cur.in, ran ? nxt.oz0 : cur.oz0, ran ? nxt.j0 : cur.j0, T + 4);
+                split_step_barrier();
+            }
+            if (!more) break;
+            cur = nxt, item += stride;
         }
     } else {
         // ---- compute waves: k_conv2_fwd_split's arithmetic; wave = (plane pair wv >> 1, k-half wv & 1), the two planes one after the
@@ -1590,6 +1651,9 @@ __global__ __launch_bounds__(split::kThreads) void k_conv12_fwd_split(
         const int P2 = O2 * O2 * O2;
         const bool second = (g >> 1) != 0;
         f32x4 prev0 = {0.f, 0.f, 0.f, 0.f}, prev1 = prev0;
+        float s_sum = 0.0f, s_sq = 0.0f;
+        int b = cur.b, oz0 = cur.oz0, np = cur.np, j0 = 0;  // the item being walked / the running step of its step 0
+        // step t of the item: output row oy = t - 1 from ring rows 2 (j0 + oy) + dy of the walk  (t & 1 == (j0 + t) & 1: nsteps is even)
         auto plane_step = [&](const int q, f32x4 &prev, int t) {
             const int oy = t - 1, pl = 2 * pl2 + q;
             const uint32_t a_lane = (uint32_t)(2 * pl * kRing * kRowBytes + m * 32 + (g & 1) * 16);
@@ -1613,7 +1677,7 @@ __global__ __launch_bounds__(split::kThreads) void k_conv12_fwd_split(
             if (pl < np && oy < O2) {
                 uint32_t rowoff[3];
 #pragma unroll
-                for (int dy = 0; dy < 3; ++dy) rowoff[dy] = (uint32_t)(((2 * oy + dy) % kRing) * kRowBytes);
+                for (int dy = 0; dy < 3; ++dy) rowoff[dy] = (uint32_t)(((2 * (j0 + oy) + dy) % kRing) * kRowBytes);
                 auto tap_off = [&](int tp) {
                     const int dz = tp / 9, dy = (tp / 3) % 3, dx = tp % 3;
                     return (uint32_t)(dz * kRing * kRowBytes + (dx == 1 ? 1024 : 0) + (dx == 2 ? 32 : 0)) + rowoff[dy];
@@ -1652,13 +1716,33 @@ __global__ __launch_bounds__(split::kThreads) void k_conv12_fwd_split(
         split_step_barrier();
         split_step_barrier();
         split_step_barrier();
-        for (int t = 1; t <= nsteps; ++t) {
-            plane_step(0, prev0, t);
-            plane_step(1, prev1, t);
-            split_step_barrier();
+        for (int item = (int)blockIdx.x;;) {
+            for (int t = 1; t <= nsteps; ++t) {
+                plane_step(0, prev0, t);
+                plane_step(1, prev1, t);
+                if (TRAIN && t == nsteps) {
+                    // the item's BN2 partial row: the sums of waves 0 and 2 (the odd waves and the staging waves hold none), added by wave 0
+                    // behind the step's barrier -- the same additions in the same order as one workgroup per item made them
+                    const float s = kgroup_sum(s_sum), sq = kgroup_sum(s_sq);
+                    if (kh == 0 && lane < kC) {
+                        bn2x[pl2][lane] = s;
+                        bn2x[pl2][kC + lane] = sq;
+                    }
+                    s_sum = 0.0f, s_sq = 0.0f;
+                }
+                split_step_barrier();
+            }
+            if (TRAIN && wv == 0 && lane < 2 * kC) partials[(size_t)item * 2 * kC + lane] = bn2x[0][lane] + bn2x[1][lane];
+            item += stride;
+            int oz1;
+            if (item >= nitems || !sample_plane_group(B, O2, kNP, b, oz0, oz1, item)) {
+                if (TRAIN && wv == 0 && lane < 2 * kC)
+                    for (; item < nitems; item += stride) partials[(size_t)item * 2 * kC + lane] = 0.0f;  // (a non-live item still has its zero row)
+                break;
+            }
+            np = oz1 - oz0, j0 += nsteps;
         }
     }
-    if (TRAIN) write_partials(partials, kWaves, wv, s_sum, s_sq);
 }
 
 

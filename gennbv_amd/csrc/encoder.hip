@@ -2021,7 +2021,7 @@ static inline int splitx_max_wg()
     const int v = e ? atoi(e) : 0;
     return v >= 8 && v <= 512 ? (v & ~7) : 512;
 }
-// most workgroups of the G = 64 split kernels that walk several items (round 6: k_conv2_wgrad_split_dma): 256 = one per CU, i.e. two items
+// most workgroups of the G = 64 split kernels that walk several items (k_conv2_wgrad_split_dma, k_conv12_fwd_split): 256 = one per CU, i.e. two items
 // per workgroup at the bench's minibatch instead of two workgroups per CU one after the other; GENNBV_CONV_MAXWG=512 restores one item per
 // workgroup (bit-identity tests against the register-staged kernel, A/B runs)
 static inline int conv_max_wg()
@@ -2127,8 +2127,10 @@ GNBV_API int gnbv_encoder_grid_forward(const float *obs_grid, const int64_t *row
             if (e != hipSuccess) return (int)e;
             attr_fe = true;
         }
-        hipLaunchKernelGGL(k_conv12_fwd_split<false>, dim3(sample_plane_group_grid(batch, O2, split::kNP)), dim3(split::kThreads), fsplit::kLdsBytes, st,
-                           p->grid_i8, rows, p->grid_i8_row_stride, p->w1, p->b1, (const float *)bn1, (const float *)(bn1 + kC), batch, grid, O1, O2,
+        // (a workgroup walks items block, block + grid, ... on one continuous ring: one workgroup per CU by default)
+        const int nitems = sample_plane_group_grid(batch, O2, split::kNP);
+        hipLaunchKernelGGL(k_conv12_fwd_split<false>, dim3(min(nitems, conv_max_wg())), dim3(split::kThreads), fsplit::kLdsBytes, st,
+                           p->grid_i8, rows, p->grid_i8_row_stride, p->w1, p->b1, (const float *)bn1, (const float *)(bn1 + kC), batch, grid, O1, O2, nitems,
                            (const uint4 *)w.w2split, p->b2, y2, (float *)nullptr, (float *)nullptr);
         if ((err = gnbv_launch_status())) return err;
     } else {
@@ -2159,8 +2161,10 @@ GNBV_API int gnbv_encoder_grid_forward(const float *obs_grid, const int64_t *row
             if (e != hipSuccess) return (int)e;
             attr_ft = true;
         }
-        hipLaunchKernelGGL(k_conv12_fwd_split<true>, dim3(sample_plane_group_grid(batch, O2, split::kNP)), dim3(split::kThreads), fsplit::kLdsBytes, st,
-                           p->grid_i8, rows, p->grid_i8_row_stride, p->w1, p->b1, (const float *)bn1, (const float *)(bn1 + kC), batch, grid, O1, O2,
+        // (the BN2 partial rows stay one per ITEM, whatever the grid: k_stats_reduce sees the same rows)
+        const int nitems = sample_plane_group_grid(batch, O2, split::kNP);
+        hipLaunchKernelGGL(k_conv12_fwd_split<true>, dim3(min(nitems, conv_max_wg())), dim3(split::kThreads), fsplit::kLdsBytes, st,
+                           p->grid_i8, rows, p->grid_i8_row_stride, p->w1, p->b1, (const float *)bn1, (const float *)(bn1 + kC), batch, grid, O1, O2, nitems,
                            (const uint4 *)w.w2split, p->b2, y2, (float *)y1, w.bn_part);
     } else {
         const size_t c1_lds = (size_t)3 * (2 * O1 + 1) * grid * sizeof(float);
