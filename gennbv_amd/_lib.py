@@ -98,6 +98,7 @@ SIGNATURES = {
     "gnbv_gather_minibatch": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "gnbv_ppo_loss": (_i, [_p, _p]),
     "gnbv_ppo_loss_finish": (_i, [_p, _p]),
+    "gnbv_imitation_loss": (_i, [_p, _p]),
     "gnbv_multicategorical_sample": (_i, [_p, _i, _i, _i, _p, _p, _i, _p, _p, _p]),
     "gnbv_ppo_loss_rsl": (_i, [_i, _p, _p, _p, _p, _p, _p, _f, _f, _f, _i, _p, _p, _p, _p, _p]),
     "gnbv_adam_workspace_bytes": (_sz, []),
@@ -244,6 +245,14 @@ class GnbvPpoLoss(C.Structure):
                 ("advantages", _p), ("returns", _p), ("d_logits", _p), ("d_values", _p), ("head_entropy", _p),
                 ("head_lse", _p), ("stats", _p), ("stats_row", _p), ("stop_flag", _p), ("scratch", _p), ("kl_out", _p),
                 ("rows", _p), ("adv_norm", _p), ("defer_stats", _i)]
+
+
+class GnbvImitationLoss(C.Structure):
+    """include/gennbv_hip.h: GnbvImitationLoss"""
+    _fields_ = [("batch", _i), ("n_logits", _i), ("n_heads", _i), ("head_dims", _i * 8), ("k", _i),
+                ("label_smoothing", _f), ("ent_coef", _f), ("vf_coef", _f),
+                ("logits", _p), ("values", _p), ("cand", _p), ("cand_w", _p), ("sample_w", _p), ("returns", _p), ("rows", _p),
+                ("d_logits", _p), ("d_values", _p), ("stats", _p), ("stats_row", _p), ("flags", _p), ("scratch", _p)]
 
 
 class GennbvHipError(RuntimeError):

@@ -15,7 +15,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 OUT = os.path.join(PKG, "libgennbv_hip.so")
-SOURCES = ["voxel.hip", "gae.hip", "envstep.hip", "encoder.hip", "linear.hip", "head.hip", "chamfer.hip", "ppo.hip", "render.hip",
+SOURCES = ["voxel.hip", "gae.hip", "envstep.hip", "encoder.hip", "linear.hip", "head.hip", "chamfer.hip", "ppo.hip", "imitation.hip", "render.hip",
            "voxelize.hip", "collide.hip", "sweep.hip", "flight.hip", "flightmap.hip", "sweepmap.hip", "frontier.hip", "frontview.hip", "scan.hip", "viewgain.hip", "viewcover.hip", "covergreedy.hip",
            "tour.hip"]
 HEADERS = ["common.h", "conv_split.h", "conv_splitx.h", "backproject.h", "raytrace.h", "scene_cells.h", "voxel_frame.h", "map_bits.h", "seg_box.h", "ray_walk.h", "view_kernels.h",

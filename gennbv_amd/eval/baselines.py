@@ -184,13 +184,39 @@ def candidate_contact(env, poses: torch.Tensor, out: torch.Tensor, sweep: bool, 
 def choose(gain: torch.Tensor, weights: Sequence[int], contact: Optional[torch.Tensor] = None) -> torch.Tensor:
     """gain [N,K,3] int -> index [N] of the candidate with the largest w0 * unknown + w1 * unknown_hit (int64); candidates
     with contact[N,K] != 0 score -1; ties go to the lowest candidate index."""
-    k = gain.shape[1]
+    return choose_scored(gain, weights, contact)[0]
+
+
+def candidate_score(gain: torch.Tensor, weights: Sequence[int], contact: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The score `choose` ranks, int64 [N,K]: w0 * unknown + w1 * unknown_hit, -1 where contact[N,K] != 0 (refused)."""
     score = int(weights[0]) * gain[..., 0].to(torch.int64) + int(weights[1]) * gain[..., 1].to(torch.int64)
     if contact is not None:
         score = torch.where(contact != 0, torch.full_like(score, -1), score)
+    return score
+
+
+def choose_scored(gain: torch.Tensor, weights: Sequence[int], contact: Optional[torch.Tensor] = None):
+    """(`choose`'s index [N], the score [N,K] it ranked): what a teacher exposes to imitation (sb3/imitation.py)."""
+    k = gain.shape[1]
+    score = candidate_score(gain, weights, contact)
     # one key per candidate, strictly larger for the lower index at equal score: argmax has a single answer
     key = score * k + (k - 1 - torch.arange(k, device=score.device))
-    return key.argmax(dim=1)
+    return key.argmax(dim=1), score
+
+
+def soft_targets(score: torch.Tensor, temperature: float) -> torch.Tensor:
+    """Candidate weights fp32 [N,K] from a planner's scores int [N,K] (`last_score`; -1 = refused): over the candidates with
+    score >= 0, q_j = exp((s_j - s_max) / (temperature * max(1, s_max))), normalised over them; refused candidates get 0; a row whose
+    candidates are all refused is all zero (a dead sample of the imitation loss).  Computed in fp64 and rounded once."""
+    if not float(temperature) > 0.0:  # (a NaN fails too)
+        raise ValueError(f"soft_targets: temperature must be > 0, got {temperature}")
+    s = score.to(torch.float64)
+    ok = score >= 0
+    s_max = torch.where(ok, s, torch.full_like(s, -1.0)).amax(dim=1, keepdim=True)
+    z = (s - s_max) / (float(temperature) * s_max.clamp(min=1.0))
+    e = torch.where(ok, torch.exp(z), torch.zeros_like(s))
+    tot = e.sum(dim=1, keepdim=True)
+    return torch.where(tot > 0, e / torch.where(tot > 0, tot, torch.ones_like(tot)), torch.zeros_like(e)).to(torch.float32)
 
 
 class GreedyGainPolicy:
@@ -224,6 +250,7 @@ class GreedyGainPolicy:
         self.gain_backend = gain_backend
         self._contact = None
         self.last_gain = None
+        self.last_candidates = self.last_score = None  # the last decision's candidates int64 [N,K,6] and the score `choose` ranked [N,K]
 
     def __call__(self, obs, deterministic: bool = True):
         cfg, n, k = self.cfg, self.num_envs, self.k
@@ -245,7 +272,8 @@ class GreedyGainPolicy:
                 for j in range(k):  # one call per candidate column ([N,6] rows, stride K * 6)
                     mesh.collide(poses[:, j], self.env.collision, out=self._contact[j])
                 contact = self._contact.t()
-        best = choose(gain, self.weights, contact)
+        best, self.last_score = choose_scored(gain, self.weights, contact)
+        self.last_candidates = cand
         return cand[torch.arange(n, device=cand.device), best], None, None
 
     def _sample(self, tri: torch.Tensor) -> torch.Tensor:
@@ -305,7 +333,8 @@ class MapGreedyPolicy(GreedyGainPolicy):
         self.last_gain = gain
         if self._contact is None:
             self._contact = torch.zeros(n, self.k, dtype=torch.uint8, device=obs.device)
-        best = choose(gain, self.weights, self.contact(poses))
+        best, self.last_score = choose_scored(gain, self.weights, self.contact(poses))
+        self.last_candidates = cand
         return cand[torch.arange(n, device=cand.device), best], None, None
 
     def contact(self, poses: torch.Tensor) -> torch.Tensor:
@@ -602,6 +631,7 @@ class OracleGainPolicy:
         self.cover_backend = cover_backend
         self._contact = None
         self.last_cover = None
+        self.last_candidates = self.last_score = None  # as GreedyGainPolicy's
 
     def __call__(self, obs, deterministic: bool = True):
         n, k = self.num_envs, self.k
@@ -615,7 +645,8 @@ class OracleGainPolicy:
             if self._contact is None:
                 self._contact = torch.zeros(n, k, dtype=torch.uint8, device=obs.device)
             contact = candidate_contact(self.env, poses, self._contact, self.sweep)
-        best = choose(cover, (1, 0), contact)
+        best, self.last_score = choose_scored(cover, (1, 0), contact)
+        self.last_candidates = cand
         return cand[torch.arange(n, device=cand.device), best], None, None
 
     @property

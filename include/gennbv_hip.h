@@ -812,6 +812,50 @@ typedef struct GnbvPpoLoss {
 int gnbv_ppo_loss(const GnbvPpoLoss *args /*[host]*/, void *stream);
 int gnbv_ppo_loss_finish(const GnbvPpoLoss *args /*[host]; defer_stats == 1*/, void *stream);
 
+/* Soft-target imitation loss (gennbv_amd/sb3/imitation.py): k weighted candidate action tuples per sample -- a planner's scores over
+ * its k candidates -- against the policy's MultiCategorical heads.  ONE launch, one wave per sample.  For sample b with source row
+ * r = rows ? rows[b] : b, w_b = sample_w ? sample_w[r] : 1, candidate weights q_j = cand_w ? cand_w[r,j] : [j == 0], Q = sum_j q_j:
+ *   dead, flags |= 2 : w_b or any q_j negative or non-finite;
+ *   else dead        : w_b == 0 or Q == 0;
+ *   else dead, flags |= 1 : a candidate with q_j != 0 has an index outside [0, head_dims[h]) (a candidate of weight 0 is not judged).
+ * A dead sample gets a zero d_logits row and a zero d_values element and enters no sum.  For a live sample, per head h of n categories:
+ *   m_h[c] = (1 - label_smoothing) * sum_j (q_j / Q) [cand[r,j,h] == c] + label_smoothing / n   (added in candidate order)
+ *   lp_h = log_softmax, p_h = exp(lp_h), H_h = -sum p lp, ce_b = -sum_h sum_c m_h[c] lp_h[c]
+ *   W = sum of w_b over the live samples
+ *   loss = (1/W) sum_b w_b (ce_b - ent_coef sum_h H_h + vf_coef (v_b - R_r)^2)
+ *   d_logits[b,h,c] = (w_b/W) ((p - m) + ent_coef p (lp + H_h)),  d_values[b] = (w_b/W) 2 vf_coef (v_b - R_r)
+ * A head of one category contributes nothing (zero gradient).  values == NULL: no value term; returns == NULL: (v - R) counts as 0.
+ * stats row (8 floats, at stats[*stats_row], then *stats_row += 1) = weighted mean ce, weighted mean (v - R)^2, weighted mean
+ * sum_h H_h, agreement (share of live samples whose first arg-max equals candidate j* on every head of more than one category;
+ * j* = the first candidate of the largest weight), mean over live samples of -sum_h lp_h[cand[r,j*,h]], loss, live count, 0.
+ * W == 0: every output is zero and the row is zero.  Every element of d_logits (and d_values) is written on every call; all sums,
+ * W included, are added in one fixed order by the workgroup that finishes last, which also applies 1/W: deterministic, independent
+ * of the grid, and with `rows` bit-identical to the call on gathered arrays.  No workspace beyond `scratch`, no allocation, no host
+ * synchronisation.  Returns hipErrorInvalidValue, before any launch, for a value outside the ranges below, a NULL logits, cand,
+ * d_logits, stats, stats_row, flags or scratch, values without d_values, or values with vf_coef > 0 without returns.
+ * [host struct, device pointers] */
+typedef struct GnbvImitationLoss {
+    int batch, n_logits, n_heads; /* batch >= 1, n_heads 1..8 */
+    int head_dims[8];             /* each 1..1024, sum == n_logits */
+    int k;                        /* candidates per sample, >= 1 */
+    float label_smoothing /* [0,1) */, ent_coef /* >= 0 */, vf_coef /* >= 0 */;
+    const float *logits;          /* [B, n_logits] */
+    const float *values;          /* [B] or NULL */
+    const int64_t *cand;          /* [R, k, n_heads] */
+    const float *cand_w;          /* [R, k] or NULL: candidate 0 alone carries weight 1 */
+    const float *sample_w;        /* [R] or NULL: 1 */
+    const float *returns;         /* [R] or NULL */
+    const int64_t *rows;          /* [B] or NULL: fused gather, sample b reads source row rows[b]; NULL: row b */
+    float *d_logits;              /* out [B, n_logits] */
+    float *d_values;              /* out [B]; required iff values != NULL */
+    float *stats;                 /* [rows, 8] */
+    int64_t *stats_row;           /* in/out [1] */
+    int *flags;                   /* in/out [1], sticky: bit 0 index out of range, bit 1 bad weight */
+    float *scratch;               /* [8*B + 64], ZERO-initialised by the caller once (per-sample terms + a completion counter
+                                     that every call leaves at zero) */
+} GnbvImitationLoss;
+int gnbv_imitation_loss(const GnbvImitationLoss *args /*[host]*/, void *stream);
+
 /* C5  rollout side of MultiCategoricalDistribution (stable_baselines3/common/distributions.py:299-352 via
  *     ActorCriticPolicy.forward, policies.py:1024-1030): actions[b][h] ~ Categorical(softmax(logits_h[b])) by
  *     the inverse CDF at uniforms[b][h] in [0,1) (deterministic != 0: first arg-max = mode()), and
