@@ -33,9 +33,11 @@
 #include "../../include/gennbv_hip.h"
 #include <stdlib.h>
 #include <stdio.h>
+#include <type_traits>
 
 #include "backproject.h"
 #include "voxel_frame.h"
+#include "voxel_plan.h"  // launch constants, workspace layout and the launch plan (plain host C++)
 
 // ---------------------------------------------------------------------------
 // integer 3-D Bresenham (gennbv/utils.py:48-167).  Visit(x, y, z) is invoked for
@@ -78,8 +80,6 @@ __device__ __forceinline__ int bresenham_walk(int x0, int y0, int z0, int x1, in
 // ===========================================================================
 // fused path, launch 1: hit mask
 // ===========================================================================
-constexpr int kHitThreads = 256;
-
 // floor(num / den) for 0 <= num < 2^23, den > 0, inv_den = 1/den rounded: one mul + fix-up.
 __device__ __forceinline__ int floor_div_small(int num, int den, float inv_den)
 {
@@ -239,11 +239,7 @@ __global__ __launch_bounds__(kHitThreads) void k_hit_mask(
 // (per-ray setup is replicated over 64 lanes); thread-contiguous word ranges made
 // the mask reads uncoalesced and latency-serialised (141 us of pure overhead).
 // ===========================================================================
-constexpr int kRayThreads = 1024;
 constexpr int kRayWaves = kRayThreads / kWave;
-constexpr int kRayWordsPerLane = 8;
-constexpr int kRayChunkWords = kRayThreads * kRayWordsPerLane;
-constexpr int kQueueCap = 4096;  // targets per round (16 KiB of LDS)
 
 template <bool LDS_PATH, bool WIN = false>
 __device__ __forceinline__ void trace_ray_lane(const int (&src)[3], int lin_t, int g, int gg, uint32_t *s_path, uint32_t *pm, int w0 = 0,
@@ -412,16 +408,6 @@ __global__ __launch_bounds__(kRayThreads) void k_raycast(
 //
 // A voxel hit from pixels of two chunks is listed by both workgroups: harmless, the path is a set.
 // ===========================================================================
-#ifndef FUSED_THREADS
-#define FUSED_THREADS 1024
-#endif
-constexpr int kFusedThreads = FUSED_THREADS;
-constexpr int kListThreads = 384;    // k_ray_list: rays per work item = lanes per workgroup (four workgroups of six waves per CU: their
-                                     // 32 KiB masks are what limits the residency; 256 / 320 / 512 measured within 8 %, profiles/r05_notes.md)
-constexpr int kListGridSlices = 5;   // k_ray_list: grid = this many workgroups per env on average
-constexpr int kSlabThreads = 256;    // k_ray_slab: rays per slice
-constexpr int kListSlices = 16;      // k_ray_slab: slices per env and slab at most
-
 typedef float v4f_t __attribute__((ext_vector_type(4)));
 // streaming 16-byte load (read-once camera data: keep it out of the L2's way)
 __device__ __forceinline__ float4 ld4_stream(const float *p)
@@ -619,8 +605,7 @@ __device__ __forceinline__ void load_pixel_frame(PixelFrame &pf, const float *__
     pf.g = g; pf.gg = g * g; pf.sense_dist = sense_dist;
 }
 
-// undecided pixels of the predictor per workgroup (LDS queue); GNBV_NO_PREDICTOR builds (A/B, tests) run the canonical chain only
-constexpr int kQueueCapPx = 2048;
+// GNBV_NO_PREDICTOR builds (A/B, tests) run the canonical chain only
 #ifdef GNBV_NO_PREDICTOR
 constexpr bool kUsePredictor = false;
 #else
@@ -1438,8 +1423,6 @@ __global__ __launch_bounds__(kSlabThreads) void k_ray_slab(
 // ===========================================================================
 // fused path, launch 3: streaming grid update (A6 tail + A7 + coverage count)
 // ===========================================================================
-constexpr int kGridThreads = 256;
-
 __device__ __forceinline__ void update_voxel(float &prob, float &scan, float gt, bool hit, bool path, float &tri, int &cov)
 {
     float pr = prob;
@@ -1920,10 +1903,6 @@ static inline int grid_for(int64_t count, int block, int cap = 256 * 8)
     return (int)(b < 1 ? 1 : (b > cap ? cap : b));
 }
 
-static inline int mask_words(int g) { return (int)(((int64_t)g * g * g + 31) / 32); }
-// words rounded so that every env's mask starts 256-byte aligned
-static inline int mask_words_padded(int g) { return (mask_words(g) + 63) & ~63; }
-
 struct VoxelWorkspace {
     uint32_t *hit, *path;
     int words;
@@ -1932,11 +1911,6 @@ struct VoxelWorkspace {
     int64_t ray_cap;
 };
 
-GNBV_API size_t gnbv_voxel_workspace_bytes_hw(int n, int g, int h, int w);
-static inline size_t ray_count_ints(int n) { return ((size_t)n + 63) & ~(size_t)63; }
-// an env lists one ray per distinct voxel and chunk: never more than its pixels
-static inline int64_t ray_list_cap(int g, int h, int w) { return ((int64_t)h * w + 63) & ~(int64_t)63; }
-
 static inline VoxelWorkspace carve(void *ws, size_t ws_bytes, int n, int g, int h, int w)
 {
     VoxelWorkspace v;
@@ -1944,7 +1918,7 @@ static inline VoxelWorkspace carve(void *ws, size_t ws_bytes, int n, int g, int 
     v.hit = (uint32_t *)ws;
     v.path = v.hit + (size_t)n * v.words;
     v.ray_count = nullptr; v.ray_list = nullptr; v.ray_cap = 0;
-    if (h > 0 && w > 0 && ws_bytes >= gnbv_voxel_workspace_bytes_hw(n, g, h, w)) {
+    if (h > 0 && w > 0 && ws_bytes >= voxel_workspace_bytes_hw(n, g, h, w)) {
         v.ray_count = (int32_t *)(v.path + (size_t)n * v.words);
         v.ray_list = v.ray_count + ray_count_ints(n);
         v.ray_cap = ray_list_cap(g, h, w);
@@ -1952,24 +1926,16 @@ static inline VoxelWorkspace carve(void *ws, size_t ws_bytes, int n, int g, int 
     return v;
 }
 
-GNBV_API size_t gnbv_voxel_workspace_bytes(int n, int g)
-{
-    if (n <= 0 || g <= 0) return 0;
-    return (size_t)2 * n * mask_words_padded(g) * sizeof(uint32_t);
-}
-
-GNBV_API size_t gnbv_voxel_workspace_bytes_hw(int n, int g, int h, int w)
-{
-    if (n <= 0 || g <= 0 || h <= 0 || w <= 0) return 0;
-    return gnbv_voxel_workspace_bytes(n, g) + (ray_count_ints(n) + (size_t)n * (size_t)ray_list_cap(g, h, w)) * sizeof(int32_t);
-}
+GNBV_API size_t gnbv_voxel_workspace_bytes(int n, int g) { return voxel_workspace_bytes(n, g); }
+GNBV_API size_t gnbv_voxel_workspace_bytes_hw(int n, int g, int h, int w) { return voxel_workspace_bytes_hw(n, g, h, w); }
 
 // inv_intri is a HOST pointer to 9 floats: the matrix is a constant of the task
 // (env_train_gennbv.py:168-169) and travels to the kernels by value.
-static inline int fetch_intrinsics(const float *p, hipStream_t, Intrinsics *K)
+static inline Intrinsics fetch_intrinsics(const float *p)
 {
-    for (int i = 0; i < 9; ++i) K->k[i] = p[i];
-    return 0;
+    Intrinsics K;
+    for (int i = 0; i < 9; ++i) K.k[i] = p[i];
+    return K;
 }
 
 GNBV_API int gnbv_abi_version(void) { return GNBV_ABI_VERSION; }
@@ -1998,9 +1964,7 @@ GNBV_API int gnbv_back_projection(const float *depth, const float *seg, const fl
                                   int w, float *world, uint8_t *fg, void *stream)
 {
     GNBV_CHECK_ARG(depth && seg && c2w && inv_intri && world && fg && n > 0 && h > 0 && w > 0);
-    Intrinsics K;
-    int err = fetch_intrinsics(inv_intri, gnbv_stream(stream), &K);
-    if (err) return err;
+    const Intrinsics K = fetch_intrinsics(inv_intri);
     hipLaunchKernelGGL(k_back_projection, dim3(grid_for((int64_t)n * h * w, 256)), dim3(256), 0, gnbv_stream(stream), depth,
                        seg, c2w, K, n, h, w, world, fg);
     return gnbv_launch_status();
@@ -2046,6 +2010,11 @@ GNBV_API int gnbv_grid_tri_cls(const float *grid_prob, int64_t count, float thre
 }
 
 
+// ---------------------------------------------------------------------------
+// the voxel update: gnbv_update_occ_grid / _packed / _coded.  voxel_begin checks what the three share, carves the workspace and
+// plans the mask launches (voxel_plan.h) before anything is launched; launch_masks carries the plan out; every entry point then
+// adds its own grid update.
+// ---------------------------------------------------------------------------
 // GENNBV_VOXEL_LARGE: 1 = the large-grid kernels (k_hit_atomic + k_ray_slab) at every grid size, 0 = never (the round-1 kernels above
 // G = 104), unset = by size.  Read per call (tests switch it between calls).
 static int voxel_large_mode()
@@ -2054,176 +2023,50 @@ static int voxel_large_mode()
     return (v && (v[0] == '0' || v[0] == '1')) ? v[0] - '0' : -1;
 }
 
-// launches 1 + 2 (and the memsets): hit mask and path mask of every env into the workspace
-static int launch_masks(const float *depth_raw, const float *seg_raw, const float *c2w, const float *inv_intri,
-                        const float *poses_xyz, int64_t poses_row_stride, const float *range_gt, const float *voxel_size, int n,
-                        int h, int w, int g, float depth_sense_dist, int32_t *coverage_count, const VoxelWorkspace &ws,
-                        hipStream_t st, bool masks_are_zero = false, bool *used_lists = nullptr)
+// GENNBV_VOXEL_SLAB_PLANES=k: planes per slab of k_ray_slab, rounded up to the alignment (tests); unset or <= 0 = by size
+static int voxel_slab_planes()
 {
-    if (used_lists) *used_lists = false;
-    Intrinsics K;
-    int err = fetch_intrinsics(inv_intri, st, &K);
-    if (err) return err;
-    const int words = ws.words;
-    const size_t mask_bytes = (size_t)words * sizeof(uint32_t);
-    // LDS staging of the masks: a gfx950 workgroup may use all 160 KiB.  Larger masks (G > 104) are split into windows
-    // of <= 128 KiB, one workgroup per window.
-    const size_t kLdsMax = 160 * 1024, ray_fixed = (kQueueCap + 32) * sizeof(uint32_t);
-    const int hit_windows = mask_bytes <= kLdsMax ? 1 : (int)((mask_bytes + 128 * 1024 - 1) / (128 * 1024));
-    const int path_windows = mask_bytes + ray_fixed <= kLdsMax ? 1 : (int)((mask_bytes + 128 * 1024 - 1) / (128 * 1024));
-    const int hit_nw = (words + hit_windows - 1) / hit_windows, path_nw = (words + path_windows - 1) / path_windows;
-    const size_t hit_lds = (size_t)hit_nw * sizeof(uint32_t), path_lds = ray_fixed + (size_t)path_nw * sizeof(uint32_t);
-    // ray-cast workgroups per env: ~4 per CU in total, so that an env with many hit voxels
-    // (measured 4x the mean) is spread over several CUs (profiles/r01_notes.md)
-    int splits = (1024 + n - 1) / n;
-    splits = splits < 1 ? 1 : (splits > 8 ? 8 : splits);
-    // inv_intri of a pinhole camera is [[a,0,c],[0,b,d],[0,0,1]]: lets the kernels drop exact-zero terms
-    const bool kfast = K.k[1] == 0.0f && K.k[3] == 0.0f && K.k[6] == 0.0f && K.k[7] == 0.0f && K.k[8] == 1.0f;
-    const int env_groups = (n + 7) / 8;
-    // hit mask + ray list, then the load-balanced ray cast over the lists (needs the h/w-sized workspace)
-    const size_t list_lds = mask_bytes + 64 * sizeof(uint32_t) + (size_t)((words + 1) & ~1) * sizeof(uint16_t) + kQueueCapPx * sizeof(int32_t);
-    if (ws.ray_list != nullptr && list_lds <= kLdsMax && words <= 65536 && voxel_large_mode() != 1) {
-        // workgroups per env: two per CU in total (1024 threads each = 32 waves per CU).  (The kernel is capped at 80 SGPRs:
-        // with the 96 it wanted, the SIMD's 800-entry SGPR file held 7 waves and a second 16-wave workgroup never became
-        // resident beside the first -- 512 workgroups ran as two rounds, profiles/r02_notes.md.)
-        int fchunks = (512 + n - 1) / n;
-        fchunks = fchunks < 1 ? 1 : (fchunks > 16 ? 16 : fchunks);
-        if (used_lists) *used_lists = true;
-        // one fill: [hit (only when OR-accumulated) | path | ray counts] are adjacent for the full env range
-        if (masks_are_zero) {
-            // (the previous call's grid-update launch left masks and counts zero: GNBV_VOXEL_WS_CLEAN)
-        } else if (ws.path == ws.hit + (size_t)n * words && (void *)ws.ray_count == (void *)(ws.path + (size_t)n * words)) {
-            uint32_t *z0 = fchunks > 1 ? ws.hit : ws.path;
-            const size_t zb = (size_t)((char *)(ws.ray_count + ray_count_ints(n)) - (char *)z0);
-            if ((err = (int)hipMemsetAsync(z0, 0, zb, st))) return err;
-        } else {
-            if (fchunks > 1 && (err = (int)hipMemsetAsync(ws.hit, 0, (size_t)n * mask_bytes, st))) return err;
-            if ((err = (int)hipMemsetAsync(ws.path, 0, (size_t)n * mask_bytes, st))) return err;
-            if ((err = (int)hipMemsetAsync(ws.ray_count, 0, (size_t)n * sizeof(int32_t), st))) return err;
-        }
-        const int fgrid = env_groups * 8 * fchunks;
-#define GNBV_HITLIST(KF)                                                                                                             \
-    do {                                                                                                                             \
-        if (list_lds > 64 * 1024 &&                                                                                                  \
-            hipFuncSetAttribute((const void *)k_hit_list<KF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)list_lds) != hipSuccess) \
-            return (int)hipGetLastError();                                                                                           \
-        hipLaunchKernelGGL((k_hit_list<KF>), dim3(fgrid), dim3(kFusedThreads), list_lds, st, depth_raw, seg_raw, c2w, K, range_gt,   \
-                           voxel_size, n, h, w, g, depth_sense_dist, fchunks, words, ws.hit, ws.ray_count, ws.ray_list, ws.ray_cap,   \
-                           coverage_count);                                                                                          \
-    } while (0)
-        if (kfast) GNBV_HITLIST(true);
-        else GNBV_HITLIST(false);
-#undef GNBV_HITLIST
-        if ((err = gnbv_launch_status())) return err;
-        const size_t ray_lds = mask_bytes;
-        if (ray_lds > 64 * 1024 &&
-            hipFuncSetAttribute((const void *)k_ray_list, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ray_lds) != hipSuccess)
-            return (int)hipGetLastError();
-        // grid: kListGridSlices workgroups per env on average (an env takes as many as it has slices of kListThreads rays; 256 x 240x320 x
-        // 64^3: ~3.5); past that the workgroups take several items
-        hipLaunchKernelGGL(k_ray_list, dim3(env_groups * 8 * kListGridSlices), dim3(kListThreads), ray_lds, st, ws.ray_count, ws.ray_list,
-                           ws.ray_cap, poses_xyz, poses_row_stride, range_gt, voxel_size, n, g, words, ws.path);
-        return gnbv_launch_status();
-    }
-    // large grids (the mask does not fit a workgroup's LDS next to its lists: G > 104) with the list workspace: k_hit_atomic +
-    // k_ray_slab.  (GENNBV_VOXEL_LARGE=1 takes this path at every grid size: tests.)
-    // (GENNBV_VOXEL_LARGE=0: the round-1 kernels below; GENNBV_VOXEL_SLAB_PLANES=k: planes per slab, rounded up to the alignment -- tests.)
-    if (ws.ray_list != nullptr && voxel_large_mode() != 0) {
-        // slabs of whole x-planes whose first bit is word-aligned, <= 32 KiB of mask each where the grid allows it
-        const int64_t gg = (int64_t)g * g;
-        int align = 32;
-        while (align > 1 && (gg * (align / 2)) % 32 == 0) align /= 2;
-        int64_t per = (8192 * 32) / (gg * align);
-        int slab_planes = (int)(align * (per < 1 ? 1 : per));
-        if (const char *sp = getenv("GENNBV_VOXEL_SLAB_PLANES")) {
-            const int k = atoi(sp);
-            if (k > 0) slab_planes = ((k + align - 1) / align) * align;
-        }
-        slab_planes = slab_planes > g ? ((g + align - 1) / align) * align : slab_planes;
-        const int slabs = (g + slab_planes - 1) / slab_planes;
-        const size_t slab_lds = (size_t)((slab_planes * gg + 31) / 32) * sizeof(uint32_t);
-        if (slab_lds <= kLdsMax) {
-            if (used_lists) *used_lists = true;
-            if (masks_are_zero) {
-            } else if (ws.path == ws.hit + (size_t)n * words && (void *)ws.ray_count == (void *)(ws.path + (size_t)n * words)) {
-                const size_t zb = (size_t)((char *)(ws.ray_count + ray_count_ints(n)) - (char *)ws.hit);
-                if ((err = (int)hipMemsetAsync(ws.hit, 0, zb, st))) return err;
-            } else {
-                if ((err = (int)hipMemsetAsync(ws.hit, 0, (size_t)n * mask_bytes, st))) return err;
-                if ((err = (int)hipMemsetAsync(ws.path, 0, (size_t)n * mask_bytes, st))) return err;
-                if ((err = (int)hipMemsetAsync(ws.ray_count, 0, (size_t)n * sizeof(int32_t), st))) return err;
-            }
-            int fchunks = (512 + n - 1) / n;  // two 1024-thread workgroups per CU in total
-            fchunks = fchunks < 1 ? 1 : (fchunks > 16 ? 16 : fchunks);
-            const int fgrid = env_groups * 8 * fchunks;
-            if (kfast)
-                hipLaunchKernelGGL((k_hit_atomic<true>), dim3(fgrid), dim3(kFusedThreads), 0, st, depth_raw, seg_raw, c2w, K, range_gt, voxel_size, n, h, w, g,
-                                   depth_sense_dist, fchunks, words, ws.hit, ws.ray_count, ws.ray_list, ws.ray_cap, coverage_count);
-            else
-                hipLaunchKernelGGL((k_hit_atomic<false>), dim3(fgrid), dim3(kFusedThreads), 0, st, depth_raw, seg_raw, c2w, K, range_gt, voxel_size, n, h, w, g,
-                                   depth_sense_dist, fchunks, words, ws.hit, ws.ray_count, ws.ray_list, ws.ray_cap, coverage_count);
-            if ((err = gnbv_launch_status())) return err;
-            if (slab_lds > 64 * 1024 &&
-                hipFuncSetAttribute((const void *)k_ray_slab, hipFuncAttributeMaxDynamicSharedMemorySize, (int)slab_lds) != hipSuccess)
-                return (int)hipGetLastError();
-            int slab_slices = 32 / slabs;  // ~32 workgroups per env, at least two per slab
-            slab_slices = slab_slices < 2 ? 2 : (slab_slices > kListSlices ? kListSlices : slab_slices);
-            hipLaunchKernelGGL(k_ray_slab, dim3(env_groups * 8 * slabs * slab_slices), dim3(kSlabThreads), slab_lds, st, ws.ray_count, ws.ray_list, ws.ray_cap,
-                               poses_xyz, poses_row_stride, range_gt, voxel_size, n, g, words, slabs, slab_planes, slab_slices, ws.path);
-            return gnbv_launch_status();
-        }
-    }
-    // zero the hit masks (OR-accumulated by atomics); the path masks only when they are
-    // OR-accumulated too (several splits, or no LDS staging)
-    const bool path_needs_zero = splits > 1;  // (windows write disjoint word ranges)
-    err = (int)hipMemsetAsync(ws.hit, 0, (size_t)n * mask_bytes, st);
-    if (err) return err;
-    if (path_needs_zero) {
-        err = (int)hipMemsetAsync(ws.path, 0, (size_t)n * mask_bytes, st);  // (hit / path of an env RANGE are not adjacent)
-        if (err) return err;
-    }
-    err = (int)hipMemsetAsync(coverage_count, 0, (size_t)n * sizeof(int32_t), st);
-    if (err) return err;
-    // launch 1: hit mask.  chunks: enough workgroups to cover the chip several times.
-    int chunks = (8 * 256 + n - 1) / n;
-    chunks = chunks < 1 ? 1 : (chunks > 16 ? 16 : chunks);
-    const int hit_grid = env_groups * 8 * chunks * hit_windows;
-#define GNBV_HIT(KF, WIN)                                                                                                            \
-    do {                                                                                                                             \
-        if (hit_lds > 64 * 1024 &&                                                                                                   \
-            hipFuncSetAttribute((const void *)k_hit_mask<KF, WIN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)hit_lds) != hipSuccess) \
-            return (int)hipGetLastError();                                                                                           \
-        hipLaunchKernelGGL((k_hit_mask<KF, WIN>), dim3(hit_grid), dim3(kHitThreads), hit_lds, st, depth_raw, seg_raw, c2w, K, range_gt, \
-                           voxel_size, n, h, w, g, depth_sense_dist, chunks, words, ws.hit, hit_windows, hit_nw);                    \
-    } while (0)
-    if (hit_windows > 1) {
-        if (kfast) GNBV_HIT(true, true);
-        else GNBV_HIT(false, true);
-    } else {
-        if (kfast) GNBV_HIT(true, false);
-        else GNBV_HIT(false, false);
-    }
-#undef GNBV_HIT
-    err = gnbv_launch_status();
-    if (err) return err;
-    // launch 2: ray cast, N x splits (x windows) workgroups
-    const int ray_grid = env_groups * 8 * splits * path_windows;
-#define GNBV_RAY(WIN)                                                                                                                \
-    do {                                                                                                                             \
-        if (path_lds > 64 * 1024 &&                                                                                                  \
-            hipFuncSetAttribute((const void *)k_raycast<true, WIN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)path_lds) != hipSuccess) \
-            return (int)hipGetLastError();                                                                                           \
-        hipLaunchKernelGGL((k_raycast<true, WIN>), dim3(ray_grid), dim3(kRayThreads), path_lds, st, ws.hit, poses_xyz, poses_row_stride, \
-                           range_gt, voxel_size, n, g, words, splits, ws.path, path_windows, path_nw);                               \
-    } while (0)
-    if (path_windows > 1) {
-        GNBV_RAY(true);
-    } else {
-        GNBV_RAY(false);
-    }
-#undef GNBV_RAY
-    return gnbv_launch_status();
+    const char *v = getenv("GENNBV_VOXEL_SLAB_PLANES");
+    return v ? atoi(v) : 0;
 }
+
+// f(kFlag) with the flag as a std::bool_constant value: `decltype(kFlag)::value` is a template argument
+template <typename F>
+static int with_bool(bool flag, F &&f)
+{
+    return flag ? f(std::true_type{}) : f(std::false_type{});
+}
+
+// A launch may ask for 64 KiB of dynamic LDS without the attribute; the first launch of kKernel that asks for more raises its limit
+// to the whole 160 KiB.
+template <auto kKernel>
+static int raise_lds(size_t lds_bytes)
+{
+    static bool raised = false;
+    if (lds_bytes <= 64 * 1024 || raised) return 0;
+    if (hipFuncSetAttribute((const void *)kKernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kVoxelLdsMax) != hipSuccess)
+        return (int)hipGetLastError();
+    raised = true;
+    return 0;
+}
+
+// what the three entry points share
+struct VoxelInputs {
+    const float *depth_raw, *seg_raw, *c2w, *inv_intri, *poses_xyz;
+    int64_t poses_row_stride;
+    const float *range_gt, *voxel_size;
+    int n, h, w, g;
+    float depth_sense_dist;
+    int32_t *coverage_count;
+};
+
+struct VoxelCall {
+    hipStream_t st;
+    int64_t g3;
+    VoxelWorkspace ws;
+    VoxelMaskPlan plan;
+    bool lists() const { return plan.regime != VoxelRegime::ROUND1; }  // the ray-list kernels run: their workspace can be kept clean
+};
 
 // k_hit_mask / k_hit_list / k_hit_atomic fetch the camera rows with 16-byte requests when four consecutive pixels share an image row
 // (w % 4 == 0; rows of h * w floats then keep the base pointer's alignment): the base pointers must be 16-byte aligned there.
@@ -2233,11 +2076,107 @@ static inline bool camera_rows_aligned(const float *depth_raw, const float *seg_
     return (((uintptr_t)depth_raw | (uintptr_t)seg_raw) & 15) == 0;
 }
 
-static inline int grid_update_blocks(int64_t items, int n)
+// (launches nothing: a refused call leaves the workspace alone)
+static int voxel_begin(const VoxelInputs &in, void *workspace, size_t workspace_bytes, void *stream, VoxelCall *vc)
 {
-    int bx = (int)((items + kGridThreads - 1) / kGridThreads);
-    const int cap = (4096 + n - 1) / n;  // ~16 workgroups per CU in total, grid-stride beyond
-    return bx > cap ? cap : bx;
+    GNBV_CHECK_ARG(in.depth_raw && in.seg_raw && in.c2w && in.inv_intri && in.poses_xyz && in.range_gt && in.voxel_size);
+    GNBV_CHECK_ARG(in.coverage_count && workspace);
+    GNBV_CHECK_ARG(in.n > 0 && in.h > 0 && in.w > 0 && in.g > 1 && in.g <= 1024 && in.poses_row_stride >= 3);
+    vc->g3 = (int64_t)in.g * in.g * in.g;
+    GNBV_CHECK_ARG(vc->g3 < (1ll << 31) && (int64_t)in.h * in.w < (1ll << 31));
+    GNBV_CHECK_ARG(workspace_bytes >= voxel_workspace_bytes(in.n, in.g) && ((uintptr_t)workspace & 255) == 0);
+    GNBV_CHECK_ARG(camera_rows_aligned(in.depth_raw, in.seg_raw, in.h, in.w));
+    vc->st = gnbv_stream(stream);
+    vc->ws = carve(workspace, workspace_bytes, in.n, in.g, in.h, in.w);
+    vc->plan = voxel_mask_plan(in.n, in.g, in.h, in.w, vc->ws.ray_list != nullptr, voxel_large_mode(), voxel_slab_planes());
+    return 0;
+}
+
+// hit mask + ray list, then the load-balanced ray cast over the lists (k_hit_list's SGPR cap: see fchunks in voxel_plan.h)
+static int masks_list(const VoxelInputs &in, const Intrinsics &K, bool kfast, const VoxelCall &vc)
+{
+    const VoxelWorkspace &ws = vc.ws;
+    const VoxelMaskPlan &p = vc.plan;
+    int err = with_bool(kfast, [&](auto kFast) {
+        constexpr bool KF = decltype(kFast)::value;
+        if (const int bad = raise_lds<k_hit_list<KF>>(p.list_lds)) return bad;
+        hipLaunchKernelGGL((k_hit_list<KF>), dim3(p.hit_grid), dim3(kFusedThreads), p.list_lds, vc.st, in.depth_raw, in.seg_raw, in.c2w, K,
+                           in.range_gt, in.voxel_size, in.n, in.h, in.w, in.g, in.depth_sense_dist, p.fchunks, p.words, ws.hit, ws.ray_count,
+                           ws.ray_list, ws.ray_cap, in.coverage_count);
+        return gnbv_launch_status();
+    });
+    if (err || (err = raise_lds<k_ray_list>(p.ray_list_lds))) return err;
+    hipLaunchKernelGGL(k_ray_list, dim3(p.ray_grid), dim3(kListThreads), p.ray_list_lds, vc.st, ws.ray_count, ws.ray_list, ws.ray_cap,
+                       in.poses_xyz, in.poses_row_stride, in.range_gt, in.voxel_size, in.n, in.g, p.words, ws.path);
+    return gnbv_launch_status();
+}
+
+// large grids: hit bits by global atomics + ray list, then the ray cast slab by slab
+static int masks_large(const VoxelInputs &in, const Intrinsics &K, bool kfast, const VoxelCall &vc)
+{
+    const VoxelWorkspace &ws = vc.ws;
+    const VoxelMaskPlan &p = vc.plan;
+    int err = with_bool(kfast, [&](auto kFast) {
+        hipLaunchKernelGGL((k_hit_atomic<decltype(kFast)::value>), dim3(p.hit_grid), dim3(kFusedThreads), 0, vc.st, in.depth_raw, in.seg_raw,
+                           in.c2w, K, in.range_gt, in.voxel_size, in.n, in.h, in.w, in.g, in.depth_sense_dist, p.fchunks, p.words, ws.hit,
+                           ws.ray_count, ws.ray_list, ws.ray_cap, in.coverage_count);
+        return gnbv_launch_status();
+    });
+    if (err || (err = raise_lds<k_ray_slab>(p.slab_lds))) return err;
+    hipLaunchKernelGGL(k_ray_slab, dim3(p.ray_grid), dim3(kSlabThreads), p.slab_lds, vc.st, ws.ray_count, ws.ray_list, ws.ray_cap,
+                       in.poses_xyz, in.poses_row_stride, in.range_gt, in.voxel_size, in.n, in.g, p.words, p.slabs, p.slab_planes,
+                       p.slab_slices, ws.path);
+    return gnbv_launch_status();
+}
+
+// round 1: hit mask in LDS (windowed above 160 KiB), then the ray cast from the set bits of the hit mask
+static int masks_round1(const VoxelInputs &in, const Intrinsics &K, bool kfast, const VoxelCall &vc)
+{
+    const VoxelWorkspace &ws = vc.ws;
+    const VoxelMaskPlan &p = vc.plan;
+    int err = with_bool(p.hit_windows > 1, [&](auto kWin) {
+        return with_bool(kfast, [&](auto kFast) {
+            constexpr bool KF = decltype(kFast)::value, WIN = decltype(kWin)::value;
+            if (const int bad = raise_lds<k_hit_mask<KF, WIN>>(p.hit_lds)) return bad;
+            hipLaunchKernelGGL((k_hit_mask<KF, WIN>), dim3(p.hit_grid), dim3(kHitThreads), p.hit_lds, vc.st, in.depth_raw, in.seg_raw, in.c2w,
+                               K, in.range_gt, in.voxel_size, in.n, in.h, in.w, in.g, in.depth_sense_dist, p.chunks, p.words, ws.hit,
+                               p.hit_windows, p.hit_nw);
+            return gnbv_launch_status();
+        });
+    });
+    if (err) return err;
+    return with_bool(p.path_windows > 1, [&](auto kWin) {
+        constexpr bool WIN = decltype(kWin)::value;
+        if (const int bad = raise_lds<k_raycast<true, WIN>>(p.path_lds)) return bad;
+        hipLaunchKernelGGL((k_raycast<true, WIN>), dim3(p.ray_grid), dim3(kRayThreads), p.path_lds, vc.st, ws.hit, in.poses_xyz,
+                           in.poses_row_stride, in.range_gt, in.voxel_size, in.n, in.g, p.words, p.splits, ws.path, p.path_windows, p.path_nw);
+        return gnbv_launch_status();
+    });
+}
+
+// the fills in front of the mask launches.  masks_are_zero: the previous call's grid-update launch left masks and counts zero
+// (GNBV_VOXEL_WS_CLEAN); the round-1 kernels zero what they need themselves
+static int zero_for_masks(const VoxelInputs &in, const VoxelCall &vc, bool masks_are_zero)
+{
+    const VoxelMaskPlan &p = vc.plan;
+    int err;
+    if (!(masks_are_zero && vc.lists()) && (err = (int)hipMemsetAsync((char *)vc.ws.hit + p.zero_offset, 0, p.zero_bytes, vc.st))) return err;
+    if (p.zero_coverage && (err = (int)hipMemsetAsync(in.coverage_count, 0, (size_t)in.n * sizeof(int32_t), vc.st))) return err;
+    return 0;
+}
+
+// launches 1 + 2 (and the memsets): hit mask and path mask of every env into the workspace
+static int launch_masks(const VoxelInputs &in, const VoxelCall &vc, bool masks_are_zero = false)
+{
+    const Intrinsics K = fetch_intrinsics(in.inv_intri);
+    // inv_intri of a pinhole camera is [[a,0,c],[0,b,d],[0,0,1]]: lets the kernels drop exact-zero terms
+    const bool kfast = K.k[1] == 0.0f && K.k[3] == 0.0f && K.k[6] == 0.0f && K.k[7] == 0.0f && K.k[8] == 1.0f;
+    if (const int err = zero_for_masks(in, vc, masks_are_zero)) return err;
+    switch (vc.plan.regime) {
+    case VoxelRegime::LIST: return masks_list(in, K, kfast, vc);
+    case VoxelRegime::LARGE: return masks_large(in, K, kfast, vc);
+    default: return masks_round1(in, K, kfast, vc);
+    }
 }
 
 GNBV_API int gnbv_update_occ_grid(const float *depth_raw, const float *seg_raw, const float *c2w, const float *inv_intri,
@@ -2247,31 +2186,21 @@ GNBV_API int gnbv_update_occ_grid(const float *depth_raw, const float *seg_raw, 
                                   float *tri_out, int64_t tri_row_stride, int32_t *coverage_count, void *workspace,
                                   size_t workspace_bytes, void *stream)
 {
-    GNBV_CHECK_ARG(depth_raw && seg_raw && c2w && inv_intri && poses_xyz && range_gt && voxel_size && grid_gt);
-    GNBV_CHECK_ARG(prob_grid && scanned_gt_grid && tri_out && coverage_count && workspace);
-    GNBV_CHECK_ARG(n > 0 && h > 0 && w > 0 && g > 1 && g <= 1024 && poses_row_stride >= 3);
-    const int64_t g3 = (int64_t)g * g * g;
-    GNBV_CHECK_ARG(g3 < (1ll << 31) && tri_row_stride >= g3 && (int64_t)h * w < (1ll << 31));
-    GNBV_CHECK_ARG(workspace_bytes >= gnbv_voxel_workspace_bytes(n, g) && ((uintptr_t)workspace & 255) == 0);
-    GNBV_CHECK_ARG(camera_rows_aligned(depth_raw, seg_raw, h, w));
-    hipStream_t st = gnbv_stream(stream);
-    VoxelWorkspace ws = carve(workspace, workspace_bytes, n, g, h, w);
-    int err = launch_masks(depth_raw, seg_raw, c2w, inv_intri, poses_xyz, poses_row_stride, range_gt, voxel_size, n, h, w, g,
-                           depth_sense_dist, coverage_count, ws, st);
+    const VoxelInputs in = {depth_raw, seg_raw, c2w, inv_intri, poses_xyz, poses_row_stride, range_gt, voxel_size, n, h, w, g,
+                            depth_sense_dist, coverage_count};
+    VoxelCall vc;
+    int err = voxel_begin(in, workspace, workspace_bytes, stream, &vc);
     if (err) return err;
+    GNBV_CHECK_ARG(grid_gt && prob_grid && scanned_gt_grid && tri_out && tri_row_stride >= vc.g3);
+    if ((err = launch_masks(in, vc))) return err;
     // launch 3: grid update
-    const bool vec4 = (g3 % 4 == 0) && (tri_row_stride % 4 == 0) && (((uintptr_t)tri_out & 15) == 0) &&
-                      (((uintptr_t)prob_grid & 15) == 0) && (((uintptr_t)scanned_gt_grid & 15) == 0) &&
-                      (((uintptr_t)grid_gt & 15) == 0);
-    const int bx = grid_update_blocks(vec4 ? g3 / 4 : g3, n);
-    if (vec4)
-        hipLaunchKernelGGL(k_grid_update<true>, dim3(bx, n), dim3(kGridThreads), 0, st, ws.hit, ws.path, grid_gt, reset_mask,
-                           n, (int)g3, ws.words, prob_grid, scanned_gt_grid, tri_out, tri_row_stride, coverage_count);
-    else
-        hipLaunchKernelGGL(k_grid_update<false>, dim3(bx, n), dim3(kGridThreads), 0, st, ws.hit, ws.path, grid_gt,
-                           reset_mask, n, (int)g3, ws.words, prob_grid, scanned_gt_grid, tri_out, tri_row_stride,
-                           coverage_count);
-    return gnbv_launch_status();
+    const bool vec4 = grid_update_vec4(vc.g3, tri_row_stride, (uintptr_t)tri_out | (uintptr_t)prob_grid | (uintptr_t)scanned_gt_grid | (uintptr_t)grid_gt);
+    const int bx = grid_update_blocks(vec4 ? vc.g3 / 4 : vc.g3, n);
+    return with_bool(vec4, [&](auto kVec4) {
+        hipLaunchKernelGGL(k_grid_update<decltype(kVec4)::value>, dim3(bx, n), dim3(kGridThreads), 0, vc.st, vc.ws.hit, vc.ws.path, grid_gt,
+                           reset_mask, n, (int)vc.g3, vc.ws.words, prob_grid, scanned_gt_grid, tri_out, tri_row_stride, coverage_count);
+        return gnbv_launch_status();
+    });
 }
 
 GNBV_API int gnbv_grid_bit_words(int g) { return g > 0 ? mask_words_padded(g) : 0; }
@@ -2300,40 +2229,6 @@ GNBV_API int gnbv_unpack_grid_bits(const uint32_t *bits, int n, int g, float *gr
     return gnbv_launch_status();
 }
 
-// one chain (hit mask -> ray cast -> grid update) over the env range [e0, e0 + n) of the batch
-static int update_packed_range(const float *depth_raw, const float *seg_raw, const float *c2w, const float *inv_intri,
-                               const float *poses_xyz, int64_t poses_row_stride, const float *range_gt, const float *voxel_size,
-                               const uint32_t *gt_bits, const uint8_t *reset_mask, int e0, int n, int h, int w, int g,
-                               float depth_sense_dist, float *prob_grid, uint32_t *scanned_bits, float *tri_out,
-                               int64_t tri_row_stride, int32_t *coverage_count, const VoxelWorkspace &full, hipStream_t st)
-{
-    const int64_t g3 = (int64_t)g * g * g, hw = (int64_t)h * w;
-    VoxelWorkspace ws = full;
-    ws.hit = full.hit + (size_t)e0 * full.words;
-    ws.path = full.path + (size_t)e0 * full.words;
-    if (full.ray_list) { ws.ray_count = full.ray_count + e0; ws.ray_list = full.ray_list + (size_t)e0 * full.ray_cap; }
-    depth_raw += e0 * hw; seg_raw += e0 * hw; c2w += (size_t)e0 * 16; poses_xyz += (size_t)e0 * poses_row_stride;
-    range_gt += (size_t)e0 * 6; voxel_size += (size_t)e0 * 3; gt_bits += (size_t)e0 * full.words;
-    if (reset_mask) reset_mask += e0;
-    prob_grid += (size_t)e0 * g3; scanned_bits += (size_t)e0 * full.words; tri_out += (size_t)e0 * tri_row_stride;
-    coverage_count += e0;
-    int err = launch_masks(depth_raw, seg_raw, c2w, inv_intri, poses_xyz, poses_row_stride, range_gt, voxel_size, n, h, w, g,
-                           depth_sense_dist, coverage_count, ws, st);
-    if (err) return err;
-    const bool vec4 = (g3 % 4 == 0) && (tri_row_stride % 4 == 0) && (((uintptr_t)tri_out & 15) == 0) &&
-                      (((uintptr_t)prob_grid & 15) == 0);
-    const int bx = grid_update_blocks(vec4 ? g3 / 4 : g3, n);
-    if (vec4)
-        hipLaunchKernelGGL(k_grid_update_packed<true>, dim3(bx, n), dim3(kGridThreads), 0, st, ws.hit, ws.path, gt_bits,
-                           reset_mask, n, (int)g3, ws.words, ws.words, prob_grid, scanned_bits, tri_out, tri_row_stride,
-                           coverage_count);
-    else
-        hipLaunchKernelGGL(k_grid_update_packed<false>, dim3(bx, n), dim3(kGridThreads), 0, st, ws.hit, ws.path, gt_bits,
-                           reset_mask, n, (int)g3, ws.words, ws.words, prob_grid, scanned_bits, tri_out, tri_row_stride,
-                           coverage_count);
-    return gnbv_launch_status();
-}
-
 GNBV_API int gnbv_update_occ_grid_packed(const float *depth_raw, const float *seg_raw, const float *c2w, const float *inv_intri,
                                          const float *poses_xyz, int64_t poses_row_stride, const float *range_gt,
                                          const float *voxel_size, const uint32_t *gt_bits, const uint8_t *reset_mask, int n,
@@ -2341,17 +2236,21 @@ GNBV_API int gnbv_update_occ_grid_packed(const float *depth_raw, const float *se
                                          float *tri_out, int64_t tri_row_stride, int32_t *coverage_count, void *workspace,
                                          size_t workspace_bytes, void *stream)
 {
-    GNBV_CHECK_ARG(depth_raw && seg_raw && c2w && inv_intri && poses_xyz && range_gt && voxel_size && gt_bits);
-    GNBV_CHECK_ARG(prob_grid && scanned_bits && tri_out && coverage_count && workspace);
-    GNBV_CHECK_ARG(n > 0 && h > 0 && w > 0 && g > 1 && g <= 1024 && poses_row_stride >= 3);
-    const int64_t g3 = (int64_t)g * g * g;
-    GNBV_CHECK_ARG(g3 < (1ll << 31) && tri_row_stride >= g3 && (int64_t)h * w < (1ll << 31));
-    GNBV_CHECK_ARG(workspace_bytes >= gnbv_voxel_workspace_bytes(n, g) && ((uintptr_t)workspace & 255) == 0);
-    GNBV_CHECK_ARG(camera_rows_aligned(depth_raw, seg_raw, h, w));
-    hipStream_t st = gnbv_stream(stream);
-    VoxelWorkspace ws = carve(workspace, workspace_bytes, n, g, h, w);
-    return update_packed_range(depth_raw, seg_raw, c2w, inv_intri, poses_xyz, poses_row_stride, range_gt, voxel_size, gt_bits, reset_mask, 0,
-                               n, h, w, g, depth_sense_dist, prob_grid, scanned_bits, tri_out, tri_row_stride, coverage_count, ws, st);
+    const VoxelInputs in = {depth_raw, seg_raw, c2w, inv_intri, poses_xyz, poses_row_stride, range_gt, voxel_size, n, h, w, g,
+                            depth_sense_dist, coverage_count};
+    VoxelCall vc;
+    int err = voxel_begin(in, workspace, workspace_bytes, stream, &vc);
+    if (err) return err;
+    GNBV_CHECK_ARG(gt_bits && prob_grid && scanned_bits && tri_out && tri_row_stride >= vc.g3);
+    if ((err = launch_masks(in, vc))) return err;
+    const bool vec4 = grid_update_vec4(vc.g3, tri_row_stride, (uintptr_t)tri_out | (uintptr_t)prob_grid);
+    const int bx = grid_update_blocks(vec4 ? vc.g3 / 4 : vc.g3, n);
+    return with_bool(vec4, [&](auto kVec4) {
+        hipLaunchKernelGGL(k_grid_update_packed<decltype(kVec4)::value>, dim3(bx, n), dim3(kGridThreads), 0, vc.st, vc.ws.hit, vc.ws.path,
+                           gt_bits, reset_mask, n, (int)vc.g3, vc.ws.words, vc.ws.words, prob_grid, scanned_bits, tri_out, tri_row_stride,
+                           coverage_count);
+        return gnbv_launch_status();
+    });
 }
 
 // host helper: the two 256-entry tables of the coded probability grid, by the exact fp32 iteration of the reference
@@ -2385,32 +2284,23 @@ GNBV_API int gnbv_update_occ_grid_coded(const float *depth_raw, const float *seg
                                         int64_t tri_i8_row_stride, int32_t *coverage_count, int32_t *overflow, void *workspace,
                                         size_t workspace_bytes, int workspace_flags, void *stream)
 {
-    GNBV_CHECK_ARG(depth_raw && seg_raw && c2w && inv_intri && poses_xyz && range_gt && voxel_size && gt_bits);
-    GNBV_CHECK_ARG(prob_code && tri_lut && scanned_bits && (tri_out || tri_i8) && coverage_count && workspace);
-    GNBV_CHECK_ARG(n > 0 && h > 0 && w > 0 && g > 1 && g <= 1024 && poses_row_stride >= 3);
-    const int64_t g3 = (int64_t)g * g * g;
-    GNBV_CHECK_ARG(g3 < (1ll << 31) && (tri_out == nullptr || tri_row_stride >= g3) && (int64_t)h * w < (1ll << 31));
-    GNBV_CHECK_ARG(workspace_bytes >= gnbv_voxel_workspace_bytes(n, g) && ((uintptr_t)workspace & 255) == 0);
-    GNBV_CHECK_ARG(camera_rows_aligned(depth_raw, seg_raw, h, w));
-    GNBV_CHECK_ARG(tri_i8 == nullptr || tri_i8_row_stride >= g3);  // (before any launch: a refused call leaves the workspace alone)
-    hipStream_t st = gnbv_stream(stream);
-    VoxelWorkspace ws = carve(workspace, workspace_bytes, n, g, h, w);
-    const bool clean = (workspace_flags & GNBV_VOXEL_WS_CLEAN) != 0;
-    bool lists = false;
-    int err = launch_masks(depth_raw, seg_raw, c2w, inv_intri, poses_xyz, poses_row_stride, range_gt, voxel_size, n, h, w, g,
-                           depth_sense_dist, coverage_count, ws, st, clean, &lists);
+    const VoxelInputs in = {depth_raw, seg_raw, c2w, inv_intri, poses_xyz, poses_row_stride, range_gt, voxel_size, n, h, w, g,
+                            depth_sense_dist, coverage_count};
+    VoxelCall vc;
+    int err = voxel_begin(in, workspace, workspace_bytes, stream, &vc);
     if (err) return err;
-    const int leave_clean = (clean && lists) ? 1 : 0;  // (the two-launch mask kernels zero what they need themselves)
-    const bool vec4 = (g3 % 4 == 0) && (tri_out == nullptr || ((tri_row_stride % 4 == 0) && (((uintptr_t)tri_out & 15) == 0))) &&
-                      (((uintptr_t)prob_code & 3) == 0) && (tri_i8 == nullptr || ((((uintptr_t)tri_i8 | (uintptr_t)tri_i8_row_stride) & 3) == 0));
-    const bool vec16 = tri_out == nullptr && (g3 % 16 == 0) && (((uintptr_t)prob_code & 15) == 0) &&
-                       ((((uintptr_t)tri_i8 | (uintptr_t)tri_i8_row_stride) & 15) == 0);
-    const int vpl = vec16 ? 16 : vec4 ? 4 : 1;
+    const int64_t g3 = vc.g3;
+    GNBV_CHECK_ARG(gt_bits && prob_code && tri_lut && scanned_bits && (tri_out || tri_i8));
+    GNBV_CHECK_ARG((tri_out == nullptr || tri_row_stride >= g3) && (tri_i8 == nullptr || tri_i8_row_stride >= g3));
+    const bool clean = (workspace_flags & GNBV_VOXEL_WS_CLEAN) != 0;
+    if ((err = launch_masks(in, vc, clean))) return err;
+    const int leave_clean = (clean && vc.lists()) ? 1 : 0;  // (the two-launch mask kernels zero what they need themselves)
+    const int vpl = grid_update_vpl(g3, (uintptr_t)prob_code, (uintptr_t)tri_out, tri_row_stride, (uintptr_t)tri_i8, tri_i8_row_stride);
     const int bx = grid_update_blocks(g3 / vpl, n);
 #define GNBV_LAUNCH_CODED(V)                                                                                                          \
-    hipLaunchKernelGGL(k_grid_update_coded<V>, dim3(bx, n), dim3(kGridThreads), 0, st, ws.hit, ws.path, leave_clean, ws.ray_count, gt_bits, reset_mask, n, (int)g3, \
-                       ws.words, ws.words, prob_code, tri_lut, scanned_bits, tri_out, tri_row_stride, tri_i8, tri_i8_row_stride,        \
-                       coverage_count, overflow)
+    hipLaunchKernelGGL(k_grid_update_coded<V>, dim3(bx, n), dim3(kGridThreads), 0, vc.st, vc.ws.hit, vc.ws.path, leave_clean, vc.ws.ray_count, \
+                       gt_bits, reset_mask, n, (int)g3, vc.ws.words, vc.ws.words, prob_code, tri_lut, scanned_bits, tri_out, tri_row_stride,  \
+                       tri_i8, tri_i8_row_stride, coverage_count, overflow)
     if (vpl == 16) GNBV_LAUNCH_CODED(16);
     else if (vpl == 4) GNBV_LAUNCH_CODED(4);
     else GNBV_LAUNCH_CODED(1);

@@ -1,10 +1,11 @@
 """Shared by tests/test_voxel_abi_gpu.py and tests/test_voxel_abi_regimes_cpu.py: frames whose geometry differs per env, the
-launch geometry of csrc/voxel.hip restated from its comments and constants, the CPU oracle run over a case, and device buffers the
+launch geometry of csrc/voxel.hip and csrc/voxel_plan.h restated from their comments and constants, the CPU oracle run over a case, and device buffers the
 test places itself (base, byte offset and row stride chosen by the test, the bytes around the rows filled with a sentinel).
 
 Nothing here touches the GPU at import; only `Rows` and `VoxelCall` do."""
 import ctypes as C
 import functools
+import math
 from types import SimpleNamespace
 
 import numpy as np
@@ -26,6 +27,7 @@ K_RAY_CHUNK_WORDS = 8192    # kRayChunkWords: mask words per k_raycast super-chu
 K_LIST_THREADS = 384        # kListThreads: rays per k_ray_list item
 K_LIST_GRID_SLICES = 5      # kListGridSlices: k_ray_list workgroups per env on average
 K_QUEUE_CAP_PX = 2048       # kQueueCapPx
+K_LIST_SLICES = 16          # kListSlices: k_ray_slab slices per env and slab at most
 K_WAVE = 64
 LDS_MAX = 160 * 1024
 GRID_STRIDE_THREADS = 2048 * 256  # grid_for(): at most 2048 blocks of 256 threads, grid-stride beyond
@@ -46,18 +48,32 @@ def chunk_ranges(hw, chunks):
     return [(c * ppc, min(hw, c * ppc + ppc)) for c in range(chunks)]
 
 
-def dispatch(n, g, h, w, full_ws, large=None):
+def slab_geometry(g, planes=0):
+    """k_ray_slab: a slab is a run of whole x-planes of the path mask that starts on a word boundary and, where the grid allows it,
+    holds at most 32 KiB of mask.  planes: GENNBV_VOXEL_SLAB_PLANES (0: by size), rounded up to the alignment."""
+    gg = g * g
+    align = 32 // math.gcd(gg, 32)                         # fewest planes whose bits fill whole words
+    per = align * max(1, (32 * 1024 * 8) // (gg * align))  # aligned groups in 32 KiB, at least one
+    if planes > 0:
+        per = -(-planes // align) * align
+    per = min(per, -(-g // align) * align)                 # (never more than the grid, rounded up to the alignment)
+    slabs = -(-g // per)
+    return SimpleNamespace(align=align, planes=per, slabs=slabs, lds=-(-per * gg // 32) * 4,
+                           slices=_clamp(32 // slabs, 2, K_LIST_SLICES))  # ~32 workgroups per env, at least two per slab
+
+
+def dispatch(n, g, h, w, full_ws, large=None, slab_planes=0):
     """Which kernels a call launches and with which geometry.  full_ws: the workspace has the h*w-sized ray lists;
-    large: GENNBV_VOXEL_LARGE ("0", "1" or None)."""
+    large: GENNBV_VOXEL_LARGE ("0", "1" or None); slab_planes: GENNBV_VOXEL_SLAB_PLANES."""
     words = mask_words(g)
     d = SimpleNamespace(n=n, g=g, words=words, env_groups=(n + 7) // 8)
     list_lds = words * 4 + 64 * 4 + ((words + 1) & ~1) * 2 + K_QUEUE_CAP_PX * 4
     if full_ws and list_lds <= LDS_MAX and words <= 65536 and large != "1":
         d.path = "list"       # k_hit_list + k_ray_list
-    elif full_ws and large != "0":
+    elif full_ws and large != "0" and slab_geometry(g, slab_planes).lds <= LDS_MAX:
         d.path = "large"      # k_hit_atomic + k_ray_slab
     else:
-        d.path = "round1"     # k_hit_mask + k_raycast
+        d.path = "round1"     # k_hit_mask + k_raycast (also where no slab fits a workgroup's LDS)
     d.fchunks = _clamp(-(-512 // n), 1, 16)      # k_hit_list / k_hit_atomic workgroups per env
     d.chunks = _clamp(-(-2048 // n), 1, 16)      # k_hit_mask workgroups per env
     d.splits = _clamp(-(-1024 // n), 1, 8)       # k_raycast workgroups per env
