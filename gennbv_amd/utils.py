@@ -78,10 +78,12 @@ def points_to_idx(world: torch.Tensor, fg: torch.Tensor, range_gt: torch.Tensor,
     lib = _lib.load()
     world = world.contiguous().float()
     fg8 = fg.to(torch.uint8).contiguous()
+    # (held in names until the launch is enqueued: a converted copy that dies right after .data_ptr() gives its block back to the
+    # allocator, and the next conversion may take and overwrite it before the kernel runs)
+    rg, vs = range_gt.contiguous().float(), voxel_size_gt.contiguous().float()
     n, p = world.shape[0], world.shape[1]
     idx = torch.empty((n, p, 3), dtype=torch.int32, device=world.device)
-    _lib.check(lib.gnbv_points_to_idx(world.data_ptr(), fg8.data_ptr(), range_gt.contiguous().float().data_ptr(),
-                                      voxel_size_gt.contiguous().float().data_ptr(), n, p, int(map_size),
+    _lib.check(lib.gnbv_points_to_idx(world.data_ptr(), fg8.data_ptr(), rg.data_ptr(), vs.data_ptr(), n, p, int(map_size),
                                       idx.data_ptr(), _st(world)), "gnbv_points_to_idx")
     return idx
 
@@ -98,7 +100,7 @@ def scanned_pts_to_idx_3D(pts_target: Sequence[torch.Tensor], range_gt: torch.Te
             out.append([])
             continue
         ones = torch.ones(1, pts.shape[0], dtype=torch.uint8, device=pts.device)
-        idx = points_to_idx(pts.view(1, -1, 3), ones, range_gt[env_idx:env_idx + 1], voxel_size_gt[env_idx:env_idx + 1], g)[0]
+        idx = points_to_idx(pts.reshape(1, -1, 3), ones, range_gt[env_idx:env_idx + 1], voxel_size_gt[env_idx:env_idx + 1], g)[0]
         keep = idx[:, 0] >= 0
         if not bool(keep.any()):
             out.append([])
@@ -115,10 +117,9 @@ def pose_coord_to_idx_3D(poses: torch.Tensor, range_gt: torch.Tensor, voxel_size
     assert poses.shape[1] == 3, f"Invalid poses shape: {poses.shape}"
     _lib.require_cuda(poses, range_gt, voxel_size_gt)
     lib = _lib.load()
-    p = poses.contiguous().float()
+    p, rg, vs = poses.contiguous().float(), range_gt.contiguous().float(), voxel_size_gt.contiguous().float()
     out = torch.empty((p.shape[0], 3), dtype=torch.int64, device=p.device)
-    _lib.check(lib.gnbv_pose_to_idx(p.data_ptr(), range_gt.contiguous().float().data_ptr(),
-                                    voxel_size_gt.contiguous().float().data_ptr(), p.shape[0], out.data_ptr(), _st(p)),
+    _lib.check(lib.gnbv_pose_to_idx(p.data_ptr(), rg.data_ptr(), vs.data_ptr(), p.shape[0], out.data_ptr(), _st(p)),
                "gnbv_pose_to_idx")
     if if_col:
         out[(out < 0).any(dim=-1)] = -1
@@ -180,7 +181,8 @@ def back_projection_fg(depth_processed: torch.Tensor, seg_processed: torch.Tenso
     ki = inv_intri.detach().to("cpu", torch.float32).contiguous()  # [host] 9 floats
     world = torch.empty((n, h * w, 3), dtype=torch.float32, device=d.device)
     fg = torch.empty((n, h * w), dtype=torch.uint8, device=d.device)
-    _lib.check(lib.gnbv_back_projection(d.data_ptr(), s.data_ptr(), c2w.contiguous().float().data_ptr(), ki.data_ptr(),
+    m = c2w.contiguous().float()
+    _lib.check(lib.gnbv_back_projection(d.data_ptr(), s.data_ptr(), m.data_ptr(), ki.data_ptr(),
                                         n, h, w, world.data_ptr(), fg.data_ptr(), _st(d)), "gnbv_back_projection")
     fgb = fg.bool()
     pts = [world[i][fgb[i]] for i in range(n)]
