@@ -121,5 +121,19 @@ __device__ __forceinline__ long long wave_max_all(long long v)
     return v;
 }
 
+// ---- host: a launch may ask for 64 KiB of dynamic LDS without the attribute; the first launch of kKernel that asks for more raises
+// its limit to `limit` bytes (once per process and kernel).  Keyed on the kernel itself, not on its type: the instantiations of a
+// kernel template may share one function type.
+template <auto kKernel>
+int gnbv_raise_lds(size_t lds_bytes, int limit)
+{
+    static bool raised = false;
+    if (lds_bytes <= 64 * 1024 || raised) return 0;
+    if (hipFuncSetAttribute((const void *)kKernel, hipFuncAttributeMaxDynamicSharedMemorySize, limit) != hipSuccess)
+        return (int)hipGetLastError();
+    raised = true;
+    return 0;
+}
+
 // ---- host: workspace carving
 static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }

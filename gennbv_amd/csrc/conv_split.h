@@ -36,7 +36,7 @@ typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 namespace split {
 constexpr int kThreads = 1024, kWaves = 16;          // waves 0-7 compute (output plane = wave / 2, half of the k-steps each), waves 8-15 stage
 constexpr int kConsWaves = 8, kProdThreads = 512;
-constexpr int kNP = 4, kNPl = 2 * kNP + 1;           // output planes per workgroup / input planes they read
+constexpr int kNPl = 2 * kNP + 1;                    // input planes the kNP (encoder_plan.h) output planes of a workgroup read
 constexpr int kRing = 5;                             // input rows resident per plane: 3 being read + 2 being written
 constexpr int kRowBytes = 2048;                      // one input row: [x parity 2][hi | lo][16 voxels][16 channels] f16
 constexpr int kStageBytes = kNPl * kRing * kRowBytes;
@@ -830,8 +830,7 @@ __global__ __launch_bounds__(split::kThreads) void k_conv2_wgrad_split_dma(
 //       channel sums, and the conv1 weight-gradient contraction T1 += x^T g with the input slab (f16, de-interleaved by x mod 4;
 //       requested one step ahead).
 // ---------------------------------------------------------------------------
-namespace dsplit {
-constexpr int kPairs = 4;
+namespace dsplit {  // (kPairs: encoder_plan.h)
 constexpr int kYVox = 80, kYHalf = 16 * kYVox, kYRow = 2 * kYHalf, kYBuf = 2 * 2 * kPairs * kYRow;  // 40 960 per step buffer
 constexpr int kDyHalf = 18 * 32, kDyRow = 2 * kDyHalf, kDyPlanes = kPairs + 1, kDyRing = 3;
 constexpr int kDyBytes = kDyPlanes * kDyRing * kDyRow;

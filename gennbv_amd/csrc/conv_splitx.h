@@ -47,7 +47,6 @@ __device__ __forceinline__ bool item_of(int B, int O2, int XT, int item, int &b,
     oz1 = min(O2, oz0 + kNP);
     return b < B;
 }
-static inline int items(int B, int O2, int XT) { return ((B + 7) / 8) * 8 * ((O2 + kNP - 1) / kNP) * XT; }
 
 // The staging role: one of 512 threads that move the step's 18 new input rows (windows of 33 voxels) through registers into the ring as
 // f16 hi | lo planes of z1 = 2^8 relu(bn1(y1)).  Requests are unconditional (clamped into the sample and the row); a thread whose piece
@@ -402,7 +401,6 @@ __device__ __forceinline__ bool item_of(int B, int NA, int XT, int item, int &b,
     a1 = min(NA, a0 + kPairs);
     return b < B;
 }
-static inline int items(int B, int NA, int XT) { return ((B + 7) / 8) * 8 * ((NA + kPairs - 1) / kPairs) * XT; }
 }  // namespace dsplitx
 
 template <bool LOOP>

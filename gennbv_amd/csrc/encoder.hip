@@ -24,13 +24,11 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "encoder_plan.h"
 #include "../../include/gennbv_hip.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-constexpr int kC = 16;          // channels of both conv layers
-constexpr int kTaps = 27;
-constexpr int kEncThreads = 256;
-constexpr int kEncWaves = kEncThreads / kWave;
+static_assert(kEncWaves * kWave == kEncThreads, "encoder_plan.h counts waves of 64 lanes");
 
 // Layer-1 activations (y1, dz1') are channels-last AND split by x-parity:
 //   voxel (b, z, y, x) -> (((b*O1 + z)*O1 + y)*2 + (x & 1))*XH + (x >> 1)      XH = ceil(O1 / 2)
@@ -45,7 +43,6 @@ __device__ __forceinline__ uint32_t vox1(int b, int z, int y, int x, int O1)
     const uint32_t XH = (uint32_t)(O1 + 1) >> 1;
     return ((((uint32_t)b * O1 + z) * O1 + y) * 2 + (x & 1)) * XH + ((uint32_t)x >> 1);
 }
-static inline size_t y1_elems(int batch, int O1) { return (size_t)batch * O1 * O1 * 2 * ((O1 + 1) / 2) * kC; }
 
 // Storage type of the layer-1 activations (y1, dz1'): fp32.  (The kernels keep the storage policy as a template parameter; the bf16
 // storage mode of rounds 1-3 was removed in round 4: slower than fp32 on the split kernels and 1e-3-class loss deltas)
@@ -76,7 +73,6 @@ __device__ __forceinline__ bool sample_plane(int B, int O, int &b, int &o)
     b = (slot / O) * 8 + xcd;
     return b < B;
 }
-static inline int sample_plane_grid(int B, int O) { return ((B + 7) / 8) * 8 * O; }
 
 // BN partial sums: one row of 32 floats per WORKGROUP, part[block][0][c] = sum, [1][c] = sum of squares
 // / second sum.  The waves' 32-vectors meet in LDS and are added in wave order (deterministic).
@@ -389,26 +385,12 @@ __device__ __forceinline__ bool sample_plane_group(int B, int O, int PZ, int &b,
     o1 = min(O, o0 + PZ);
     return b < B;
 }
-static inline int sample_plane_group_grid(int B, int O, int PZ) { return ((B + 7) / 8) * 8 * ((O + PZ - 1) / PZ); }
-constexpr int kPlanesPerGroup = 4;
-// Planes per workgroup of the fp32 conv2 forward kernel: the smallest of 1, 2, 4 whose grid is at most 512 workgroups (two
-// per CU: one round), four beyond that.  At the reference's 20^3 (O2 = 4, 128 samples) four planes were ONE workgroup per sample whose
-// waves walked two tiles one after the other in a launch that is nothing but latency:
-// forward 128 -> 512 workgroups: 14.3 -> 11.7 us.  (The data gradient does NOT gain: see gnbv_encoder_grid_backward.)
-static inline int planes_per_group(int B, int O)
-{
-    for (int pz = 1; pz < kPlanesPerGroup; pz <<= 1)
-        if (sample_plane_group_grid(B, O, pz) <= 512) return pz;
-    return kPlanesPerGroup;
-}
-constexpr int kBigThreads = 1024;  // conv2 fwd / dgrad: 16 waves share one 27 KiB weight image -> 32 waves per CU
 constexpr int kBigWaves = kBigThreads / kWave;
 
 // ---------------------------------------------------------------------------
 // conv2 forward: z1 = relu(scale1*y1 + shift1) applied on load; y2 [B,16,O2^3] (NCDHW, pre-BN)
 // ---------------------------------------------------------------------------
-// Workgroup = 12 waves (three per SIMD, <= 168 VGPRs each): room for the third slab buffer; 4 planes x 15 rows = 60 tiles = 5 per wave.
-constexpr int kFwdThreads = 768, kFwdWaves = kFwdThreads / kWave;
+constexpr int kFwdWaves = kFwdThreads / kWave;
 template <typename A>
 __global__ __launch_bounds__(kFwdThreads) void k_conv2_fwd(
     const typename A::T *__restrict__ y1, const float *__restrict__ scale1, const float *__restrict__ shift1, int B, int O1, int O2,
@@ -1196,7 +1178,6 @@ __global__ __launch_bounds__(kBigThreads) void k_conv2_dgrad(
 // per-wave int8 slab in LDS: the 5 x 5 x 65 input voxels under one 2 x 2 x 32 super-tile.
 // ---------------------------------------------------------------------------
 constexpr int kSlabRow = 80, kSlabBytes = 25 * kSlabRow;  // 5 planes x 5 rows x (65 -> 80) bytes
-constexpr int kE1F = 512 + 2 * kC;                        // T1 [32 taps][16], S1, S2 [16]
 
 template <int EZ, int EY, int EX>
 __device__ __forceinline__ void dgrad_c1w_subtile(
@@ -1396,12 +1377,7 @@ __global__ __launch_bounds__(kBigThreads) void k_conv2_dgrad_c1w(
 // grid) or, with out_row_stride == 0, the sum over the minibatch.
 // Row layout: 3 tiles of 16 x 16 ints = R[0..15][0..15], R[0..15][16..31], R[16..31][16..31].
 typedef int i32x4 __attribute__((ext_vector_type(4)));
-constexpr int kAcThreads = 512, kAcWaves = kAcThreads / kWave, kAcRow = 3 * 256;
-static inline int autocorr_planes(int grid)
-{
-    const int p = (64 * 1024 / (grid * grid) - 1) / 2;
-    return p < 1 ? 1 : (p > 4 ? 4 : p);
-}
+constexpr int kAcWaves = kAcThreads / kWave;
 
 __global__ __launch_bounds__(kAcThreads) void k_input_autocorr(const int8_t *__restrict__ grid_i8, const int64_t *__restrict__ rows,
                                                              int64_t row_stride, int B, int G, int O1, int P, int *__restrict__ out,
@@ -1930,147 +1906,70 @@ __global__ void k_conv1_wgrad_finish(const double *__restrict__ tmp /*[slices][E
 #include "conv_split.h"
 #include "conv_splitx.h"
 
-static inline int out_size(int g) { return (g - 3) / 2 + 1; }
+// The host side carries out the plans of encoder_plan.h: facts -> switches -> plan -> one switch per stage.
+static_assert(split::kW2ImgU4 * sizeof(uint4) == kW2SplitImgBytes && dsplit::kImgSlotU4 * sizeof(uint4) == kW2SplitDgradSlotBytes &&
+              dsplit::kImgBytes <= (int)kW2SplitDgradSlotBytes, "enc_ws_layout's slots of the split weight images");
+static_assert(split::kLdsBytes > kLds64K && split::kWgLdsBytes > kLds64K && splitx::kLdsBytes > kLds64K && splitx::kWgLdsBytes > kLds64K &&
+              wdma::kLdsBytes > kLds64K && dsplit::kLdsBytes > kLds64K && dsplit::kLdsBytesT > kLds64K && fsplit::kLdsBytes > kLds64K,
+              "every split kernel needs the LDS opt-in");
 
 GNBV_API size_t gnbv_encoder_y1_elems(int batch, int grid)
 {
     if (batch <= 0 || grid < 7) return 0;
-    return y1_elems(batch, (grid - 3) / 2 + 1);
+    return y1_elems(batch, out_size(grid));
 }
 
-GNBV_API size_t gnbv_encoder_workspace_bytes(int batch, int grid)
-{
-    if (batch <= 0 || grid < 7) return 0;
-    const int o1 = out_size(grid);
-    // BN partials of the largest producer (conv1 fwd / conv2 dgrad: B*O1 workgroups x 4 waves x 32 floats),
-    // weight-gradient partials (kWgradWaves x 6928 floats), fp64 reduction scratch
-    const size_t bn = (size_t)(batch + 8) * o1 * kEncWaves * 2 * kC * sizeof(float);
-    const size_t wg = (size_t)2048 * (kTaps * 256 + kC) * sizeof(float);
-    return bn + wg + (8192 + (size_t)64 * (kTaps * 256 + kC)) * sizeof(double) + 2 * kTaps * 256 * sizeof(float) +
-           2 * 14 * 2 * 64 * 16 /*split f16 weight images*/ + 1024 /*their |W2| bounds*/ + 8192 + 4096;
-}
+GNBV_API size_t gnbv_encoder_workspace_bytes(int batch, int grid) { return enc_ws_layout(batch, grid).total; }
 
+// the regions of enc_ws_layout as pointers
 struct EncWs {
-    float *bn_part, *wg_part;
-    double *red, *tmp;
-    float *w2img;  // 2 x 6912 floats
-    uint4 *w2split;  // 2 x split::kW2ImgU4 (conv_split.h)
+    float *bn_part, *wg_part, *wg1_part;
+    double *S2, *S1, *tmp, *tmp1;
+    int *Rac;
+    unsigned *dy2_absmax;
+    float *w2img, *w2img_dgrad;
+    uint4 *w2split, *w2split_dgrad;
+    float *w2split_bounds;
 };
 static inline EncWs enc_carve(void *ws, int batch, int grid)
 {
+    const EncWsLayout l = enc_ws_layout(batch, grid);
+    char *b = (char *)ws;
     EncWs w;
-    const int o1 = out_size(grid);
-    w.bn_part = (float *)ws;
-    w.wg_part = w.bn_part + (size_t)(batch + 8) * o1 * kEncWaves * 2 * kC;
-    w.red = (double *)(((uintptr_t)(w.wg_part + (size_t)2048 * (kTaps * 256 + kC)) + 255) & ~(uintptr_t)255);
-    w.tmp = w.red + 8192;
-    w.w2img = (float *)(w.tmp + (size_t)64 * (kTaps * 256 + kC));
-    w.w2split = (uint4 *)(w.w2img + 2 * kTaps * 256);
+    w.bn_part = (float *)(b + l.bn_part), w.wg_part = (float *)(b + l.wg_part), w.wg1_part = (float *)(b + l.wg1_part);
+    w.S2 = (double *)(b + l.S2), w.S1 = (double *)(b + l.S1), w.tmp = (double *)(b + l.tmp), w.tmp1 = (double *)(b + l.tmp1);
+    w.Rac = (int *)(b + l.Rac), w.dy2_absmax = (unsigned *)(b + l.dy2_absmax);
+    w.w2img = (float *)(b + l.w2img), w.w2img_dgrad = (float *)(b + l.w2img_dgrad);
+    w.w2split = (uint4 *)(b + l.w2split), w.w2split_dgrad = (uint4 *)(b + l.w2split_dgrad), w.w2split_bounds = (float *)(b + l.w2split_bounds);
     return w;
 }
 
-constexpr int kReduceSlices = 64;
-
-// stage 1 of the deterministic fp64 reduction: partial [P][E] -> tmp [slices][E]; the consumer (a
-// *_finish kernel) adds the <= 64 slices in order.  Returns the number of slices.
-static inline int reduce_slices(int P)
+static EncFacts enc_facts(const float *obs_grid, int64_t row_stride, int batch, int grid, const GnbvEncoderParams *p, bool training, bool features)
 {
-    const int slices = P / 32;  // ~32 partial rows per workgroup
-    return slices < 1 ? 1 : (slices > kReduceSlices ? kReduceSlices : slices);
+    EncFacts f = {};
+    f.batch = batch, f.grid = grid, f.training = training, f.features = features;
+    f.obs = obs_grid != nullptr, f.obs_addr15 = (int)((uintptr_t)obs_grid & 15), f.obs_stride4 = (int)(row_stride % 4);
+    f.i8 = p->grid_i8 != nullptr, f.i8_addr15 = (int)((uintptr_t)p->grid_i8 & 15), f.i8_stride16 = (int)(p->grid_i8_row_stride % 16);
+    f.autocorr = p->autocorr != nullptr, f.autocorr_total = p->autocorr_total != nullptr, f.autocorr_global = p->autocorr_global != nullptr;
+    f.force_fp32 = p->force_fp32 != 0, f.eval_prepared = p->eval_prepared != 0;
+    f.dp = p->world > 1 && p->sync_sum != nullptr && p->sync_buf != nullptr;
+    return f;
 }
-static inline int reduce_stage1(const float *partial, int P, int E, double *tmp, hipStream_t st)
+
+// stage 1 of the deterministic fp64 reduction: partial [P][E] -> tmp [slices][E] (reduce_slices)
+static inline void reduce_stage1(const float *partial, int P, int E, int slices, double *tmp, hipStream_t st)
 {
-    const int slices = reduce_slices(P);
     const int per = (P + slices - 1) / slices;
-    if (E % 4 == 0 && (((uintptr_t)partial) & 15) == 0)
+    if (enc_reduce_vec4((uintptr_t)partial, E))
         hipLaunchKernelGGL(k_reduce_partials4, dim3((E / 4 + 63) / 64, slices), dim3(256), 0, st, partial, P, E, per, tmp);
     else
         hipLaunchKernelGGL(k_reduce_partials<float>, dim3((E + 63) / 64, slices), dim3(256), 0, st, partial, P, E, per, tmp,
                            (float *)nullptr);
-    return slices;
-}
-// Kernel-path predicates shared by forward and backward (they must agree on what the layer-1 buffer holds).
-//   fused_path: conv2 data gradient fused with the conv1 weight gradient (needs the grid as aligned int8 rows)
-static inline bool env_off(const char *name)
-{
-    const char *e = getenv(name);
-    return e && e[0] == '0';
-}
-// conv2 kernels on the f16 matrix pipe with split (hi + lo) operands, staged through LDS (conv_split.h): fp32 y1 in the default
-// x-parity layout, 16 voxel slots per half row (G = 64)
-static inline bool conv_split_path(const GnbvEncoderParams *p, int grid)
-{
-    const int O1 = out_size(grid), O2 = out_size(O1);
-    return !env_off("GENNBV_CONV_SPLIT") && !p->force_fp32 && (O1 + 1) / 2 == 16 && O2 <= 15;
-}
-// the same arithmetic for rows wider than 16 voxel slots per x parity (conv_splitx.h: x tiles of 16 outputs, 17-voxel ring rows): the
-// G = 128 class (O1 = 63, O2 = 31); GENNBV_SPLITX=1 also routes the G = 64 class through these kernels (tests)
-static inline bool conv_splitx_path(const GnbvEncoderParams *p, int grid)
-{
-    const int O1 = out_size(grid), O2 = out_size(O1), XH = (O1 + 1) / 2;
-    if (env_off("GENNBV_CONV_SPLIT") || p->force_fp32 || O2 < 1) return false;
-    const char *e = getenv("GENNBV_SPLITX");
-    if (e && e[0] == '0') return false;
-    return (XH > 16 && XH <= 32 && O2 <= 32) || (XH == 16 && O2 <= 15 && e && e[0] == '1');
-}
-// most workgroups of the x-tiled backward kernels (each walks items block, block + grid, ...); GENNBV_SPLITX_MAXWG lowers it so that small
-// test shapes exercise the several-items-per-workgroup path
-static inline int splitx_max_wg()
-{
-    const char *e = getenv("GENNBV_SPLITX_MAXWG");
-    const int v = e ? atoi(e) : 0;
-    return v >= 8 && v <= 512 ? (v & ~7) : 512;
-}
-// most workgroups of the G = 64 split kernels that walk several items (k_conv2_wgrad_split_dma, k_conv12_fwd_split): 256 = one per CU, i.e. two items
-// per workgroup at the bench's minibatch instead of two workgroups per CU one after the other; GENNBV_CONV_MAXWG=512 restores one item per
-// workgroup (bit-identity tests against the register-staged kernel, A/B runs)
-static inline int conv_max_wg()
-{
-    const char *e = getenv("GENNBV_CONV_MAXWG");
-    const int v = e ? atoi(e) : 0;
-    return v >= 8 && v <= 512 ? (v & ~7) : 256;
-}
-// conv2 weight gradient with the LDS-DMA transport (k_conv2_wgrad_split_dma, round 6): the default at G = 64 -- bit-identical to the
-// register-staged k_conv2_wgrad_split, which GENNBV_WGRAD_DMA=0 keeps selectable (A/B runs, tests/test_encoder_gpu.py)
-static inline bool wgrad_dma_path()
-{
-    const char *e = getenv("GENNBV_WGRAD_DMA");
-    return !(e && e[0] == '0');
-}
-static inline bool fused_path(const GnbvEncoderParams *p, int grid)
-{
-    return !env_off("GENNBV_FUSED_BWD") && p->grid_i8 != nullptr && grid % 16 == 0 && 3 * grid * grid <= 64 * 1024 &&
-           p->grid_i8_row_stride % 16 == 0 && (((uintptr_t)p->grid_i8 & 15) == 0);
-}
-static inline bool conv1_i8_staged(const GnbvEncoderParams *p, int grid)
-{
-    const int O1 = out_size(grid);
-    return p->grid_i8 != nullptr && grid % 16 == 0 && p->grid_i8_row_stride % 16 == 0 && (((uintptr_t)p->grid_i8 & 15) == 0) &&
-           (size_t)3 * (2 * O1 + 1) * grid * sizeof(float) <= 64 * 1024 && 2 * O1 + 1 <= grid;
-}
-
-// bn_state = [2][4][16] floats (scale, shift, mean, rstd per layer) + kAcRow ints: the minibatch total of the input
-// autocorrelation, written by the forward whenever it computed BN1's statistics from it (analytic_bn1) and read
-// back by the backward instead of gathering the rows again
-constexpr int kBnStateFloats = 2 * 4 * kC;
-static inline bool analytic_bn1(const GnbvEncoderParams *p, int grid)
-{
-    return p->autocorr != nullptr && conv1_i8_staged(p, grid) && 3 * grid * grid <= 64 * 1024 && !env_off("GENNBV_ANALYTIC_BN1");
-}
-
-// minibatch total of the input autocorrelation into `Rac` (when the caller has no per-row results)
-static int launch_autocorr_total(const GnbvEncoderParams *p, const int64_t *rows, int batch, int grid, int *Rac, hipStream_t st)
-{
-    if (hipMemsetAsync(Rac, 0, kAcRow * sizeof(int), st) != hipSuccess) return (int)hipGetLastError();
-    const int P = autocorr_planes(grid), O1 = out_size(grid);
-    hipLaunchKernelGGL(k_input_autocorr, dim3(sample_plane_group_grid(batch, O1, P)), dim3(kAcThreads), (size_t)(2 * P + 1) * grid * grid, st,
-                       p->grid_i8, rows, p->grid_i8_row_stride, batch, grid, O1, P, Rac, (int64_t)0);
-    return gnbv_launch_status();
 }
 
 // The launches of an inference forward that depend on the parameters only (GnbvEncoderParams.eval_prepared): BatchNorm-1's
 // (scale, shift, mean, rstd) from the running statistics + the bound check of its channels, the conv2 weight images, and -- bn2 --
-// BatchNorm-2's.  One-launch conv1 + conv2 inference path (fused_eval below) only.
+// BatchNorm-2's.  One-launch conv1 + conv2 inference path (EncPaths::fused_eval) only.
 static int eval_prepare_launches(const GnbvEncoderParams *p, int batch, int O1, int P2, float *bn_state, const EncWs &w, hipStream_t st, bool bn2_too)
 {
     float *bn1 = bn_state, *bn2 = bn_state + 4 * kC;
@@ -2090,7 +1989,8 @@ GNBV_API int gnbv_encoder_eval_prepare(int batch, int grid, const GnbvEncoderPar
     GNBV_CHECK_ARG(workspace_bytes >= gnbv_encoder_workspace_bytes(batch, grid) && ((uintptr_t)workspace & 255) == 0);
     GNBV_CHECK_ARG(p->w1 && p->b1 && p->bn1_w && p->bn1_b && p->bn1_rm && p->bn1_rv && p->w2 && p->b2 && p->bn2_w && p->bn2_b &&
                    p->bn2_rm && p->bn2_rv);
-    if (!(conv_split_path(p, grid) && conv1_i8_staged(p, grid) && grid == 64 && !env_off("GENNBV_FUSED_EVAL"))) return GNBV_ERR_NOT_APPLICABLE;
+    const EncFacts f = enc_facts(nullptr, 0, batch, grid, p, /*training=*/false, false);
+    if (enc_eval_prepare_refusal(f, enc_switches_from_env()) != EncRefusal::NONE) return GNBV_ERR_NOT_APPLICABLE;
     const int O1 = out_size(grid), O2 = out_size(O1);
     return eval_prepare_launches(p, batch, O1, O2 * O2 * O2, bn_state, enc_carve(workspace, batch, grid), gnbv_stream(stream), /*bn2=*/true);
 }
@@ -2106,157 +2006,127 @@ GNBV_API int gnbv_encoder_grid_forward(const float *obs_grid, const int64_t *row
     GNBV_CHECK_ARG(workspace_bytes >= gnbv_encoder_workspace_bytes(batch, grid) && ((uintptr_t)workspace & 255) == 0);
     GNBV_CHECK_ARG(p->w1 && p->b1 && p->bn1_w && p->bn1_b && p->bn1_rm && p->bn1_rv && p->w2 && p->b2 && p->bn2_w && p->bn2_b &&
                    p->bn2_rm && p->bn2_rv);
-    hipStream_t st = gnbv_stream(stream);
-    const int O1 = out_size(grid), O2 = out_size(O1);
-    GNBV_CHECK_ARG(O2 >= 1 && y1_elems(batch, O1) < ((size_t)1 << 31));
-    const int P2 = O2 * O2 * O2;
-    EncWs w = enc_carve(workspace, batch, grid);
-    float *bn1 = bn_state, *bn2 = bn_state + 4 * kC;
-    int err;
+    GNBV_CHECK_ARG(out_size(out_size(grid)) >= 1 && y1_elems(batch, out_size(grid)) < ((size_t)1 << 31));
     GNBV_CHECK_ARG(p->autocorr == nullptr || (p->autocorr_row_stride >= kAcRow && p->autocorr_row_stride % 4 == 0 && ((uintptr_t)p->autocorr & 15) == 0));
-    const bool dp = training && p->world > 1 && p->sync_sum != nullptr && p->sync_buf != nullptr;  // BatchNorm over the replicas' global minibatch
-    // Inference with the grid as int8 rows at G = 64: conv1 + BN1 + ReLU + conv2 in one kernel, no layer-1 buffer at all
-    // (conv_split.h).  y1 is left untouched (no backward follows an eval-mode forward).
-    const bool fused_eval = !training && conv_split_path(p, grid) && conv1_i8_staged(p, grid) && grid == 64 && !env_off("GENNBV_FUSED_EVAL");
-    bool fused_train = false;
-    if (fused_eval) {
-        if (!p->eval_prepared && (err = eval_prepare_launches(p, batch, O1, P2, bn_state, w, st, /*bn2=*/false))) return err;
-        static bool attr_fe = false;
-        if (!attr_fe) {
-            const hipError_t e = hipFuncSetAttribute((const void *)k_conv12_fwd_split<false>, hipFuncAttributeMaxDynamicSharedMemorySize, fsplit::kLdsBytes);
-            if (e != hipSuccess) return (int)e;
-            attr_fe = true;
-        }
-        // (a workgroup walks items block, block + grid, ... on one continuous ring: one workgroup per CU by default)
-        const int nitems = sample_plane_group_grid(batch, O2, split::kNP);
-        hipLaunchKernelGGL(k_conv12_fwd_split<false>, dim3(min(nitems, conv_max_wg())), dim3(split::kThreads), fsplit::kLdsBytes, st,
-                           p->grid_i8, rows, p->grid_i8_row_stride, p->w1, p->b1, (const float *)bn1, (const float *)(bn1 + kC), batch, grid, O1, O2, nitems,
-                           (const uint4 *)w.w2split, p->b2, y2, (float *)nullptr, (float *)nullptr);
-        if ((err = gnbv_launch_status())) return err;
-    } else {
-    // BN1 batch statistics analytically from the stored input autocorrelation rows (k_bn1_analytic: 6 us, independent of
-    // conv1) instead of partial sums in conv1 + a 12 us reduction behind it; y1 is stored as before
-    const bool analytic = training && analytic_bn1(p, grid);
-    if (dp && !(analytic && fused_path(p, grid) && p->autocorr_global != nullptr)) return (int)hipErrorInvalidValue;  // (see GnbvEncoderParams.world)
-    // Training with BN1's statistics known beforehand: conv1 + BN1 + ReLU + conv2 as ONE launch that also stores y1 for the backward
-    // (conv_split.h) -- conv2 never reads the 244 MB it would otherwise fetch right after conv1 wrote them.
-    fused_train = analytic && conv_split_path(p, grid) && grid == 64 && !env_off("GENNBV_CONV1_SPLIT") && !env_off("GENNBV_FUSED_TRAIN");
-    if (analytic) {
-        // (the caller may hand over the minibatch's autocorrelation total: no gather then -- GnbvEncoderParams.autocorr_total)
-        const bool have_total = p->autocorr_total != nullptr && !dp;
-        hipLaunchKernelGGL(k_bn1_analytic, dim3(fused_train ? 9 : 1), dim3(1024), 0, st, have_total ? (const int *)p->autocorr_total : (const int *)p->autocorr,
-                           p->autocorr_row_stride, rows, have_total ? 0 : batch, p->w1,
+    const EncForwardPlan pl = enc_forward_plan(enc_facts(obs_grid, row_stride, batch, grid, p, training != 0, features != nullptr), enc_switches_from_env());
+    if (pl.refusal != EncRefusal::NONE) return (int)hipErrorInvalidValue;
+    hipStream_t st = gnbv_stream(stream);
+    const int O1 = pl.O1, O2 = pl.O2, P2 = pl.P2;
+    const EncWs w = enc_carve(workspace, batch, grid);
+    float *bn1 = bn_state, *bn2 = bn_state + 4 * kC;
+    float *c1_part = pl.c1_part ? w.bn_part : nullptr;
+    const double n1 = (double)batch * O1 * O1 * O1;
+    const dim3 g1(pl.c1_grid), t1(kEncThreads);
+    int err;
+    // ---- BatchNorm-1 where it is known before conv1 runs ----
+    if (pl.bn1 == Bn1::PREPARE) {
+        if ((err = eval_prepare_launches(p, batch, O1, P2, bn_state, w, st, /*bn2=*/false))) return err;
+    } else if (pl.bn1 == Bn1::ANALYTIC) {
+        const bool dp = pl.bn2 == Bn2::DP;
+        hipLaunchKernelGGL(k_bn1_analytic, dim3(pl.bn1_grid), dim3(1024), 0, st, pl.have_total ? (const int *)p->autocorr_total : (const int *)p->autocorr,
+                           p->autocorr_row_stride, rows, pl.have_total ? 0 : batch, p->w1,
                            p->b1, p->bn1_w, p->bn1_b, p->eps, p->momentum, p->bn1_rm, p->bn1_rv, p->bn1_nbt, skip_flag, bn1, bn1 + kC, bn1 + 2 * kC,
                            bn1 + 3 * kC, (int *)(bn_state + kBnStateFloats), dp ? (const int *)p->autocorr_global : (const int *)nullptr,
                            p->w2, w.w2img, p->range_flag);
         if ((err = gnbv_launch_status())) return err;
     }
-    float *c1_part = (training && !analytic) ? w.bn_part : nullptr;
-    const int split_img = (conv_split_path(p, grid) || conv_splitx_path(p, grid)) ? 1 : 0;  // (the f16 weight images: only where a split kernel reads them)
-    // conv1 (+ BN1 statistics)
-    if (fused_train) {
-        static bool attr_ft = false;
-        if (!attr_ft) {
-            const hipError_t e = hipFuncSetAttribute((const void *)k_conv12_fwd_split<true>, hipFuncAttributeMaxDynamicSharedMemorySize, fsplit::kLdsBytes);
-            if (e != hipSuccess) return (int)e;
-            attr_ft = true;
+    // ---- conv1 (+ BN1 partial sums; + conv2 in the one-launch kernel).  The conv2 weight images are written in passing. ----
+#define GNBV_C12_ARGS dim3(pl.c1_grid), dim3(split::kThreads), fsplit::kLdsBytes, st, p->grid_i8, rows, p->grid_i8_row_stride, p->w1, p->b1,             \
+                      (const float *)bn1, (const float *)(bn1 + kC), batch, grid, O1, O2, pl.nitems, (const uint4 *)w.w2split, p->b2, y2
+    switch (pl.conv1) {
+    case Conv1::FUSED:
+        if (training) {
+            if ((err = gnbv_raise_lds<k_conv12_fwd_split<true>>(fsplit::kLdsBytes, fsplit::kLdsBytes))) return err;
+            hipLaunchKernelGGL(k_conv12_fwd_split<true>, GNBV_C12_ARGS, (float *)y1, w.bn_part);
+        } else {
+            if ((err = gnbv_raise_lds<k_conv12_fwd_split<false>>(fsplit::kLdsBytes, fsplit::kLdsBytes))) return err;
+            hipLaunchKernelGGL(k_conv12_fwd_split<false>, GNBV_C12_ARGS, (float *)nullptr, (float *)nullptr);
         }
-        // (the BN2 partial rows stay one per ITEM, whatever the grid: k_stats_reduce sees the same rows)
-        const int nitems = sample_plane_group_grid(batch, O2, split::kNP);
-        hipLaunchKernelGGL(k_conv12_fwd_split<true>, dim3(min(nitems, conv_max_wg())), dim3(split::kThreads), fsplit::kLdsBytes, st,
-                           p->grid_i8, rows, p->grid_i8_row_stride, p->w1, p->b1, (const float *)bn1, (const float *)(bn1 + kC), batch, grid, O1, O2, nitems,
-                           (const uint4 *)w.w2split, p->b2, y2, (float *)y1, w.bn_part);
-    } else {
-        const size_t c1_lds = (size_t)3 * (2 * O1 + 1) * grid * sizeof(float);
-        const bool c1_staged = obs_grid != nullptr && (grid % 4 == 0) && (row_stride % 4 == 0) && (((uintptr_t)obs_grid & 15) == 0) && c1_lds <= 64 * 1024 &&
-                               2 * O1 + 1 <= grid;
-        if (conv1_i8_staged(p, grid) && c1_part == nullptr && grid == 64 && conv_split_path(p, grid) && !env_off("GENNBV_CONV1_SPLIT"))  // (no partial sums: BN1 is analytic or in eval mode)
-            hipLaunchKernelGGL(k_conv1_fwd_split, dim3(sample_plane_grid(batch, O1)), dim3(kEncThreads), 0, st, p->grid_i8, rows, p->grid_i8_row_stride, batch, grid,
-                               O1, p->w1, p->b1, (float *)y1, p->w2, w.w2img);
-        else if (conv1_i8_staged(p, grid))  // compact int8 copy of the tri-class grid: a quarter of the input bytes
-            hipLaunchKernelGGL((k_conv1_fwd_lds<ActF32, int8_t>), dim3(sample_plane_grid(batch, O1)), dim3(kEncThreads), c1_lds, st, p->grid_i8, rows,
-                               p->grid_i8_row_stride, batch, grid, O1, p->w1, p->b1, (float *)y1, c1_part, p->w2, w.w2img, split_img);
-        else if (c1_staged)
-            hipLaunchKernelGGL((k_conv1_fwd_lds<ActF32, float>), dim3(sample_plane_grid(batch, O1)), dim3(kEncThreads), c1_lds, st, obs_grid, rows,
-                               row_stride, batch, grid, O1, p->w1, p->b1, (float *)y1, c1_part, p->w2, w.w2img, split_img);
-        else if (p->grid_i8 != nullptr && grid % 16 == 0 && p->grid_i8_row_stride % 16 == 0 && (((uintptr_t)p->grid_i8 & 15) == 0) &&
-                 c1_lds / 4 <= 64 * 1024 && 2 * O1 + 1 <= grid)  // int8 rows, fp32 slab too large (G = 128): int8 slab
-            hipLaunchKernelGGL((k_conv1_fwd_lds<ActF32, int8_t, true>), dim3(sample_plane_grid(batch, O1)), dim3(kEncThreads), c1_lds / 4, st, p->grid_i8,
-                               rows, p->grid_i8_row_stride, batch, grid, O1, p->w1, p->b1, (float *)y1, c1_part, p->w2, w.w2img, split_img);
-        else if (obs_grid == nullptr)  // compact rows at a size the staged kernels do not take
-            hipLaunchKernelGGL((k_conv1_fwd<ActF32, int8_t>), dim3(sample_plane_grid(batch, O1)), dim3(kEncThreads), 0, st, p->grid_i8, rows,
-                               p->grid_i8_row_stride, batch, grid, O1, p->w1, p->b1, (float *)y1, c1_part, p->w2, w.w2img, split_img);
-        else
-            hipLaunchKernelGGL(k_conv1_fwd<ActF32>, dim3(sample_plane_grid(batch, O1)), dim3(kEncThreads), 0, st, obs_grid, rows, row_stride,
-                               batch, grid, O1, p->w1, p->b1, (float *)y1, c1_part, p->w2, w.w2img, split_img);
+        break;
+    case Conv1::SPLIT:
+        hipLaunchKernelGGL(k_conv1_fwd_split, g1, t1, 0, st, p->grid_i8, rows, p->grid_i8_row_stride, batch, grid, O1, p->w1, p->b1, (float *)y1, p->w2,
+                           w.w2img);
+        break;
+    case Conv1::LDS_I8:
+        hipLaunchKernelGGL((k_conv1_fwd_lds<ActF32, int8_t>), g1, t1, pl.c1_lds, st, p->grid_i8, rows, p->grid_i8_row_stride, batch, grid, O1, p->w1,
+                           p->b1, (float *)y1, c1_part, p->w2, w.w2img, pl.split_img);
+        break;
+    case Conv1::LDS_F32:
+        hipLaunchKernelGGL((k_conv1_fwd_lds<ActF32, float>), g1, t1, pl.c1_lds, st, obs_grid, rows, row_stride, batch, grid, O1, p->w1, p->b1, (float *)y1,
+                           c1_part, p->w2, w.w2img, pl.split_img);
+        break;
+    case Conv1::LDS_I8_SLAB:
+        hipLaunchKernelGGL((k_conv1_fwd_lds<ActF32, int8_t, true>), g1, t1, pl.c1_lds, st, p->grid_i8, rows, p->grid_i8_row_stride, batch, grid, O1,
+                           p->w1, p->b1, (float *)y1, c1_part, p->w2, w.w2img, pl.split_img);
+        break;
+    case Conv1::DIRECT_I8:
+        hipLaunchKernelGGL((k_conv1_fwd<ActF32, int8_t>), g1, t1, 0, st, p->grid_i8, rows, p->grid_i8_row_stride, batch, grid, O1, p->w1, p->b1,
+                           (float *)y1, c1_part, p->w2, w.w2img, pl.split_img);
+        break;
+    case Conv1::DIRECT_F32:
+        hipLaunchKernelGGL(k_conv1_fwd<ActF32>, g1, t1, 0, st, obs_grid, rows, row_stride, batch, grid, O1, p->w1, p->b1, (float *)y1, c1_part, p->w2,
+                           w.w2img, pl.split_img);
+        break;
+    }
+#undef GNBV_C12_ARGS
+    if ((err = gnbv_launch_status())) return err;
+    // ---- BatchNorm-1 from conv1's partial sums (training) or from the running statistics ----
+    if (pl.bn1 == Bn1::REDUCE)
+        hipLaunchKernelGGL(k_stats_reduce, dim3(1), dim3(1024), 0, st, w.bn_part, pl.c1_grid, (double *)nullptr, n1, p->bn1_w, p->bn1_b, p->eps,
+                           p->momentum, p->bn1_rm, p->bn1_rv, p->bn1_nbt, skip_flag, bn1, bn1 + kC, bn1 + 2 * kC, bn1 + 3 * kC, (const float *)nullptr,
+                           (float *)nullptr, p->w1, p->b1, p->range_flag);
+    else if (pl.bn1 == Bn1::FINALIZE)
+        hipLaunchKernelGGL(k_bn_finalize, dim3(1), dim3(64), 0, st, n1, p->bn1_w, p->bn1_b, p->eps, p->momentum, p->bn1_rm, p->bn1_rv, bn1, bn1 + kC,
+                           bn1 + 2 * kC, bn1 + 3 * kC, p->w1, p->b1, p->range_flag);
+    if ((err = gnbv_launch_status())) return err;
+    // ---- conv2 (BN1 + ReLU on load; + BN2 partial sums) ----
+    float *c2_part = training ? w.bn_part : nullptr;
+    switch (pl.conv2) {
+    case Conv2::FUSED:  // (y2 was written by k_conv12_fwd_split above)
+        break;
+    case Conv2::SPLITX:
+        if ((err = gnbv_raise_lds<k_conv2_fwd_splitx>(splitx::kLdsBytes, splitx::kLdsBytes))) return err;
+        hipLaunchKernelGGL(k_conv2_fwd_splitx, dim3(pl.g2), dim3(split::kThreads), splitx::kLdsBytes, st, (const float *)y1, bn1, bn1 + kC, batch, O1, O2,
+                           pl.XT, (const uint4 *)w.w2split, p->b2, y2, c2_part);
+        break;
+    case Conv2::SPLIT:
+        if ((err = gnbv_raise_lds<k_conv2_fwd_split>(split::kLdsBytes, split::kLdsBytes))) return err;
+        hipLaunchKernelGGL(k_conv2_fwd_split, dim3(pl.g2), dim3(split::kThreads), split::kLdsBytes, st, (const float *)y1, bn1, bn1 + kC, batch, O1, O2,
+                           (const uint4 *)w.w2split, p->b2, y2, c2_part);
+        break;
+    case Conv2::FP32:
+        hipLaunchKernelGGL(k_conv2_fwd<ActF32>, dim3(pl.g2), dim3(kFwdThreads), 0, st, (const float *)y1, bn1, bn1 + kC, batch, O1, O2, w.w2img, p->b2, y2,
+                           c2_part, pl.pz2);
+        break;
     }
     if ((err = gnbv_launch_status())) return err;
-    if (analytic) {
-    } else if (training)
-        hipLaunchKernelGGL(k_stats_reduce, dim3(1), dim3(1024), 0, st, w.bn_part, sample_plane_grid(batch, O1), (double *)nullptr,
-                           (double)batch * O1 * O1 * O1, p->bn1_w, p->bn1_b, p->eps, p->momentum, p->bn1_rm, p->bn1_rv, p->bn1_nbt, skip_flag,
-                           bn1, bn1 + kC, bn1 + 2 * kC, bn1 + 3 * kC, (const float *)nullptr, (float *)nullptr, p->w1, p->b1, p->range_flag);
-    else
-        hipLaunchKernelGGL(k_bn_finalize, dim3(1), dim3(64), 0, st, (double)batch * O1 * O1 * O1, p->bn1_w, p->bn1_b, p->eps, p->momentum,
-                           p->bn1_rm, p->bn1_rv, bn1, bn1 + kC, bn1 + 2 * kC, bn1 + 3 * kC, p->w1, p->b1, p->range_flag);
-    if ((err = gnbv_launch_status())) return err;
-    }
-    // conv2 (BN1 + ReLU on load; + BN2 statistics).  Its LDS weight images were written by the conv1 kernel in passing.
-    const int pz2 = planes_per_group(batch, O2);
-    int g2 = sample_plane_group_grid(batch, O2, pz2);
-    if (fused_eval || fused_train) {
-        // (y2 was written by k_conv12_fwd_split above)
-        g2 = sample_plane_group_grid(batch, O2, split::kNP);
-    } else if (conv_splitx_path(p, grid)) {
-        const int XT = (O2 + 15) / 16;
-        g2 = splitx::items(batch, O2, XT);
-        static bool attr_sx = false;
-        if (!attr_sx) {
-            const hipError_t e = hipFuncSetAttribute((const void *)k_conv2_fwd_splitx, hipFuncAttributeMaxDynamicSharedMemorySize, splitx::kLdsBytes);
-            if (e != hipSuccess) return (int)e;
-            attr_sx = true;
-        }
-        hipLaunchKernelGGL(k_conv2_fwd_splitx, dim3(g2), dim3(split::kThreads), splitx::kLdsBytes, st, (const float *)y1, bn1, bn1 + kC, batch, O1, O2, XT,
-                           (const uint4 *)w.w2split, p->b2, y2, training ? w.bn_part : nullptr);
-    } else if (conv_split_path(p, grid)) {
-        // (its weight images, and the data-gradient kernel's, were written by the conv1 kernel in passing)
-        g2 = sample_plane_group_grid(batch, O2, split::kNP);
-        static bool attr_split = false;
-        if (!attr_split) {
-            const hipError_t e = hipFuncSetAttribute((const void *)k_conv2_fwd_split, hipFuncAttributeMaxDynamicSharedMemorySize, split::kLdsBytes);
-            if (e != hipSuccess) return (int)e;
-            attr_split = true;
-        }
-        hipLaunchKernelGGL(k_conv2_fwd_split, dim3(g2), dim3(split::kThreads), split::kLdsBytes, st, (const float *)y1, bn1, bn1 + kC, batch, O1, O2,
-                           (const uint4 *)w.w2split, p->b2, y2, training ? w.bn_part : nullptr);
-    } else {
-        hipLaunchKernelGGL(k_conv2_fwd<ActF32>, dim3(g2), dim3(kFwdThreads), 0, st, (const float *)y1, bn1, bn1 + kC, batch, O1, O2, w.w2img, p->b2, y2,
-                       training ? w.bn_part : nullptr, pz2);
-    }
-    if ((err = gnbv_launch_status())) return err;
-    if (training && dp) {
-        // BatchNorm-2 over the global minibatch: this replica's (sum, sum of squares) -> sum over the replicas -> finalize
-        hipLaunchKernelGGL(k_stats_reduce, dim3(1), dim3(1024), 0, st, w.bn_part, g2, p->sync_buf, 0.0, (const float *)nullptr, (const float *)nullptr,
+    // ---- BatchNorm-2 ----
+    switch (pl.bn2) {
+    case Bn2::DP:  // over the global minibatch: this replica's (sum, sum of squares) -> sum over the replicas -> finalize
+        hipLaunchKernelGGL(k_stats_reduce, dim3(1), dim3(1024), 0, st, w.bn_part, pl.g2, p->sync_buf, 0.0, (const float *)nullptr, (const float *)nullptr,
                            0.0f, 0.0f, (float *)nullptr, (float *)nullptr, (int64_t *)nullptr, (const int *)nullptr, (float *)nullptr, (float *)nullptr,
                            (float *)nullptr, (float *)nullptr, (const float *)nullptr, (float *)nullptr);
         if ((err = gnbv_launch_status())) return err;
         if ((err = p->sync_sum(p->sync_ctx, 0, 2 * kC, stream))) return err;
         hipLaunchKernelGGL(k_bn_finalize_sums, dim3(1), dim3(64), 0, st, (const double *)p->sync_buf, (double)batch * P2 * p->world, p->bn2_w, p->bn2_b,
                            p->eps, p->momentum, p->bn2_rm, p->bn2_rv, p->bn2_nbt, skip_flag, bn2, bn2 + kC, bn2 + 2 * kC, bn2 + 3 * kC);
-    } else if (training)
-        hipLaunchKernelGGL(k_stats_reduce, dim3(1), dim3(1024), 0, st, w.bn_part, g2, (double *)nullptr, (double)batch * P2, p->bn2_w, p->bn2_b,
+        break;
+    case Bn2::REDUCE:
+        hipLaunchKernelGGL(k_stats_reduce, dim3(1), dim3(1024), 0, st, w.bn_part, pl.g2, (double *)nullptr, (double)batch * P2, p->bn2_w, p->bn2_b,
                            p->eps, p->momentum, p->bn2_rm, p->bn2_rv, p->bn2_nbt, skip_flag, bn2, bn2 + kC, bn2 + 2 * kC, bn2 + 3 * kC,
                            (const float *)nullptr, (float *)nullptr);
-    else if (!(fused_eval && p->eval_prepared))
+        break;
+    case Bn2::FINALIZE:
         hipLaunchKernelGGL(k_bn_finalize, dim3(1), dim3(64), 0, st, (double)batch * P2, p->bn2_w, p->bn2_b, p->eps, p->momentum, p->bn2_rm,
                            p->bn2_rv, bn2, bn2 + kC, bn2 + 2 * kC, bn2 + 3 * kC);
+        break;
+    case Bn2::NONE:  // (gnbv_encoder_eval_prepare wrote it)
+        break;
+    }
     if ((err = gnbv_launch_status())) return err;
-    // BN2 + ReLU -> flat features [B, 16*P2] (C-major, the reference's .reshape(num_env, -1))
-    const int64_t total = (int64_t)batch * kC * P2;
-    int grid_x = (int)((total + 255) / 256);
-    grid_x = grid_x > 4096 ? 4096 : grid_x;
-    if (features == nullptr) return gnbv_launch_status();  // (the consumer folds BN2 + ReLU into its operand load: gnbv_linear_forward_fold)
-    hipLaunchKernelGGL(k_bn_relu_apply, dim3(grid_x), dim3(256), 0, st, y2, bn2, bn2 + kC, total, P2, features, p->range_flag);
+    // ---- BN2 + ReLU -> flat features [B, 16*P2] (C-major, the reference's .reshape(num_env, -1)) ----
+    if (pl.feat_grid > 0)
+        hipLaunchKernelGGL(k_bn_relu_apply, dim3(pl.feat_grid), dim3(256), 0, st, y2, bn2, bn2 + kC, (int64_t)batch * kC * P2, P2, features, p->range_flag);
     return gnbv_launch_status();
 }
 
@@ -2269,229 +2139,154 @@ GNBV_API int gnbv_encoder_grid_backward(const float *obs_grid, const int64_t *ro
     GNBV_CHECK_ARG(p->grid_i8 == nullptr || p->grid_i8_row_stride >= (int64_t)grid * grid * grid);
     GNBV_CHECK_ARG(batch > 0 && grid >= 7 && workspace_bytes >= gnbv_encoder_workspace_bytes(batch, grid) && ((uintptr_t)workspace & 255) == 0);
     GNBV_CHECK_ARG(g->w1 && g->b1 && g->bn1_w && g->bn1_b && g->w2 && g->b2 && g->bn2_w && g->bn2_b);
-    hipStream_t st = gnbv_stream(stream);
-    const int O1 = out_size(grid), O2 = out_size(O1), P2 = O2 * O2 * O2;
-    EncWs w = enc_carve(workspace, batch, grid);
-    const float *bn1 = bn_state, *bn2 = bn_state + 4 * kC;
-    int err;
-    // conv2 data gradient fused with the conv1 weight gradient (dz1' never stored) when the grid exists as aligned
-    // int8 rows; the input autocorrelation it needs runs on a second stream beside the kernels below
-    const bool fused = fused_path(p, grid);  // (GENNBV_FUSED_BWD=0: A/B runs, bit-equality tests)
     GNBV_CHECK_ARG(p->autocorr == nullptr || (p->autocorr_row_stride >= kAcRow && p->autocorr_row_stride % 4 == 0 && ((uintptr_t)p->autocorr & 15) == 0));
-    // the input autocorrelation: per-sample rows computed when the observation was produced (p->autocorr), or
-    // the minibatch total computed here
-    int *Rac = (int *)(w.red + 1024);  // [kAcRow]
-    // (a training forward that computed BN1's statistics from the autocorrelation left the minibatch total in bn_state)
-    const bool saved_total = fused && analytic_bn1(p, grid);
-    if (fused && !saved_total && p->autocorr == nullptr && (err = launch_autocorr_total(p, rows, batch, grid, Rac, st))) return err;
+    const EncFacts f = enc_facts(obs_grid, row_stride, batch, grid, p, /*training=*/true, false);
+    const EncBackwardPlan pl = enc_backward_plan(f, enc_switches_from_env());
+    if (pl.refusal != EncRefusal::NONE) return (int)hipErrorInvalidValue;
+    hipStream_t st = gnbv_stream(stream);
+    const int O1 = pl.O1, O2 = pl.O2, P2 = pl.P2;
+    const EncWs w = enc_carve(workspace, batch, grid);
+    const float *bn1 = bn_state, *bn2 = bn_state + 4 * kC;
+    const bool dp = f.dp;
+    int err;
+    // ---- the input autocorrelation of the fused backward: per-sample rows computed when the observation was produced (p->autocorr),
+    // the minibatch total a training forward left in bn_state (saved_total), or the total computed here ----
+    if (pl.autocorr_launch) {
+        if (hipMemsetAsync(w.Rac, 0, kAcRow * sizeof(int), st) != hipSuccess) return (int)hipGetLastError();
+        hipLaunchKernelGGL(k_input_autocorr, dim3(pl.ac_grid), dim3(kAcThreads), pl.ac_lds, st, p->grid_i8, rows, p->grid_i8_row_stride, batch, grid, O1,
+                           pl.ac_planes, w.Rac, (int64_t)0);
+        if ((err = gnbv_launch_status())) return err;
+    }
     // ---- BN2 + ReLU backward ----
     hipLaunchKernelGGL(k_bn2_bwd_reduce, dim3(batch * kC), dim3(256), 0, st, d_features, y2, bn2, bn2 + kC, bn2 + 2 * kC,
                        bn2 + 3 * kC, P2, w.bn_part);
     if ((err = gnbv_launch_status())) return err;
-    double *S2 = w.red + 128;
-    unsigned *dy2_absmax = (unsigned *)(w.red + 2048);  // max |dy2| (bit patterns, 64 slots x 128 bytes): the gradient scale of the split kernels
-    hipLaunchKernelGGL(k_bn2_bwd_finalize, dim3(1), dim3(256), 0, st, w.bn_part, batch, S2, dy2_absmax);
+    hipLaunchKernelGGL(k_bn2_bwd_finalize, dim3(1), dim3(256), 0, st, w.bn_part, batch, w.S2, w.dy2_absmax);
     if ((err = gnbv_launch_status())) return err;
-    const bool dp = p->world > 1 && p->sync_sum != nullptr && p->sync_buf != nullptr;
-    if (dp && !(fused && p->autocorr_global != nullptr && saved_total)) return (int)hipErrorInvalidValue;  // (see GnbvEncoderParams.world)
-    const double *S2m = S2;  // the sums the elementwise BN2 backward uses: this replica's, or the global minibatch's
+    const double *S2m = w.S2;  // the sums the elementwise BN2 backward uses: this replica's, or the global minibatch's
     if (dp) {
-        if (hipMemcpyAsync(p->sync_buf + 2 * kC, S2, 2 * kC * sizeof(double), hipMemcpyDeviceToDevice, st) != hipSuccess) return (int)hipGetLastError();
+        if (hipMemcpyAsync(p->sync_buf + 2 * kC, w.S2, 2 * kC * sizeof(double), hipMemcpyDeviceToDevice, st) != hipSuccess) return (int)hipGetLastError();
         if ((err = p->sync_sum(p->sync_ctx, 2 * kC, 2 * kC, stream))) return err;
         S2m = p->sync_buf + 2 * kC;
     }
-    hipLaunchKernelGGL(k_bn2_bwd_apply, dim3(batch * ((P2 + 63) / 64)), dim3(256), 0, st, d_features, y2, bn2, bn2 + kC, bn2 + 2 * kC, bn2 + 3 * kC, S2m,
-                       (double)batch * P2 * (dp ? p->world : 1), P2, dy2_scratch, dy2_absmax);
+    hipLaunchKernelGGL(k_bn2_bwd_apply, dim3(pl.bn2_apply_grid), dim3(256), 0, st, d_features, y2, bn2, bn2 + kC, bn2 + 2 * kC, bn2 + 3 * kC, S2m,
+                       (double)batch * P2 * (dp ? p->world : 1), P2, dy2_scratch, w.dy2_absmax);
     if ((err = gnbv_launch_status())) return err;
-    // ---- conv2 weight gradient: on the side stream, beside the data gradient ----
-    // (running this kernel on a second stream beside the data gradient was measured slower: both are bound by the CU's
-    // vector-load path, profiles/r01_notes.md)
-    hipStream_t sw = st;
-    int nrows2 = batch * O2 * O2;
-    // (the fp32 kernel: FOUR rows per wave where there are fewer rows than 512 workgroups x 4 waves x 4 -- at the reference's 20^3 one row per
-    // wave made the launch its epilogue, 512 workgroup-level reductions and 14 MB of partial rows for 2 048 rows of four outputs: 128
-    // workgroups -2.9 us per minibatch, 64: -1.4; profiles/r06_ab_train_g20_wgrad_blocks*.json)
-    int wg_blocks = (nrows2 + 4 * kEncWaves - 1) / (4 * kEncWaves);
-    wg_blocks = wg_blocks > 512 ? 512 : ((wg_blocks + 7) & ~7);
-    const bool split_bwd = conv_split_path(p, grid);
-    if (conv_splitx_path(p, grid)) {
-        static bool attr_wx = false;
-        if (!attr_wx) {
-            hipError_t e = hipFuncSetAttribute((const void *)k_conv2_wgrad_splitx<true>, hipFuncAttributeMaxDynamicSharedMemorySize, splitx::kWgLdsBytes);
-            if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_conv2_wgrad_splitx<false>, hipFuncAttributeMaxDynamicSharedMemorySize, splitx::kWgLdsBytes);
-            if (e != hipSuccess) return (int)e;
-            attr_wx = true;
-        }
-        const int XT = (O2 + 15) / 16, nitems = splitx::items(batch, O2, XT);
-        // one item per workgroup while the partial buffer holds a row per item (2 048 rows of E2: the whole of wg_part -- the conv1 partials
-        // behind row 512 are written later on this stream, by the data gradient); else workgroups walk items (<= 512 rows)
-        const bool wx_loop = nitems > 2048 || splitx_max_wg() < 512;
-        wg_blocks = wx_loop ? min(nitems, splitx_max_wg()) : nitems;
-        if (wx_loop)
-            hipLaunchKernelGGL(k_conv2_wgrad_splitx<true>, dim3(wg_blocks), dim3(split::kThreads), splitx::kWgLdsBytes, sw, (const float *)y1, bn1, bn1 + kC,
-                               dy2_scratch, (const unsigned *)dy2_absmax, batch, O1, O2, XT, nitems, w.wg_part);
-        else
-            hipLaunchKernelGGL(k_conv2_wgrad_splitx<false>, dim3(wg_blocks), dim3(split::kThreads), splitx::kWgLdsBytes, sw, (const float *)y1, bn1, bn1 + kC,
-                               dy2_scratch, (const unsigned *)dy2_absmax, batch, O1, O2, XT, nitems, w.wg_part);
-    } else if (split_bwd) {
-        static bool attr_wg = false;
-        if (!attr_wg) {
-            const hipError_t e = hipFuncSetAttribute((const void *)k_conv2_wgrad_split, hipFuncAttributeMaxDynamicSharedMemorySize, split::kWgLdsBytes);
-            if (e != hipSuccess) return (int)e;
-            attr_wg = true;
-        }
-        wg_blocks = sample_plane_group_grid(batch, O2, split::kNP);
-        if (wgrad_dma_path()) {
-            // (round 6) the same contraction with y1 / dy2 streamed into LDS by LDS-DMA requests and converted in place: bit-identical
-            static bool attr_wd = false;
-            if (!attr_wd) {
-                const hipError_t e = hipFuncSetAttribute((const void *)k_conv2_wgrad_split_dma, hipFuncAttributeMaxDynamicSharedMemorySize, wdma::kLdsBytes);
-                if (e != hipSuccess) return (int)e;
-                attr_wd = true;
-            }
-            const int nitems = wg_blocks;
-            wg_blocks = min(nitems, conv_max_wg());  // (a workgroup walks items block, block + grid, ...: one workgroup per CU by default)
-            hipLaunchKernelGGL(k_conv2_wgrad_split_dma, dim3(wg_blocks), dim3(split::kThreads), wdma::kLdsBytes, sw, (const float *)y1, bn1, bn1 + kC, dy2_scratch,
-                               (const unsigned *)dy2_absmax, batch, O1, O2, nitems, w.wg_part);
-        } else
-        hipLaunchKernelGGL(k_conv2_wgrad_split, dim3(wg_blocks), dim3(split::kThreads), split::kWgLdsBytes, sw, (const float *)y1, bn1, bn1 + kC, dy2_scratch,
-                           (const unsigned *)dy2_absmax, batch, O1, O2, w.wg_part);
-    } else {
-        hipLaunchKernelGGL(k_conv2_wgrad<ActF32>, dim3(wg_blocks), dim3(kEncThreads), 0, sw, (const float *)y1, bn1, bn1 + kC, dy2_scratch, batch, O1, O2,
-                       w.wg_part);
+    // ---- conv2 weight gradient (on the same stream: beside the data gradient it was measured slower, both are bound by the CU's
+    // vector-load path, profiles/r01_notes.md) ----
+#define GNBV_WG2_ARGS (const float *)y1, bn1, bn1 + kC, dy2_scratch, (const unsigned *)w.dy2_absmax, batch, O1, O2
+    const dim3 gw(pl.wg_blocks), ts(split::kThreads);
+    switch (pl.wgrad2) {
+    case Wgrad2::SPLITX_LOOP:
+        if ((err = gnbv_raise_lds<k_conv2_wgrad_splitx<true>>(splitx::kWgLdsBytes, splitx::kWgLdsBytes))) return err;
+        hipLaunchKernelGGL(k_conv2_wgrad_splitx<true>, gw, ts, splitx::kWgLdsBytes, st, GNBV_WG2_ARGS, pl.XT, pl.wg_nitems, w.wg_part);
+        break;
+    case Wgrad2::SPLITX:
+        if ((err = gnbv_raise_lds<k_conv2_wgrad_splitx<false>>(splitx::kWgLdsBytes, splitx::kWgLdsBytes))) return err;
+        hipLaunchKernelGGL(k_conv2_wgrad_splitx<false>, gw, ts, splitx::kWgLdsBytes, st, GNBV_WG2_ARGS, pl.XT, pl.wg_nitems, w.wg_part);
+        break;
+    case Wgrad2::SPLIT_DMA:  // y1 / dy2 streamed into LDS by LDS-DMA requests and converted in place: bit-identical to SPLIT
+        if ((err = gnbv_raise_lds<k_conv2_wgrad_split_dma>(wdma::kLdsBytes, wdma::kLdsBytes))) return err;
+        hipLaunchKernelGGL(k_conv2_wgrad_split_dma, gw, ts, wdma::kLdsBytes, st, GNBV_WG2_ARGS, pl.wg_nitems, w.wg_part);
+        break;
+    case Wgrad2::SPLIT:
+        if ((err = gnbv_raise_lds<k_conv2_wgrad_split>(split::kWgLdsBytes, split::kWgLdsBytes))) return err;
+        hipLaunchKernelGGL(k_conv2_wgrad_split, gw, ts, split::kWgLdsBytes, st, GNBV_WG2_ARGS, w.wg_part);
+        break;
+    case Wgrad2::FP32:
+        hipLaunchKernelGGL(k_conv2_wgrad<ActF32>, gw, dim3(kEncThreads), 0, st, (const float *)y1, bn1, bn1 + kC, dy2_scratch, batch, O1, O2, w.wg_part);
+        break;
     }
+#undef GNBV_WG2_ARGS
     if ((err = gnbv_launch_status())) return err;
-    const int E2 = kTaps * 256 + kC;
-    // the conv1 weight gradient (main stream) uses its own partial / slice regions of the workspace
-    float *wg1_part = w.wg_part + (size_t)512 * E2;
-    double *tmp1 = w.tmp + (size_t)32 * E2;
-    {
-        const int sl2 = reduce_stage1(w.wg_part, wg_blocks, E2, w.tmp, sw);  // <= 16 slices: tmp[0, 16 E2)
-        if ((err = gnbv_launch_status())) return err;
-        // (the weight images ride in the finish launch)
-        hipLaunchKernelGGL(k_conv2_wgrad_finish, dim3((E2 + 255) / 256), dim3(256), 0, sw, (const double *)w.tmp, sl2, g->w2, g->b2,
-                           p->w2, w.w2img);
-        if ((err = gnbv_launch_status())) return err;
+    reduce_stage1(w.wg_part, pl.wg_blocks, kE2, pl.wg_slices, w.tmp, st);
+    if ((err = gnbv_launch_status())) return err;
+    // (the weight images ride in the finish launch)
+    hipLaunchKernelGGL(k_conv2_wgrad_finish, dim3((kE2 + 255) / 256), dim3(256), 0, st, (const double *)w.tmp, pl.wg_slices, g->w2, g->b2, p->w2, w.w2img);
+    if ((err = gnbv_launch_status())) return err;
+    // ---- conv2 data gradient (+ ReLU1 mask, BN1 backward sums; FUSED_*: + the conv1 weight gradient, dz1' never stored) ----
+#define GNBV_DGS_ARGS dy2_scratch, (const uint4 *)w.w2split_dgrad, (const float *)w.w2split_bounds, (const unsigned *)w.dy2_absmax, (const float *)y1, bn1,   \
+                      bn1 + kC, bn1 + 2 * kC, bn1 + 3 * kC, p->grid_i8, rows, p->grid_i8_row_stride, batch, grid, O1, O2
+    const dim3 gdg(pl.gd);
+    switch (pl.dgrad) {
+    case Dgrad::FUSED_SPLITX_LOOP:
+        if ((err = gnbv_raise_lds<k_conv2_dgrad_c1w_splitx<true>>(dsplit::kLdsBytes, dsplit::kLdsBytes))) return err;
+        hipLaunchKernelGGL(k_conv2_dgrad_c1w_splitx<true>, gdg, dim3(dsplit::kThreads), dsplit::kLdsBytes, st, GNBV_DGS_ARGS, pl.dg_XT, pl.dg_nitems, w.wg1_part);
+        break;
+    case Dgrad::FUSED_SPLITX:
+        if ((err = gnbv_raise_lds<k_conv2_dgrad_c1w_splitx<false>>(dsplit::kLdsBytes, dsplit::kLdsBytes))) return err;
+        hipLaunchKernelGGL(k_conv2_dgrad_c1w_splitx<false>, gdg, dim3(dsplit::kThreads), dsplit::kLdsBytes, st, GNBV_DGS_ARGS, pl.dg_XT, pl.dg_nitems, w.wg1_part);
+        break;
+    case Dgrad::FUSED_SPLIT:
+        if ((err = gnbv_raise_lds<k_conv2_dgrad_c1w_split>(dsplit::kLdsBytesT, dsplit::kLdsBytesT))) return err;
+        hipLaunchKernelGGL(k_conv2_dgrad_c1w_split, gdg, dim3(dsplit::kThreads), dsplit::kLdsBytesT, st, GNBV_DGS_ARGS, w.wg1_part);
+        break;
+    case Dgrad::FUSED_FP32:
+        hipLaunchKernelGGL(k_conv2_dgrad_c1w, gdg, dim3(kBigThreads), 0, st, dy2_scratch, (const float *)w.w2img_dgrad, (const float *)y1, bn1, bn1 + kC,
+                           bn1 + 2 * kC, bn1 + 3 * kC, p->grid_i8, rows, p->grid_i8_row_stride, batch, grid, O1, O2, w.wg1_part);
+        break;
+    case Dgrad::PLAIN:
+        hipLaunchKernelGGL(k_conv2_dgrad<ActF32>, gdg, dim3(kBigThreads), 0, st, dy2_scratch, (const float *)w.w2img_dgrad, (const float *)y1, bn1, bn1 + kC,
+                           bn1 + 2 * kC, bn1 + 3 * kC, batch, O1, O2, (float *)dz1_scratch, w.bn_part, pl.pzd);
+        break;
     }
-    // ---- conv2 data gradient (+ ReLU1 mask, BN1 backward sums) ----
-    int gd = sample_plane_group_grid(batch, (O1 + 1) / 2, kPlanesPerGroup);  // groups of plane PAIRS
-    // (the data gradient keeps four plane pairs per workgroup at every size: with two -- 384 workgroups at 20^3 -- or one -- 640 -- it took
-    // 20-21 us instead of 16: every workgroup starts by copying the 27 KiB weight image, and that prologue is what these launches are made of)
-    // What does help is BALANCE at the same number of workgroups: the plane pairs of a sample in ceil(NA / 4) groups of equal size -- at
-    // 20^3 (NA = 5) groups of 3 + 2 instead of 4 + 1: 15 super-tiles on a workgroup's 16 waves instead of 20, one round: -2.2 us per minibatch
-    // (five in one group: +3.5; profiles/r06_ab_train_g20_dgrad_pz.json).  NA = 16, 32 (G = 64, 128) stay at four.
-    const int nad = (O1 + 1) / 2, ngd = (nad + kPlanesPerGroup - 1) / kPlanesPerGroup;
-    const int pzd = fused ? kPlanesPerGroup : (nad + ngd - 1) / ngd;
-    if (!fused) gd = sample_plane_group_grid(batch, nad, pzd);
-    if (fused) {
-        if (conv_splitx_path(p, grid)) {
-            static bool attr_dx = false;
-            if (!attr_dx) {
-                hipError_t e = hipFuncSetAttribute((const void *)k_conv2_dgrad_c1w_splitx<true>, hipFuncAttributeMaxDynamicSharedMemorySize, dsplit::kLdsBytes);
-                if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_conv2_dgrad_c1w_splitx<false>, hipFuncAttributeMaxDynamicSharedMemorySize, dsplit::kLdsBytes);
-                if (e != hipSuccess) return (int)e;
-                attr_dx = true;
-            }
-            const int NA = (O1 + 1) / 2, XT = (NA + 15) / 16, nitems = dsplitx::items(batch, NA, XT);
-            // (one item per workgroup while wg1_part -- 1 536 rows of E2 floats -- holds a row of kE1F floats per item; else T1 / S1 / S2 are kept
-            // across a workgroup's items: <= 512 partial rows)
-            const bool dx_loop = (size_t)nitems * kE1F > (size_t)1536 * (kTaps * 256 + kC) || splitx_max_wg() < 512;
-            gd = dx_loop ? min(nitems, splitx_max_wg()) : nitems;
-#define GNBV_DGX_ARGS dim3(gd), dim3(dsplit::kThreads), dsplit::kLdsBytes, st, dy2_scratch, (const uint4 *)(w.w2split + split::kW2ImgU4),                    \
-                      (const float *)(w.w2split + split::kW2ImgU4 + dsplit::kImgSlotU4), (const unsigned *)dy2_absmax, (const float *)y1, bn1, bn1 + kC,        \
-                      bn1 + 2 * kC, bn1 + 3 * kC, p->grid_i8, rows, p->grid_i8_row_stride, batch, grid, O1, O2, XT, nitems, wg1_part
-            if (dx_loop)
-                hipLaunchKernelGGL(k_conv2_dgrad_c1w_splitx<true>, GNBV_DGX_ARGS);
-            else
-                hipLaunchKernelGGL(k_conv2_dgrad_c1w_splitx<false>, GNBV_DGX_ARGS);
-#undef GNBV_DGX_ARGS
-        } else if (split_bwd) {
-            static bool attr_dg = false;
-            if (!attr_dg) {
-                const hipError_t e = hipFuncSetAttribute((const void *)k_conv2_dgrad_c1w_split, hipFuncAttributeMaxDynamicSharedMemorySize, dsplit::kLdsBytesT);
-                if (e != hipSuccess) return (int)e;
-                attr_dg = true;
-            }
-            hipLaunchKernelGGL(k_conv2_dgrad_c1w_split, dim3(gd), dim3(dsplit::kThreads), dsplit::kLdsBytesT, st, dy2_scratch, (const uint4 *)(w.w2split + split::kW2ImgU4),
-                               (const float *)(w.w2split + split::kW2ImgU4 + dsplit::kImgSlotU4),
-                               (const unsigned *)dy2_absmax, (const float *)y1, bn1, bn1 + kC, bn1 + 2 * kC, bn1 + 3 * kC, p->grid_i8, rows, p->grid_i8_row_stride,
-                               batch, grid, O1, O2, wg1_part);
-        } else
-            hipLaunchKernelGGL(k_conv2_dgrad_c1w, dim3(gd), dim3(kBigThreads), 0, st, dy2_scratch, (const float *)(w.w2img + kTaps * 256), (const float *)y1, bn1,
-                               bn1 + kC, bn1 + 2 * kC, bn1 + 3 * kC, p->grid_i8, rows, p->grid_i8_row_stride, batch, grid, O1, O2, wg1_part);
-        if ((err = gnbv_launch_status())) return err;
-        const int slf = reduce_stage1(wg1_part, gd, kE1F, tmp1, st);
+#undef GNBV_DGS_ARGS
+    if ((err = gnbv_launch_status())) return err;
+    if (pl.wgrad1 == Wgrad1::FUSED) {
+        reduce_stage1(w.wg1_part, pl.gd, kE1F, pl.wg1_slices, w.tmp1, st);
         if ((err = gnbv_launch_status())) return err;
         if (dp) {  // BatchNorm-1 backward means over the global minibatch
-            hipLaunchKernelGGL(k_gather_bn1_sums, dim3(1), dim3(64), 0, st, (const double *)tmp1, slf, p->sync_buf + 4 * kC);
+            hipLaunchKernelGGL(k_gather_bn1_sums, dim3(1), dim3(64), 0, st, (const double *)w.tmp1, pl.wg1_slices, p->sync_buf + 4 * kC);
             if ((err = gnbv_launch_status())) return err;
             if ((err = p->sync_sum(p->sync_ctx, 4 * kC, 2 * kC, stream))) return err;
         }
-        hipLaunchKernelGGL(k_c1w_fused_finish, dim3(1), dim3(1024), 0, st, (const double *)tmp1, slf,
-                           saved_total ? (const int *)(bn_state + kBnStateFloats) : (p->autocorr ? (const int *)p->autocorr : (const int *)Rac),
-                           p->autocorr_row_stride, rows, (!saved_total && p->autocorr) ? batch : 0,
-                           p->w1, bn1, bn1 + 3 * kC, p->bn1_b, g->w1, g->b1, (const double *)S2, g->bn1_w,
+        const bool saved = pl.paths.saved_total;
+        hipLaunchKernelGGL(k_c1w_fused_finish, dim3(1), dim3(1024), 0, st, (const double *)w.tmp1, pl.wg1_slices,
+                           saved ? (const int *)(bn_state + kBnStateFloats) : (p->autocorr ? (const int *)p->autocorr : (const int *)w.Rac),
+                           p->autocorr_row_stride, rows, (!saved && p->autocorr) ? batch : 0,
+                           p->w1, bn1, bn1 + 3 * kC, p->bn1_b, g->w1, g->b1, (const double *)w.S2, g->bn1_w,
                            g->bn1_b, g->bn2_w, g->bn2_b, dp ? (const double *)(p->sync_buf + 4 * kC) : (const double *)nullptr,
                            dp ? (const int *)p->autocorr_global : (const int *)nullptr);
-        if ((err = gnbv_launch_status())) return err;
         return gnbv_launch_status();
     }
-    {
-        hipLaunchKernelGGL(k_conv2_dgrad<ActF32>, dim3(gd), dim3(kBigThreads), 0, st, dy2_scratch, (const float *)(w.w2img + kTaps * 256), (const float *)y1, bn1, bn1 + kC, bn1 + 2 * kC,
-                       bn1 + 3 * kC, batch, O1, O2, (float *)dz1_scratch, w.bn_part, pzd);
-    }
-    if ((err = gnbv_launch_status())) return err;
-    double *S1 = w.red + 192;
-    hipLaunchKernelGGL(k_stats_reduce, dim3(1), dim3(1024), 0, st, w.bn_part, gd, S1, 0.0, (const float *)nullptr, (const float *)nullptr, 0.0f,
+    hipLaunchKernelGGL(k_stats_reduce, dim3(1), dim3(1024), 0, st, w.bn_part, pl.gd, w.S1, 0.0, (const float *)nullptr, (const float *)nullptr, 0.0f,
                        0.0f, (float *)nullptr, (float *)nullptr, (int64_t *)nullptr, (const int *)nullptr, (float *)nullptr, (float *)nullptr,
                        (float *)nullptr, (float *)nullptr, (const float *)nullptr, (float *)nullptr);
     if ((err = gnbv_launch_status())) return err;
     // ---- conv1 weight gradient (BN1 backward fused) ----
-    int nrows1 = batch * O1 * O1;
-    // (five rows per wave below the cap, for the same reason as the conv2 weight gradient above: 20^3, 2 048 -> 520 workgroups -6.7 us per
-    // minibatch, 256: -4.2, 128: +4.3)
-    int wg1_blocks = (nrows1 + 5 * kEncWaves - 1) / (5 * kEncWaves);
-    wg1_blocks = wg1_blocks > 2048 ? 2048 : ((wg1_blocks + 7) & ~7);  // VGPR-light: 32 waves per CU hide the load latency
-    const size_t c1w_lds = (size_t)kEncWaves * (2 * ((O1 + 1) / 2) * kC + 9 * grid) * sizeof(float);
-    const int c1w_nr = (2 * ((O1 + 1) / 2) * kC + 255) / 256, c1w_ni = (9 * grid + 255) / 256;  // 16-byte requests per lane and row
-    const bool c1w_staged = obs_grid != nullptr && (grid % 4 == 0) && (row_stride % 4 == 0) && (((uintptr_t)obs_grid & 15) == 0) && c1w_lds <= 64 * 1024 &&
-                            c1w_nr <= 4 && c1w_ni <= 5;
-    if (p->grid_i8 != nullptr && grid % 16 == 0 && 9 * grid <= 1024 && p->grid_i8_row_stride % 16 == 0 &&
-               (((uintptr_t)p->grid_i8 & 15) == 0) && c1w_lds <= 64 * 1024 && c1w_nr <= 4) {
-#define GNBV_C1W8(NR)                                                                                                             \
-    hipLaunchKernelGGL((k_conv1_wgrad_lds<ActF32, NR, 1, int8_t>), dim3(wg1_blocks), dim3(kEncThreads), c1w_lds, st, p->grid_i8,  \
-                       rows, p->grid_i8_row_stride, (const float *)dz1_scratch, (const float *)y1, bn1, bn1 + 2 * kC,            \
-                       bn1 + 3 * kC, S1, (double)batch * O1 * O1 * O1, batch, grid, O1, wg1_part)
-        if (c1w_nr <= 1) GNBV_C1W8(1);
-        else if (c1w_nr <= 2) GNBV_C1W8(2);  // G = 64
+#define GNBV_C1W(KERNEL, LDS, SRC, STRIDE)                                                                                                    \
+    hipLaunchKernelGGL(KERNEL, dim3(pl.wg1_blocks), dim3(kEncThreads), LDS, st, SRC, rows, STRIDE, (const float *)dz1_scratch, (const float *)y1, bn1, \
+                       bn1 + 2 * kC, bn1 + 3 * kC, w.S1, (double)batch * O1 * O1 * O1, batch, grid, O1, w.wg1_part)
+#define GNBV_C1W8(NR) GNBV_C1W((k_conv1_wgrad_lds<ActF32, NR, 1, int8_t>), pl.c1w_lds, p->grid_i8, p->grid_i8_row_stride)
+#define GNBV_C1WF(NR, NI) GNBV_C1W((k_conv1_wgrad_lds<ActF32, NR, NI, float>), pl.c1w_lds, obs_grid, row_stride)
+    switch (pl.wgrad1) {
+    case Wgrad1::LDS_I8:
+        if (pl.NR == 1) GNBV_C1W8(1);
+        else if (pl.NR == 2) GNBV_C1W8(2);  // G = 64
         else GNBV_C1W8(4);
-#undef GNBV_C1W8
-    } else if (c1w_staged) {
-#define GNBV_C1W(NR, NI)                                                                                                          \
-    hipLaunchKernelGGL((k_conv1_wgrad_lds<ActF32, NR, NI, float>), dim3(wg1_blocks), dim3(kEncThreads), c1w_lds, st, obs_grid, rows,\
-                       row_stride, (const float *)dz1_scratch, (const float *)y1, bn1, bn1 + 2 * kC, bn1 + 3 * kC, S1,            \
-                       (double)batch * O1 * O1 * O1, batch, grid, O1, wg1_part)
-        if (c1w_nr <= 1 && c1w_ni <= 1) GNBV_C1W(1, 1);
-        else if (c1w_nr <= 1 && c1w_ni <= 2) GNBV_C1W(1, 2);
-        else if (c1w_nr <= 2 && c1w_ni <= 3) GNBV_C1W(2, 3);  // G = 64
-        else GNBV_C1W(4, 5);
-#undef GNBV_C1W
-    } else if (obs_grid == nullptr) {
-        hipLaunchKernelGGL((k_conv1_wgrad<ActF32, int8_t>), dim3(wg1_blocks), dim3(kEncThreads), 0, st, p->grid_i8, rows, p->grid_i8_row_stride,
-                           (const float *)dz1_scratch, (const float *)y1, bn1, bn1 + 2 * kC, bn1 + 3 * kC, S1, (double)batch * O1 * O1 * O1, batch,
-                           grid, O1, wg1_part);
-    } else {
-        hipLaunchKernelGGL(k_conv1_wgrad<ActF32>, dim3(wg1_blocks), dim3(kEncThreads), 0, st, obs_grid, rows, row_stride, (const float *)dz1_scratch, (const float *)y1, bn1,
-                       bn1 + 2 * kC, bn1 + 3 * kC, S1, (double)batch * O1 * O1 * O1, batch, grid, O1, wg1_part);
+        break;
+    case Wgrad1::LDS_F32:
+        if (pl.NI == 1) GNBV_C1WF(1, 1);
+        else if (pl.NI == 2) GNBV_C1WF(1, 2);
+        else if (pl.NI == 3) GNBV_C1WF(2, 3);  // G = 64
+        else GNBV_C1WF(4, 5);
+        break;
+    case Wgrad1::DIRECT_I8:
+        GNBV_C1W((k_conv1_wgrad<ActF32, int8_t>), 0, p->grid_i8, p->grid_i8_row_stride);
+        break;
+    default:
+        GNBV_C1W(k_conv1_wgrad<ActF32>, 0, obs_grid, row_stride);
+        break;
     }
+#undef GNBV_C1WF
+#undef GNBV_C1W8
+#undef GNBV_C1W
     if ((err = gnbv_launch_status())) return err;
-    const int E1 = 512 + kC;
-    const int sl1 = reduce_stage1(wg1_part, wg1_blocks, E1, tmp1, st);
+    reduce_stage1(w.wg1_part, pl.wg1_blocks, kE1, pl.wg1_slices, w.tmp1, st);
     if ((err = gnbv_launch_status())) return err;
     // (+ BN affine gradients: d beta = S[0], d gamma = S[1])
-    hipLaunchKernelGGL(k_conv1_wgrad_finish, dim3((E1 + 255) / 256), dim3(256), 0, st, (const double *)tmp1, sl1, g->w1, g->b1,
-                       (const double *)S1, (const double *)S2, g->bn1_w, g->bn1_b, g->bn2_w, g->bn2_b);
-    if ((err = gnbv_launch_status())) return err;
+    hipLaunchKernelGGL(k_conv1_wgrad_finish, dim3((kE1 + 255) / 256), dim3(256), 0, st, (const double *)w.tmp1, pl.wg1_slices, g->w1, g->b1,
+                       (const double *)w.S1, (const double *)w.S2, g->bn1_w, g->bn1_b, g->bn2_w, g->bn2_b);
     return gnbv_launch_status();
 }
 

@@ -186,7 +186,7 @@ template <bool kLds, bool kF32, bool kTell>
 int launch_map(const MapGrid &grid, const float *range_gt, const float *voxel_size, const MapArgs &a, int n, size_t lds,
                uint32_t *blocked_out, uint32_t *costly_out, hipStream_t stream)
 {
-    const int bad = map_raise_lds<k_flight_tri<kLds, kF32, kTell>>(lds);
+    const int bad = gnbv_raise_lds<k_flight_tri<kLds, kF32, kTell>>(lds, kMapLdsBytes);
     if (bad != 0) return bad;
     hipLaunchKernelGGL((k_flight_tri<kLds, kF32, kTell>), dim3((unsigned)(n * a.chunks)), dim3(kMapLanes), lds, stream, grid.base,
                        grid.row_bytes, range_gt, voxel_size, a, blocked_out, costly_out);

@@ -142,7 +142,7 @@ template <bool kF32>
 int launch_frontier(const MapGrid &grid, const FrontierArgs &a, int n, uint32_t *bits_out, int32_t *blocks_out, hipStream_t stream)
 {
     const size_t lds = 8 * (size_t)a.lds_words;
-    const int bad = map_raise_lds<k_frontier_tri<kF32>>(lds);
+    const int bad = gnbv_raise_lds<k_frontier_tri<kF32>>(lds, kMapLdsBytes);
     if (bad != 0) return bad;
     hipLaunchKernelGGL((k_frontier_tri<kF32>), dim3((unsigned)(n * a.chunks)), dim3(kFrontLanes), lds, stream, grid.base, grid.row_bytes, a,
                        bits_out, blocks_out);

@@ -179,7 +179,7 @@ __global__ __launch_bounds__(kViewLanes) void k_frontview(const void *__restrict
 template <bool kLds, bool kF32>
 int launch_view(const MapGrid &grid, const GnbvFrontView &a, const ViewArgs &A, size_t lds, hipStream_t stream)
 {
-    const int bad = map_raise_lds<k_frontview<kLds, kF32>>(lds);
+    const int bad = gnbv_raise_lds<k_frontview<kLds, kF32>>(lds, kMapLdsBytes);
     if (bad != 0) return bad;
     hipLaunchKernelGGL((k_frontview<kLds, kF32>), dim3((unsigned)(a.n * A.chunks)), dim3(kViewLanes), lds, stream, grid.base, grid.row_bytes,
                        a.range_gt, a.voxel_size, a.field, a.targets, A, a.node_out, a.cost_out, a.count_out);

@@ -661,7 +661,7 @@ GNBV_API size_t gnbv_linear_workspace_bytes(int M, int N, int K)
 namespace {
 inline bool split_kernels_on()
 {
-    const char *e = getenv("GENNBV_CONV_SPLIT");  // "0": the fp32-MFMA kernels everywhere (csrc/encoder.hip conv_split_path)
+    const char *e = getenv("GENNBV_CONV_SPLIT");  // "0": the fp32-MFMA kernels everywhere (csrc/encoder_plan.h EncSwitches::conv_split)
     return !(e && e[0] == '0');
 }
 }  // namespace

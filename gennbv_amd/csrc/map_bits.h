@@ -5,7 +5,7 @@
 //           (map_pack_bits: one plane; map_pack: the two-plane loop, with map_pack_planes and map_pack_window its callers); the
 //           swizzle; the bits of a word inside a run (map_span).
 //   host    the front end of the entry points: the grid forms resolved and checked (map_grid), the dynamic-LDS limit raised once
-//           per kernel (map_raise_lds), (lds, f32) turned into template arguments (map_dispatch), the workgroups of an env
+//           per kernel (gnbv_raise_lds, common.h), (lds, f32) turned into template arguments (map_dispatch), the workgroups of an env
 //           (map_chunks), the geometry of a flight lattice (lattice_ok: flight.hip uses it too).
 //   The fp64 voxel frame these kernels place the grid with is voxel_frame.h's (voxel_frame_f64).
 //
@@ -193,19 +193,6 @@ static inline int map_grid(const int8_t *tri_i8, int64_t tri_i8_row_stride, cons
     grid->base = f32 ? static_cast<const void *>(tri_f32) : static_cast<const void *>(tri_i8);
     grid->row_bytes = f32 ? 4 * tri_f32_row_stride : tri_i8_row_stride;
     grid->f32 = f32;
-    return 0;
-}
-
-// A launch may ask for 64 KiB of dynamic LDS without the attribute; the first launch of kKernel that asks for more raises its limit
-// to kMapLdsBytes.  Keyed on the kernel itself, not on its type: the <kLds, kF32> instantiations of a kernel share one function type.
-template <auto kKernel>
-int map_raise_lds(size_t lds_bytes)
-{
-    static bool raised = false;
-    if (lds_bytes <= 64 * 1024 || raised) return 0;
-    const hipError_t err = hipFuncSetAttribute((const void *)kKernel, hipFuncAttributeMaxDynamicSharedMemorySize, kMapLdsBytes);
-    if (err != hipSuccess) return (int)err;
-    raised = true;
     return 0;
 }
 

@@ -232,7 +232,7 @@ template <bool kLds, bool kF32>
 int launch_sweep(const MapGrid &grid, const float *range_gt, const float *voxel_size, const float *from, const float *to, const SweepMapArgs &A,
                  int n, size_t lds, uint8_t *code_out, hipStream_t stream)
 {
-    const int bad = map_raise_lds<k_sweep_tri<kLds, kF32>>(lds);
+    const int bad = gnbv_raise_lds<k_sweep_tri<kLds, kF32>>(lds, kMapLdsBytes);
     if (bad != 0) return bad;
     hipLaunchKernelGGL((k_sweep_tri<kLds, kF32>), dim3((unsigned)(n * A.chunks)), dim3(kSweepLanes), lds, stream, grid.base, grid.row_bytes,
                        range_gt, voxel_size, from, to, A, code_out);

@@ -2037,19 +2037,6 @@ static int with_bool(bool flag, F &&f)
     return flag ? f(std::true_type{}) : f(std::false_type{});
 }
 
-// A launch may ask for 64 KiB of dynamic LDS without the attribute; the first launch of kKernel that asks for more raises its limit
-// to the whole 160 KiB.
-template <auto kKernel>
-static int raise_lds(size_t lds_bytes)
-{
-    static bool raised = false;
-    if (lds_bytes <= 64 * 1024 || raised) return 0;
-    if (hipFuncSetAttribute((const void *)kKernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kVoxelLdsMax) != hipSuccess)
-        return (int)hipGetLastError();
-    raised = true;
-    return 0;
-}
-
 // what the three entry points share
 struct VoxelInputs {
     const float *depth_raw, *seg_raw, *c2w, *inv_intri, *poses_xyz;
@@ -2099,13 +2086,13 @@ static int masks_list(const VoxelInputs &in, const Intrinsics &K, bool kfast, co
     const VoxelMaskPlan &p = vc.plan;
     int err = with_bool(kfast, [&](auto kFast) {
         constexpr bool KF = decltype(kFast)::value;
-        if (const int bad = raise_lds<k_hit_list<KF>>(p.list_lds)) return bad;
+        if (const int bad = gnbv_raise_lds<k_hit_list<KF>>(p.list_lds, (int)kVoxelLdsMax)) return bad;
         hipLaunchKernelGGL((k_hit_list<KF>), dim3(p.hit_grid), dim3(kFusedThreads), p.list_lds, vc.st, in.depth_raw, in.seg_raw, in.c2w, K,
                            in.range_gt, in.voxel_size, in.n, in.h, in.w, in.g, in.depth_sense_dist, p.fchunks, p.words, ws.hit, ws.ray_count,
                            ws.ray_list, ws.ray_cap, in.coverage_count);
         return gnbv_launch_status();
     });
-    if (err || (err = raise_lds<k_ray_list>(p.ray_list_lds))) return err;
+    if (err || (err = gnbv_raise_lds<k_ray_list>(p.ray_list_lds, (int)kVoxelLdsMax))) return err;
     hipLaunchKernelGGL(k_ray_list, dim3(p.ray_grid), dim3(kListThreads), p.ray_list_lds, vc.st, ws.ray_count, ws.ray_list, ws.ray_cap,
                        in.poses_xyz, in.poses_row_stride, in.range_gt, in.voxel_size, in.n, in.g, p.words, ws.path);
     return gnbv_launch_status();
@@ -2122,7 +2109,7 @@ static int masks_large(const VoxelInputs &in, const Intrinsics &K, bool kfast, c
                            ws.ray_count, ws.ray_list, ws.ray_cap, in.coverage_count);
         return gnbv_launch_status();
     });
-    if (err || (err = raise_lds<k_ray_slab>(p.slab_lds))) return err;
+    if (err || (err = gnbv_raise_lds<k_ray_slab>(p.slab_lds, (int)kVoxelLdsMax))) return err;
     hipLaunchKernelGGL(k_ray_slab, dim3(p.ray_grid), dim3(kSlabThreads), p.slab_lds, vc.st, ws.ray_count, ws.ray_list, ws.ray_cap,
                        in.poses_xyz, in.poses_row_stride, in.range_gt, in.voxel_size, in.n, in.g, p.words, p.slabs, p.slab_planes,
                        p.slab_slices, ws.path);
@@ -2137,7 +2124,7 @@ static int masks_round1(const VoxelInputs &in, const Intrinsics &K, bool kfast, 
     int err = with_bool(p.hit_windows > 1, [&](auto kWin) {
         return with_bool(kfast, [&](auto kFast) {
             constexpr bool KF = decltype(kFast)::value, WIN = decltype(kWin)::value;
-            if (const int bad = raise_lds<k_hit_mask<KF, WIN>>(p.hit_lds)) return bad;
+            if (const int bad = gnbv_raise_lds<k_hit_mask<KF, WIN>>(p.hit_lds, (int)kVoxelLdsMax)) return bad;
             hipLaunchKernelGGL((k_hit_mask<KF, WIN>), dim3(p.hit_grid), dim3(kHitThreads), p.hit_lds, vc.st, in.depth_raw, in.seg_raw, in.c2w,
                                K, in.range_gt, in.voxel_size, in.n, in.h, in.w, in.g, in.depth_sense_dist, p.chunks, p.words, ws.hit,
                                p.hit_windows, p.hit_nw);
@@ -2147,7 +2134,7 @@ static int masks_round1(const VoxelInputs &in, const Intrinsics &K, bool kfast, 
     if (err) return err;
     return with_bool(p.path_windows > 1, [&](auto kWin) {
         constexpr bool WIN = decltype(kWin)::value;
-        if (const int bad = raise_lds<k_raycast<true, WIN>>(p.path_lds)) return bad;
+        if (const int bad = gnbv_raise_lds<k_raycast<true, WIN>>(p.path_lds, (int)kVoxelLdsMax)) return bad;
         hipLaunchKernelGGL((k_raycast<true, WIN>), dim3(p.ray_grid), dim3(kRayThreads), p.path_lds, vc.st, ws.hit, in.poses_xyz,
                            in.poses_row_stride, in.range_gt, in.voxel_size, in.n, in.g, p.words, p.splits, ws.path, p.path_windows, p.path_nw);
         return gnbv_launch_status();
