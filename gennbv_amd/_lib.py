@@ -174,7 +174,8 @@ class GnbvViewGain(C.Structure):
     """include/gennbv_hip.h: GnbvViewGain"""
     _fields_ = [("n", _i), ("k", _i), ("g", _i), ("tri_i8", _p), ("tri_row_stride", _i64), ("poses", _p), ("range_gt", _p),
                 ("voxel_size", _p), ("inv_intri", _p), ("h", _i), ("w", _i), ("stride", _i), ("range", _f), ("gain", _p),
-                ("c2w_out", _p), ("chunk", _i), ("ablate", _i)]
+                ("c2w_out", _p), ("chunk", _i), ("ablate", _i), ("depth_raw", _p), ("depth_env_stride", _i64),
+                ("depth_cand_stride", _i64), ("depth_sense_dist", _f), ("carve_i8", _p), ("carve_row_stride", _i64)]
 
 
 class GnbvFrontView(C.Structure):

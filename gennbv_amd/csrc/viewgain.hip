@@ -25,6 +25,12 @@
 //
 //   k_vg_prep, k_vg_fate, k_vg_slab   the same integers for grids up to 128^3 (gnbv_view_gain_slab), and in their <true> forms
 //     the same two masks (gnbv_view_gain_slab_masks): further down.
+//
+//   k_view_carve, k_vg_fate_depth, k_vg_carve_slab   the view gain of a MEASURED frame (GnbvViewGain depth_raw != NULL; DESIGN.md
+//     "Free space along every ray"): the same bodies compiled with DEPTH.  A ray ends where its pixel's raw depth says
+//     (ray_target_depth), a surface-ended ray leaves the line's last step -- its target voxel, where the surface is -- unmarked,
+//     and after a candidate's counts every voxel of mask A may be stored as -1 into the caller's carve row (carve_quad: a lane
+//     scatters the quads it is about to clear).  Kernels of their own names: the ones above are the code they were.
 #include <cmath>
 #include <type_traits>
 
@@ -112,13 +118,48 @@ __device__ __forceinline__ void ray_target(const VgBase &p, const float *M, cons
     voxel_of(wp, f, ix);
 }
 
+// The view gain of a MEASURED frame (GnbvViewGain depth_raw != NULL; include/gennbv_hip.h has the rule): a lattice ray ends where
+// its pixel's raw depth says, and the voxels it marked may be carved into an int8 row.  Compile-time variants under names of their
+// own (k_view_carve, k_vg_fate_depth, k_vg_carve_slab): the kernels without a depth image are the code they were.
+struct VgDepth {
+    const float *depth;  // candidate j of env e: depth + e env_stride + j cand_stride, [h, w] row-major
+    int64_t env_stride, cand_stride;
+    float sense;         // the updater's depth_sense_dist (< 0)
+    int w;
+    int8_t *carve;       // [n, g^3] rows, row stride in bytes, or NULL
+    int64_t carve_stride;
+};
+
+// the same for a measured ray; returns whether the ray is surface-ended (its target voxel then holds the surface)
+__device__ __forceinline__ bool ray_target_depth(const VgBase &p, const VgDepth &d, const float *img, const float *M, const VgFrame &f,
+                                                 int r, int *ix)
+{
+    const int iv = r / p.nu, u = lattice_pixel(r - iv * p.nu, p.stride), v = lattice_pixel(iv, p.stride);
+    const float raw = img[(size_t)v * d.w + u], len = fabsf(raw);
+    // finite, not +-0, above the clamp (process_depth keeps it) and within range; NaN fails every comparison
+    const bool surface = len <= FLT_MAX && raw != 0.0f && raw > d.sense && len <= p.range;
+    float wp[3];
+    pixel_to_world(surface ? len : p.range, (float)u, (float)v, p.kinv, M, wp);
+    voxel_of(wp, f, ix);
+    return surface;
+}
+
+// row[bit] = -1 for every set bit of a quad of a visited mask; `bit0` is the quad's first bit
+__device__ __forceinline__ void carve_quad(int8_t *row, const uint4 &q, int bit0)
+{
+    const uint32_t w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+        for (uint32_t m = w[t]; m != 0u; m &= m - 1u) row[bit0 + 32 * t + __builtin_ctz(m)] = (int8_t)-1;
+}
+
 __device__ __forceinline__ void clear_quads(uint4 *s, int quads)
 {
     for (int w = threadIdx.x; w < quads; w += blockDim.x) s[w] = make_uint4(0u, 0u, 0u, 0u);
 }
 
-template <bool MASKS>
-__global__ __launch_bounds__(kViewMaxThreads) void k_view_gain(VgParams p)
+template <bool MASKS, bool DEPTH>
+__device__ __forceinline__ void view_gain_body(const VgParams &p, const VgDepth &d)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t s_mem[];
     __shared__ float s_cam[kCamBatch][16];
@@ -156,15 +197,21 @@ __global__ __launch_bounds__(kViewMaxThreads) void k_view_gain(VgParams p)
         // ---- 2b / 3. one ray per lane
         const int x0 = s_src[slot][0], y0 = s_src[slot][1], z0 = s_src[slot][2];
         int cnt[3] = {0, 0, 0};  // unknown voxels, those of the stopped rays, stopped rays
+        const float *img = nullptr;
+        if constexpr (DEPTH) img = d.depth + (size_t)e * d.env_stride + (size_t)j * d.cand_stride;
         for (int r = tid; r < p.nrays; r += nthreads) {
             int t[3];
-            ray_target(p, s_cam[slot], f, r, t);
+            bool surface = false;
+            if constexpr (DEPTH) surface = ray_target_depth(p, d, img, s_cam[slot], f, r, t);
+            else ray_target(p, s_cam[slot], f, r, t);
             const RayWalk rw = make_walk(x0, y0, z0, t[0], t[1], t[2], g);
             if (rw.n == 0) continue;
+            const int skip = surface ? (rw.two_da >> 1) - rw.i0 : -1;  // the line's last step is the target voxel: a surface is there
             auto walk_into = [&](uint32_t *mask, int &count, bool marking) {
-                return run_walk(rw, g, [&](int lin, int) {
+                return run_walk(rw, g, [&](int lin, int i) {
                     const uint32_t cls = grid_class(s_grid, lin);
                     if (cls == 1u) return true;
+                    if (DEPTH && i == skip) return false;
                     if (cls == 0u && marking) count += mark_first(mask, lin);
                     return false;
                 });
@@ -180,6 +227,14 @@ __global__ __launch_bounds__(kViewMaxThreads) void k_view_gain(VgParams p)
         if (tid == 0) {
             int32_t *o = p.gain + ((size_t)e * p.k + j) * 3;
             o[0] = cnt[0]; o[1] = cnt[1]; o[2] = cnt[2];
+        }
+        // ---- 4b. carve: every voxel of mask A becomes free in the caller's row.  A lane reads the quads it clears in step 5.
+        //          With carve == tri (k == 1: this workgroup owns the env) the row was packed in step 1, two barriers ago
+        if constexpr (DEPTH) {
+            if (d.carve != nullptr) {
+                int8_t *crow = d.carve + (size_t)e * d.carve_stride;
+                for (int q = tid; q < row_quads; q += nthreads) carve_quad(crow, s_masks4[q], 128 * q);
+            }
         }
         // ---- 5. clear the masks for the next candidate (ordered in front of its rays by the barrier at the loop's head, which
         //         also is the barrier block_sum leaves to its caller)
@@ -205,6 +260,18 @@ __global__ __launch_bounds__(kViewMaxThreads) void k_view_gain(VgParams p)
             if (j + 1 < j1 && mark) clear_quads(s_masks4, 2 * row_quads);
         }
     }
+}
+
+template <bool MASKS>
+__global__ __launch_bounds__(kViewMaxThreads) void k_view_gain(VgParams p)
+{
+    view_gain_body<MASKS, false>(p, VgDepth{});
+}
+
+template <bool MASKS>
+__global__ __launch_bounds__(kViewMaxThreads) void k_view_carve(VgParams p, VgDepth d)
+{
+    view_gain_body<MASKS, true>(p, d);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -318,7 +385,8 @@ __global__ __launch_bounds__(256) void k_vg_prep(VsArgs<MASKS> p, int e0, int ne
     }
 }
 
-__global__ __launch_bounds__(kFateThreads) void k_vg_fate(VsParams p, int e0, int ne)
+template <bool DEPTH>
+__device__ __forceinline__ void vg_fate_body(const VsParams &p, const VgDepth &d, int e0, int ne)
 {
     __shared__ int s_part[kFateThreads / kWave][1];
     int rem;  // (candidate, ray block)
@@ -334,13 +402,20 @@ __global__ __launch_bounds__(kFateThreads) void k_vg_fate(VsParams p, int e0, in
     int cnt[1] = {0};  // stopped rays
     if (r < p.nrays) {
         int t[3];
-        ray_target(p, M, vg_frame(p, e), r, t);
+        bool surface = false;
+        if constexpr (DEPTH)
+            surface = ray_target_depth(p, d, d.depth + (size_t)e * d.env_stride + (size_t)j * d.cand_stride, M, vg_frame(p, e), r, t);
+        else ray_target(p, M, vg_frame(p, e), r, t);
         const RayWalk rw = make_walk(src[0], src[1], src[2], t[0], t[1], t[2], g);
+        // a surface-ended ray leaves its target voxel, the line's last step, out of the record (a surface is there): the
+        // recorded steps stay contiguous and k_vg_slab needs no word of it
+        const int skip = surface && rw.n > 0 ? (rw.two_da >> 1) - rw.i0 : -1;
         int first = 0, last = -1, lin_first = 0, lin_last = 0;
         bool blocked = false;
         if (rw.n > 0)
             blocked = run_walk(rw, g, [&](int lin, int i) {
                 if (grid_class(G, lin) == 1u) return true;
+                if (DEPTH && i == skip) return false;
                 if (last < 0) { first = i; lin_first = lin; }
                 last = i; lin_last = lin;
                 return false;
@@ -355,8 +430,18 @@ __global__ __launch_bounds__(kFateThreads) void k_vg_fate(VsParams p, int e0, in
     if (tid == 0 && cnt[0] != 0) atomicAdd(p.gain + ((size_t)e * p.k + j) * 3 + 2, cnt[0]);
 }
 
-template <bool MASKS>
-__global__ __launch_bounds__(kViewMaxThreads) void k_vg_slab(VsArgs<MASKS> p, int e0, int ne)
+__global__ __launch_bounds__(kFateThreads) void k_vg_fate(VsParams p, int e0, int ne)
+{
+    vg_fate_body<false>(p, VgDepth{}, e0, ne);
+}
+
+__global__ __launch_bounds__(kFateThreads) void k_vg_fate_depth(VsParams p, VgDepth d, int e0, int ne)
+{
+    vg_fate_body<true>(p, d, e0, ne);
+}
+
+template <bool MASKS, bool DEPTH>
+__device__ __forceinline__ void vg_slab_body(const VsArgs<MASKS> &p, const VgDepth &d, int e0, int ne)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t s_mem[];
     __shared__ int s_part[kViewMaxThreads / kWave][2];
@@ -414,6 +499,13 @@ __global__ __launch_bounds__(kViewMaxThreads) void k_vg_slab(VsArgs<MASKS> p, in
             if (cnt[0] != 0) atomicAdd(o, cnt[0]);
             if (cnt[1] != 0) atomicAdd(o + 1, cnt[1]);
         }
+        // carve: the slab's voxels of mask A (bit lin + sh) become free in the caller's row; a lane reads the quads it clears below
+        if constexpr (DEPTH) {
+            if (d.carve != nullptr) {
+                int8_t *crow = d.carve + (size_t)e * d.carve_stride + (size_t)X0 * gg - sh;
+                for (int q = tid; q < (int)((sh + svox + 127) >> 7); q += nthreads) carve_quad(crow, s_masks4[q], 128 * q);
+            }
+        }
         // (ordered in front of the next candidate's rays by the barrier at the loop's head, as in k_view_gain)
         if constexpr (MASKS) {
             // store, then clear: a lane clears the quads it stored, so no barrier between the two.  The slab's bits are
@@ -450,6 +542,18 @@ __global__ __launch_bounds__(kViewMaxThreads) void k_vg_slab(VsArgs<MASKS> p, in
             if (j + 1 < j1 && mark) clear_quads(s_masks4, 2 * row_quads);
         }
     }
+}
+
+template <bool MASKS>
+__global__ __launch_bounds__(kViewMaxThreads) void k_vg_slab(VsArgs<MASKS> p, int e0, int ne)
+{
+    vg_slab_body<MASKS, false>(p, VgDepth{}, e0, ne);
+}
+
+template <bool MASKS>
+__global__ __launch_bounds__(kViewMaxThreads) void k_vg_carve_slab(VsArgs<MASKS> p, VgDepth d, int e0, int ne)
+{
+    vg_slab_body<MASKS, true>(p, d, e0, ne);
 }
 
 // what both host entry points of the slab path derive from the sizes
@@ -495,6 +599,27 @@ bool view_gain_args_ok(const GnbvViewGain &a, int max_grid)
            a.tri_row_stride >= (int64_t)a.g * a.g * a.g;
 }
 
+// the measured-frame fields (depth_raw NULL: only carve_i8 is looked at, and refused).  `lds`: the one-launch kernel, where a
+// carve row may be the tri row only with one workgroup per env (k == 1); the slab path packs every grid in a launch of its own
+bool depth_args_ok(const GnbvViewGain &a, bool lds)
+{
+    if (a.depth_raw == nullptr) return a.carve_i8 == nullptr;
+    const int64_t hw = (int64_t)a.h * a.w, g3 = (int64_t)a.g * a.g * a.g;
+    if (a.depth_env_stride < hw || !(a.depth_cand_stride >= hw || (a.depth_cand_stride == 0 && a.k == 1))) return false;
+    if (!(std::isfinite(a.depth_sense_dist) && a.depth_sense_dist < 0.0f)) return false;
+    if (a.carve_i8 == nullptr) return true;
+    if (a.ablate != 0 || a.carve_row_stride < g3) return false;
+    if (a.carve_i8 == a.tri_i8 && a.carve_row_stride == a.tri_row_stride) return !lds || a.k == 1;
+    const uintptr_t t0 = (uintptr_t)a.tri_i8, t1 = t0 + (uintptr_t)(a.n - 1) * (uintptr_t)a.tri_row_stride + (uintptr_t)g3;
+    const uintptr_t c0 = (uintptr_t)a.carve_i8, c1 = c0 + (uintptr_t)(a.n - 1) * (uintptr_t)a.carve_row_stride + (uintptr_t)g3;
+    return c1 <= t0 || t1 <= c0;
+}
+
+VgDepth vg_depth(const GnbvViewGain &a)
+{
+    return {a.depth_raw, a.depth_env_stride, a.depth_cand_stride, a.depth_sense_dist, a.w, a.carve_i8, a.carve_row_stride};
+}
+
 // the mask arguments of gnbv_view_gain_masks and gnbv_view_gain_slab_masks
 bool mask_args_ok(const GnbvViewGain &a, int words, const int32_t *unknown_bits, const int32_t *hit_bits)
 {
@@ -527,7 +652,7 @@ int view_gain_impl(const GnbvViewGain *args, int words, int32_t *unknown_bits, i
 {
     GNBV_CHECK_ARG(args != nullptr);
     const GnbvViewGain a = *args;
-    GNBV_CHECK_ARG(view_gain_args_ok(a, kMaxGrid));
+    GNBV_CHECK_ARG(view_gain_args_ok(a, kMaxGrid) && depth_args_ok(a, true));
     if (MASKS) GNBV_CHECK_ARG(mask_args_ok(a, words, unknown_bits, hit_bits));
     VgParams p;
     // candidates per workgroup: enough workgroups for two per compute unit, but the grid is packed once per workgroup
@@ -540,8 +665,14 @@ int view_gain_impl(const GnbvViewGain *args, int words, int32_t *unknown_bits, i
     p.hit_bits = MASKS ? reinterpret_cast<uint32_t *>(hit_bits) : nullptr;
     p.words = MASKS ? words : 0;
     const size_t lds = (size_t)(p.grid_words + 2 * p.mask_words) * sizeof(uint32_t);
+    const dim3 grid((unsigned)(a.n * p.chunks)), block(view_threads(p.nrays, lds));
+    if (a.depth_raw != nullptr) {
+        if (!view_raise_lds(k_view_carve<MASKS>, lds)) return (int)hipGetLastError();
+        hipLaunchKernelGGL(k_view_carve<MASKS>, grid, block, lds, gnbv_stream(stream), p, vg_depth(a));
+        return gnbv_launch_status();
+    }
     if (!view_raise_lds(k_view_gain<MASKS>, lds)) return (int)hipGetLastError();
-    hipLaunchKernelGGL(k_view_gain<MASKS>, dim3((unsigned)(a.n * p.chunks)), dim3(view_threads(p.nrays, lds)), lds, gnbv_stream(stream), p);
+    hipLaunchKernelGGL(k_view_gain<MASKS>, grid, block, lds, gnbv_stream(stream), p);
     return gnbv_launch_status();
 }
 
@@ -552,7 +683,7 @@ int view_gain_slab_impl(const GnbvViewGain *args, int slab, void *workspace, siz
 {
     GNBV_CHECK_ARG(args != nullptr);
     const GnbvViewGain a = *args;
-    GNBV_CHECK_ARG(view_gain_args_ok(a, kMaxSlabGrid) && slab >= 0);
+    GNBV_CHECK_ARG(view_gain_args_ok(a, kMaxSlabGrid) && depth_args_ok(a, false) && slab >= 0);
     VsPlan pl;
     GNBV_CHECK_ARG(vs_plan(a.n, a.k, a.g, a.h, a.w, a.stride, pl));
     GNBV_CHECK_ARG(workspace != nullptr && workspace_bytes >= pl.bytes && ((uintptr_t)workspace & 15) == 0);
@@ -590,7 +721,9 @@ int view_gain_slab_impl(const GnbvViewGain *args, int slab, void *workspace, siz
     }
     const int threads = view_threads(p.nrays, lds);
     hipStream_t st = gnbv_stream(stream);
-    if (!view_raise_lds(k_vg_slab<MASKS>, lds)) return (int)hipGetLastError();
+    const bool measured = a.depth_raw != nullptr;
+    const VgDepth d = vg_depth(a);
+    if (!(measured ? view_raise_lds(k_vg_carve_slab<MASKS>, lds) : view_raise_lds(k_vg_slab<MASKS>, lds))) return (int)hipGetLastError();
     for (int e0 = 0; e0 < a.n; e0 += pl.batch) {  // the workspace is reused: the stream orders the batches
         const int ne = a.n - e0 < pl.batch ? a.n - e0 : pl.batch, ne_pad = (ne + 7) / 8 * 8;
         int64_t items = (int64_t)ne * pl.pack_words;
@@ -599,8 +732,14 @@ int view_gain_slab_impl(const GnbvViewGain *args, int slab, void *workspace, siz
             if ((int64_t)ne * a.k * p.zero_words > items) items = (int64_t)ne * a.k * p.zero_words;
         hipLaunchKernelGGL(k_vg_prep<MASKS>, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, p, e0, ne);
         if (p.nrays == 0) continue;
-        hipLaunchKernelGGL(k_vg_fate, dim3((unsigned)(ne_pad * a.k * p.rblocks)), dim3(kFateThreads), 0, st, p, e0, ne);
-        hipLaunchKernelGGL(k_vg_slab<MASKS>, dim3((unsigned)(ne_pad * p.chunks * p.nslab)), dim3(threads), lds, st, p, e0, ne);
+        const dim3 fate_grid((unsigned)(ne_pad * a.k * p.rblocks)), slab_grid((unsigned)(ne_pad * p.chunks * p.nslab));
+        if (measured) {
+            hipLaunchKernelGGL(k_vg_fate_depth, fate_grid, dim3(kFateThreads), 0, st, p, d, e0, ne);
+            hipLaunchKernelGGL(k_vg_carve_slab<MASKS>, slab_grid, dim3(threads), lds, st, p, d, e0, ne);
+            continue;
+        }
+        hipLaunchKernelGGL(k_vg_fate, fate_grid, dim3(kFateThreads), 0, st, p, e0, ne);
+        hipLaunchKernelGGL(k_vg_slab<MASKS>, slab_grid, dim3(threads), lds, st, p, e0, ne);
     }
     return gnbv_launch_status();
 }

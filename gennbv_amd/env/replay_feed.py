@@ -54,6 +54,13 @@ penalised field's; `flight_length` still counts metres -- the Euclidean lengths 
 holds penalties -- and `route_unknown` [N] int64 is the number of costly nodes entered on the route flown this step: the flown
 route nodes but the first, the node the drone already sat at (0 on an episode's first pose and without a route; None for
 other fields).
+
+`carve=CarvedMap(...)` (ops/carve.py; closed-loop feeds only: an open-loop feed's camera is not the pose's matrix) keeps a
+second map beside the observation: after the voxel update of each step the env calls carve.update(the tri just written, the
+frame's raw depth, self.poses, self.reset_mask), `env.map_tri` is carve.map_i8 (None without carve), and a BeliefFlightField is
+refreshed from it instead of the observation's grid.  Nothing else in the step changes: observation rows, rewards, dones and
+the update's outputs are byte-identical to the same env without `carve`.  The planners of eval/baselines.py that score or route
+on the tri-class grid read `env.map_tri` (planning_grid).
 """
 from __future__ import annotations
 
@@ -131,7 +138,7 @@ class ReplayFeedEnv:
 
     def __init__(self, cfg: TaskConfig, scene: S.Scene, feed, device="cuda:0",
                  max_episode_length: Optional[int] = None, inv_intrinsics: Optional[torch.Tensor] = None,
-                 collision=None, collision_mesh=None, flight=None):
+                 collision=None, collision_mesh=None, flight=None, carve=None):
         self.lib = _lib.load()
         self.cfg = cfg
         self.device = torch.device(device)
@@ -143,6 +150,15 @@ class ReplayFeedEnv:
         self.closed_loop = bool(getattr(feed, "closed_loop", False))
         n = scene.grid_gt.shape[0]
         self.num_envs = n
+        # free space along every camera ray (module docstring): None keeps every launch of the env as it was
+        if carve is not None:
+            if not self.closed_loop:
+                raise _lib.GennbvHipError("carve needs a closed-loop feed: an open-loop feed's camera is not the pose's matrix")
+            if carve.num_envs != n or int(carve.g) != int(cfg.grid_size) or (carve.h, carve.w) != (cfg.camera_height, cfg.camera_width):
+                raise ValueError(f"carve is built for {carve.num_envs} envs, a {carve.g}^3 grid and a {carve.h} x {carve.w} camera; the "
+                                 f"env has {n}, {cfg.grid_size}^3 and {cfg.camera_height} x {cfg.camera_width}")
+        self.carve = carve
+        self.map_tri = carve.map_i8 if carve is not None else None
         # collision termination (check_termination's collision_buf): None keeps the replay feed's "no contacts"
         self.collision = collision
         self.collision_mesh = None
@@ -336,9 +352,12 @@ class ReplayFeedEnv:
             self.updater.update(depth_raw, seg_raw, c2w, self.poses, reset_mask=self.reset_mask,
                                 tri_out=obs[:, cfg.state_dim:], tri_row_stride=stride,
                                 tri_i8_out=grid_i8_out if self.updater.coded else None)
+        wrote_i8 = grid_i8_out is not None and (compact or self.updater.coded)
+        tri_written = grid_i8_out if wrote_i8 else obs[:, cfg.state_dim:cfg.state_dim + cfg.grid_dim]
+        if self.carve is not None:  # the observation's grid plus the free space along every ray of the frame it was written from
+            self.carve.update(tri_written, depth_raw, self.poses, self.reset_mask)
         if self._belief:  # what the pilot knows next step: the map just written, from the poses just arrived at
-            wrote_i8 = grid_i8_out is not None and (compact or self.updater.coded)
-            self.flight.refresh(grid_i8_out if wrote_i8 else obs[:, cfg.state_dim:cfg.state_dim + cfg.grid_dim])
+            self.flight.refresh(self.map_tri if self.carve is not None else tri_written)
             self.flight.update(self.poses)
         # rewards / termination / reset bookkeeping
         self._ep_step += 1

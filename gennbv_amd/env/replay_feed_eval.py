@@ -80,9 +80,9 @@ class _LazyAccuracy(_LazyEpisodeInfo):
 class ReplayFeedEvalEnv(ReplayFeedEnv):
     def __init__(self, cfg: TaskConfig, scene: S.Scene, feed, device="cuda:0", max_episode_length: Optional[int] = None,
                  pc_gt: Optional[List[torch.Tensor]] = None, collision=None, collision_mesh=None, accuracy: str = "host",
-                 flight=None):
+                 flight=None, carve=None):
         super().__init__(cfg, scene, _RecordingFeed(feed), device, max_episode_length, collision=collision, collision_mesh=collision_mesh,
-                         flight=flight)
+                         flight=flight, carve=carve)
         self.pc_gt = [p.to(self.device, torch.float32).contiguous() for p in
                       (pc_gt if pc_gt is not None else gt_cloud_from_grid(scene.grid_gt, scene.range_gt, scene.voxel_size))]
         assert len(self.pc_gt) == self.num_envs

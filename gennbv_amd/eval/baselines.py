@@ -131,6 +131,17 @@ class FrontierCandidates:
         return self.base.poses(actions)
 
 
+def planning_grid(env, obs: torch.Tensor) -> torch.Tensor:
+    """The tri-class grid the planners score and route on (GreedyGainPolicy, MapGreedyPolicy, MapCoverPolicy, FrontierViewPolicy
+    and, through them, FrontierCandidates.observe): `env.map_tri`, int8 [N, G^3], where the env keeps a CarvedMap (ops/carve.py:
+    the observation's grid plus the free space along every camera ray), otherwise the observation's grid slice, as ever."""
+    carved = getattr(env, "map_tri", None)
+    if carved is not None:
+        return carved
+    cfg = env.cfg
+    return obs[:, cfg.state_dim:cfg.state_dim + cfg.grid_dim]
+
+
 def _candidates(cfg: TaskConfig, k: int, seed: int, look_at_scene: bool, candidates):
     """The planners' candidate source: LatticeCandidates unless one is given, whose k must be the planner's."""
     if candidates is None:
@@ -254,7 +265,7 @@ class GreedyGainPolicy:
 
     def __call__(self, obs, deterministic: bool = True):
         cfg, n, k = self.cfg, self.num_envs, self.k
-        tri = obs[:, cfg.state_dim:cfg.state_dim + cfg.grid_dim]
+        tri = planning_grid(self.env, obs)
         cand = self._sample(tri)
         poses = self.cands.poses(cand)
         gain = self.gain_backend(tri, poses)
@@ -326,7 +337,7 @@ class MapGreedyPolicy(GreedyGainPolicy):
 
     def __call__(self, obs, deterministic: bool = True):
         cfg, n = self.cfg, self.num_envs
-        tri = obs[:, cfg.state_dim:cfg.state_dim + cfg.grid_dim]
+        tri = planning_grid(self.env, obs)
         cand = self._sample(tri)
         poses = self.cands.poses(cand)
         gain = self.gain_backend(tri, poses)
@@ -428,7 +439,7 @@ class MapCoverPolicy(MapGreedyPolicy):
         cfg, n, t_max = self.cfg, self.num_envs, self.horizon
         env, rows, slots = self.env, self._rows, self._slots
         # ---- 1. plan
-        tri = obs[:, cfg.state_dim:cfg.state_dim + cfg.grid_dim]
+        tri = planning_grid(env, obs)
         cand = self._sample(tri)
         poses = self.cands.poses(cand)
         self.last_gain3 = self.gain_backend(tri, poses)
@@ -549,7 +560,7 @@ class FrontierViewPolicy:
         from ..ops.frontier import block_centroids, top_blocks
         from ..ops.frontier_view import aim_indices, block_target_voxels, node_actions
         cfg, rows = self.cfg, self._rows
-        tri = obs[:, cfg.state_dim:cfg.state_dim + cfg.grid_dim]
+        tri = planning_grid(self.env, obs)
         fb = self.fallback(obs, deterministic)[0].to(torch.int64)
         blocks = self.frontier(tri)
         count = blocks[..., 0]

@@ -6,6 +6,10 @@ before their first occupied voxel, the same over the rays that meet one, and the
 include/gennbv_hip.h gnbv_view_gain).  One launch for all N x K candidates; outputs are preallocated and reused: a result is
 valid until the next call.  GPU only, no CPU fallback.
 
+With `depth` (the raw depth images measured at the poses) the same call is the view gain of a MEASURED frame: every ray ends
+where its pixel's depth says, and `carve_out` receives -1 in every unknown voxel a ray crossed (ops/carve.py CarvedMap is the
+map built on it).
+
 ViewGain keeps an env's grid in LDS (grid_size <= 64); ViewGainSlab computes the same integers for grid_size <= 128 through
 gnbv_view_gain_slab (the rays' fates first, then slabs of x-planes) with a preallocated workspace; make_view_gain picks.
 """
@@ -58,12 +62,18 @@ class ViewGain:
         a.h, a.w, a.stride, a.range = self.h, self.w, self.stride, self.range_m
         a.gain, a.c2w_out = self.gain.data_ptr(), _lib.ptr(self.c2w)
         a.chunk, a.ablate = int(chunk), 0
+        self.depth_sense_dist = float(cfg.depth_sense_dist)
         self._args = a
 
-    def __call__(self, tri: torch.Tensor, poses: torch.Tensor) -> torch.Tensor:
+    def __call__(self, tri: torch.Tensor, poses: torch.Tensor, depth: Optional[torch.Tensor] = None,
+                 carve_out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """tri: int8 rows [N, G^3] (or [N,G,G,G]; unit element stride, any row stride) or the fp32 grid slice of a flat
         observation (converted with one .to(torch.int8)); poses [N,K,6] f32 (x, y, z, roll, pitch, yaw), env-local.
-        -> gain [N,K,3] int32 (unknown, unknown_hit, blocked)."""
+        -> gain [N,K,3] int32 (unknown, unknown_hit, blocked).
+        depth: None, or the raw depth images measured at the poses, f32 [N,K,H,W] ([N,H,W] with K = 1): the view gain of a
+        measured frame (include/gennbv_hip.h), rays ended by their pixel's depth.  carve_out: with depth only, int8 rows
+        [N, G^3] (unit element stride) in which every unknown voxel a ray visited becomes -1; it may be `tri` itself where the
+        header allows it (K = 1, or the slab operators)."""
         _lib.require_cuda(tri, poses)
         n, k, g3 = self.num_envs, self.k, self.g ** 3
         if tri.dtype != torch.int8:
@@ -79,6 +89,25 @@ class ViewGain:
         poses = poses.contiguous()
         a = self._args
         a.tri_i8, a.tri_row_stride, a.poses = tri.data_ptr(), max(int(tri.stride(0)), g3), poses.data_ptr()
+        a.depth_raw = a.carve_i8 = None
+        a.depth_env_stride = a.depth_cand_stride = a.carve_row_stride = 0
+        a.depth_sense_dist = 0.0
+        if carve_out is not None and depth is None:
+            raise _lib.GennbvHipError("ViewGain: carve_out needs depth")
+        if depth is not None:
+            _lib.require_cuda(depth)
+            hw = self.h * self.w
+            if depth.dtype != torch.float32 or depth.shape[0] != n or depth.numel() != n * k * hw:
+                raise _lib.GennbvHipError(f"ViewGain: depth must be f32 [{n}, {k}, {self.h}, {self.w}], got {depth.dtype} {tuple(depth.shape)}")
+            depth = depth.contiguous()
+            a.depth_raw, a.depth_env_stride, a.depth_cand_stride = depth.data_ptr(), k * hw, hw
+            a.depth_sense_dist = self.depth_sense_dist
+            if carve_out is not None:
+                _lib.require_cuda(carve_out)
+                if carve_out.dtype != torch.int8 or carve_out.dim() != 2 or carve_out.shape != (n, g3) or carve_out.stride(1) != 1:
+                    raise _lib.GennbvHipError(f"ViewGain: carve_out must be int8 rows [{n}, {g3}] with unit element stride, got "
+                                              f"{carve_out.dtype} {tuple(carve_out.shape)}")
+                a.carve_i8, a.carve_row_stride = carve_out.data_ptr(), max(int(carve_out.stride(0)), g3)
         self._launch(a)
         return self.gain
 

@@ -1028,8 +1028,37 @@ typedef struct GnbvViewGain {
     int chunk;                      /* candidates per workgroup, 0 = chosen from n and k (any value gives the same result) */
     int ablate;                     /* measurements only, 0 otherwise: bit 0 walk without marking (the counts are then 0),
                                      * bit 1 no second mask (unknown_hit is then 0) */
+    /* the view gain of a MEASURED frame (below); all zero / NULL: the rule above, bit for bit */
+    const float *depth_raw;         /* raw camera depth as gnbv_render_depth writes it, or NULL: candidate j of env e reads
+                                     * [h, w] floats, row-major, at depth_raw + e depth_env_stride + j depth_cand_stride */
+    int64_t depth_env_stride, depth_cand_stride; /* in floats, >= h w; a candidate stride of 0 is legal with k == 1 */
+    float depth_sense_dist;         /* the updater's value: negative and finite */
+    int8_t *carve_i8;               /* [n, g^3] with a row stride in BYTES (>= g^3), or NULL; only with depth_raw */
+    int64_t carve_row_stride;
 } GnbvViewGain;
 int gnbv_view_gain(const GnbvViewGain *args /*[host]*/, void *stream);
+
+/* The view gain of a measured frame: what the frame revealed.  With args->depth_raw != NULL every one of the four entry points
+ * gnbv_view_gain, gnbv_view_gain_masks, gnbv_view_gain_slab and gnbv_view_gain_slab_masks ends the ray of lattice pixel (u, v) by
+ * the pixel's raw depth r instead of by `range`:
+ *   - the ray is SURFACE-ENDED iff r is finite, r != 0, r > depth_sense_dist and |r| <= range; its length is then |r|, exactly the
+ *     depth gnbv_voxel_update's A1 gives that pixel;
+ *   - every other ray is RANGE-ENDED with length `range`: -inf, NaN, +-0, a value at or below the clamp, a hit beyond `range`;
+ *   - the ray ends at the world point gnbv_back_projection gives the pixel at that length; source voxel, target voxel, the line,
+ *     its in-grid voxels in order and the stop in front of the first occupied voxel are gnbv_view_gain's, unchanged;
+ *   - on a surface-ended ray a visited voxel equal to the ray's target voxel is not marked and not counted: a surface is there.
+ *     On a range-ended ray it is a voxel like any other.
+ * gain, unknown_bits, hit_bits and c2w_out keep their meaning and layouts over this ray set.  carve_i8[e, lin] = -1 for every
+ * voxel of U(e, j) of any candidate j: plain byte stores of one value, and no other byte of the row is touched.  carve_i8 may be
+ * tri_i8 (same pointer, same stride) with k == 1 in gnbv_view_gain / _masks, where one workgroup owns the env and packs the row
+ * before it stores, and with any k in the slab entry points, where the first kernel packs every row.  The kernels are compile-time
+ * variants of their own: a call without depth_raw runs the code it ran before.  Deterministic, no global atomics beyond those of
+ * gnbv_view_gain_slab / _masks, no workspace growth, no allocation, no host synchronisation; `chunk` and `slab` do not change
+ * the result.
+ * Returns hipErrorInvalidValue, before any launch, also for: a depth stride below h w (a candidate stride of 0 with k > 1
+ * included), depth_sense_dist not finite or >= 0, carve_i8 without depth_raw, with ablate != 0 or with a row stride below g^3,
+ * and any other overlap of carve_i8 and tri_i8.  The test is made on the two SPANS [base, base + (n - 1) stride + g^3), not row
+ * by row: interleaved rows that are pairwise disjoint (carve_i8 = tri_i8 + g^3 with both strides 2 g^3) are refused too. */
 
 /* gnbv_view_gain that keeps the sets it counts (a new entry point of ABI 5).  Rays, camera, source and target voxels, walk and
  * stop rule are gnbv_view_gain's, unchanged.  For env e and candidate j, U(e, j) = the distinct unknown voxels visited by any ray

@@ -1,7 +1,8 @@
 """Closed-loop table of DESIGN.md "Flying on the scanned map": the greedy planner with the privileged flight field beside the
 pilot that knows only its own map.
 
-    python tools/closed_loop_belief.py [--envs 16] [--grid 20] [--steps 20] [--k 32] [--seeds 1] [--stride 2] [--penalties 1,5,20] [--out FILE.json]
+    python tools/closed_loop_belief.py [--envs 16] [--grid 20] [--steps 20] [--k 32] [--seeds 1] [--stride 2] [--penalties 1,5,20] [--carve] [--carve-stride 2]
+                                        [--out FILE.json]
 
 The set-up of tools/closed_loop_flight.py (box scenes, 60 x 80 camera, CollisionBody(sweep=True), episodes of at most `steps`
 steps, each env's first episode).  Rows:
@@ -20,6 +21,14 @@ straight (privileged: the straight flight was free; belief: no route node was fl
 collision and by a pose collision, for the belief rows the share of decisions in which every candidate was refused, and for
 the shortcut rows the mean number of waypoints a step's straight first leg skipped, and for the cautious rows the mean
 env.route_unknown per flown step (costly nodes entered).  Reported, not asserted.
+
+`--carve` gives the belief rows' envs a CarvedMap (ops/carve.py; `--carve-stride` is its pixel lattice): the pilot's field and the
+planner read the observation's grid plus the free space along every camera ray.  The privileged row does not change.  Two more
+columns then: the mean share of free voxels on the map at the episode's end, beside the observation's.  The belief rows also
+report, with or without --carve, `mean_routed_nodes`: the lattice nodes the field holds a route to, per decision of a live env
+(1: the drone's own node and nothing else), and `path_collisions_on_a_route`: of the episodes ended by a path collision, the
+share whose last step flew a route of the field (the others flew the straight fallback of a decision without a reachable
+candidate).
 """
 from __future__ import annotations
 
@@ -40,6 +49,7 @@ from gennbv_amd.env.mesh_scene import MeshScene  # noqa: E402
 from gennbv_amd.env.render_feed import RenderFeed  # noqa: E402
 from gennbv_amd.env.replay_feed import ReplayFeedEnv  # noqa: E402
 from gennbv_amd.eval.baselines import GreedyGainPolicy, MapGreedyPolicy  # noqa: E402
+from gennbv_amd.ops.carve import CarvedMap  # noqa: E402
 from gennbv_amd.ops.flight_field import BeliefFlightField, FlightField  # noqa: E402
 
 DEV = "cuda:0"
@@ -54,10 +64,14 @@ def run(policy, env, steps):
     cautious = belief and env.route_unknown is not None
     shortcut = belief and bool(getattr(env.flight, "shortcut", False))
     code = torch.zeros(n, dtype=torch.uint8, device=DEV)
+    cfg = env.cfg
+    free_map, free_obs, nodes = torch.zeros(n, device=DEV), torch.zeros(n, device=DEV), torch.zeros(n, device=DEV)
+    last_routed = torch.zeros(n, dtype=torch.bool, device=DEV)
     for t in range(steps):
         act = policy(obs)[0]
         if belief:
             stuck += (alive & (policy._contact != 0).all(dim=1)).float()
+            nodes += torch.where(alive, (env.flight.field != -1).sum(dim=1), torch.zeros_like(alive, dtype=torch.int64)).float()
         decisions += alive.float()
         obs, _, done, _ = env.step(act)
         moved += alive.float()  # reset() set the first pose: every step of an env's first episode is flown
@@ -73,6 +87,11 @@ def run(policy, env, steps):
             unknown += torch.where(alive, env.route_unknown, torch.zeros_like(env.route_unknown)).float()
         flown = torch.where(alive, env.flight_length, flown)
         ends = alive & done
+        if env.map_tri is not None:  # (a done env's row shows the finished episode's grid until its next step)
+            free_map = torch.where(ends, (env.map_tri < 0).float().mean(dim=1), free_map)
+            free_obs = torch.where(ends, (obs[:, cfg.state_dim:cfg.state_dim + cfg.grid_dim] < 0).float().mean(dim=1), free_obs)
+        if belief:
+            last_routed = torch.where(ends, env.routed, last_routed)
         final = torch.where(ends, env.coverage_ratio, final)
         length = torch.where(ends, torch.full_like(length, t + 1), length)
         code = torch.where(ends, env.collision_buf, code)
@@ -90,6 +109,10 @@ def run(policy, env, steps):
     if belief:
         out["all_candidates_unreachable_share"] = float(stuck.sum() / decisions.sum().clamp(min=1.0))
         out["route_overflows"] = int(env.route_overflow)
+        out["mean_routed_nodes"] = float(nodes.sum() / decisions.sum().clamp(min=1.0))
+        out["path_collisions_on_a_route"] = float((path_hit & last_routed).float().sum() / path_hit.float().sum().clamp(min=1.0))
+    if env.map_tri is not None:
+        out["free_share_map"], out["free_share_observation"] = float(free_map.mean()), float(free_obs.mean())
     if shortcut:
         out["mean_skipped"] = float(skipped.sum() / moved.sum().clamp(min=1.0))
     if cautious:
@@ -106,6 +129,8 @@ def main():
     ap.add_argument("--seeds", default="1")
     ap.add_argument("--stride", type=int, default=2)
     ap.add_argument("--penalties", default="1,5,20", help="the cautious rows' unknown_penalty_m, metres per unknown node entered")
+    ap.add_argument("--carve", action="store_true", help="the belief rows fly and plan on a CarvedMap: free space along every camera ray")
+    ap.add_argument("--carve-stride", type=int, default=2, help="the CarvedMap's pixel lattice")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -117,7 +142,8 @@ def main():
     body = CollisionBody(sweep=True)
     lattice = FlightLattice(cfg, stride=args.stride)
     blocked = mesh.flight_blocked(lattice, body)  # once per scene set
-    res = {"envs": n, "grid": g, "steps": args.steps, "k": args.k, "stride": args.stride, "rows": []}
+    res = {"envs": n, "grid": g, "steps": args.steps, "k": args.k, "stride": args.stride, "carve": bool(args.carve),
+           "carve_stride": args.carve_stride if args.carve else None, "rows": []}
     for seed in (int(s) for s in args.seeds.split(",")):
         names = ["greedy / privileged", "map-greedy / optimistic", "map-greedy / conservative"]
         names += [f"map-greedy / cautious {p} m" for p in args.penalties.split(",")]
@@ -130,7 +156,11 @@ def main():
                     dict(unknown="free" if kind == "optimistic" else "blocked")
                 flight = BeliefFlightField(n, lattice, body, scene.range_gt, scene.voxel_size, g, device=DEV,
                                            shortcut=name.endswith("shortcut"), **kw)
-            env = ReplayFeedEnv(cfg, scene, RenderFeed(mesh, cfg), DEV, max_episode_length=args.steps, collision=body, flight=flight)
+            carve = None
+            if args.carve and not name.startswith("greedy"):
+                carve = CarvedMap(n, cfg, scene.range_gt, scene.voxel_size, stride=args.carve_stride, device=DEV)
+            env = ReplayFeedEnv(cfg, scene, RenderFeed(mesh, cfg), DEV, max_episode_length=args.steps, collision=body, flight=flight,
+                                carve=carve)
             pol = (GreedyGainPolicy if name.startswith("greedy") else MapGreedyPolicy)(env, k=args.k, weights=(1, 4), seed=seed)
             row = {"seed": seed, "row": name}
             row.update(run(pol, env, args.steps))

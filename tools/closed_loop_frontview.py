@@ -1,7 +1,8 @@
 """Closed-loop table of DESIGN.md "Frontier viewpoints": the nearest-frontier planner beside the map-greedy rows of the frontier table.
 
     python tools/closed_loop_frontview.py [--envs 8] [--grid 20] [--steps 20] [--k 32] [--seeds 1,2] [--top 8] [--block 4]
-                                          [--r_min_m 1.0] [--r_max_m 4.0] [--voxel_value_mm 50] [--stride 2] [--out FILE.json]
+                                          [--r_min_m 1.0] [--r_max_m 4.0] [--voxel_value_mm 50] [--stride 2] [--carve] [--carve-stride 2]
+                                          [--out FILE.json]
 
 The set-up of tools/closed_loop_frontier.py's map-greedy rows: ReplayFeedEvalEnv over RenderFeed(MeshScene.from_boxes(make_scenes(
 envs, grid, seed=1))), 60 x 80 camera, `steps`-step episodes, CollisionBody(sweep=True), BeliefFlightField(unknown="free") over the
@@ -15,6 +16,8 @@ stride-`stride` flight lattice.  Rows, per seed:
 Columns: final coverage (mean over envs of coverage_ratio on each env's done step), mean_AUC, mean episode length, the mean of
 env.flight_length on the done step (metres flown in the episode), and the share of decisions that fell back (0 for the map-greedy
 rows: they have no fallback).  Small samples: reported, not asserted.
+`--carve` gives every row's env a CarvedMap (ops/carve.py; `--carve-stride` is its pixel lattice): field, frontier and view gain
+then read the observation's grid plus the free space along every camera ray.
 """
 from __future__ import annotations
 
@@ -37,6 +40,7 @@ from gennbv_amd.env.render_feed import RenderFeed  # noqa: E402
 from gennbv_amd.env.replay_feed_eval import ReplayFeedEvalEnv  # noqa: E402
 from gennbv_amd.eval import evaluate_policy_grid_obs  # noqa: E402
 from gennbv_amd.eval.baselines import FrontierCandidates, FrontierViewPolicy, MapGreedyPolicy  # noqa: E402
+from gennbv_amd.ops.carve import CarvedMap  # noqa: E402
 from gennbv_amd.ops.flight_field import BeliefFlightField  # noqa: E402
 from gennbv_amd.ops.frontier import Frontier  # noqa: E402
 
@@ -91,6 +95,8 @@ def main():
     ap.add_argument("--r_max_m", type=float, default=4.0)
     ap.add_argument("--voxel_value_mm", type=int, default=50)
     ap.add_argument("--stride", type=int, default=2)
+    ap.add_argument("--carve", action="store_true", help="every row flies and plans on a CarvedMap: free space along every camera ray")
+    ap.add_argument("--carve-stride", type=int, default=2, help="the CarvedMap's pixel lattice")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -102,12 +108,14 @@ def main():
     body = CollisionBody(sweep=True)
     lattice = FlightLattice(cfg, stride=args.stride)
     res = {k: getattr(args, k) for k in ("envs", "grid", "steps", "k", "top", "block", "r_min_m", "r_max_m", "voxel_value_mm", "stride")}
-    res["rows"] = []
+    res["carve"], res["rows"] = bool(args.carve), []
     names = ("map-greedy / uniform", "map-greedy / frontier aim", "frontier view / nearest", f"frontier view / value {args.voxel_value_mm}")
     for seed in (int(s) for s in args.seeds.split(",")):
         for name in names:
             flight = BeliefFlightField(n, lattice, body, scene.range_gt, scene.voxel_size, g, unknown="free", device=DEV)
-            env = ReplayFeedEvalEnv(cfg, scene, RenderFeed(mesh, cfg), DEV, max_episode_length=args.steps, collision=body, flight=flight)
+            carve = CarvedMap(n, cfg, scene.range_gt, scene.voxel_size, stride=args.carve_stride, device=DEV) if args.carve else None
+            env = ReplayFeedEvalEnv(cfg, scene, RenderFeed(mesh, cfg), DEV, max_episode_length=args.steps, collision=body, flight=flight,
+                                    carve=carve)
             cands = None
             if name.endswith("aim"):
                 cands = FrontierCandidates(cfg, args.k, seed, Frontier(n, g, block=args.block, device=DEV), scene.range_gt,
