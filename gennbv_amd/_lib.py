@@ -126,6 +126,7 @@ SIGNATURES = {
     "gnbv_cover_greedy": (_i, [_p, _p]),
     "gnbv_cover_greedy_w": (_i, [_p, _p]),
     "gnbv_tour_route": (_i, [_p, _p]),
+    "gnbv_depth_sensor": (_i, [_p, _p]),
     "gnbv_gae_sb3": (_i, [_p, _p, _p, _p, _p, _i, _i, _d, _d, _p, _p, _p]),
     "gnbv_gae_rsl": (_i, [_p, _p, _p, _p, _i, _i, _d, _d, _p, _p, _p]),
 }
@@ -210,6 +211,14 @@ class GnbvTourRoute(C.Structure):
     """include/gennbv_hip.h: GnbvTourRoute"""
     _fields_ = [("n", _i), ("p", _i), ("dist_mm", _p), ("count", _p), ("max_moves", _i), ("order", _p), ("routed", _p),
                 ("length_mm", _p), ("status", _p)]
+
+
+class GnbvDepthSensor(C.Structure):
+    """include/gennbv_hip.h: GnbvDepthSensor"""
+    _fields_ = [("n", _i), ("h", _i), ("w", _i), ("depth_in", _p), ("seg_in", _p), ("in_env_stride", _i64), ("depth_out", _p),
+                ("seg_out", _p), ("out_env_stride", _i64), ("frame", _p), ("seed", C.c_uint64), ("min_range", _f), ("max_range", _f),
+                ("edge_radius", _i), ("edge_abs", _f), ("edge_rel", _f), ("edge_drop", _u32), ("drop", _u32), ("sigma0", _f),
+                ("sigma1", _f), ("sigma2", _f), ("gauss_lut", _p), ("quant", _f)]
 
 
 class GnbvEncoderParams(C.Structure):

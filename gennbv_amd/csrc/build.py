@@ -17,7 +17,7 @@ PKG = os.path.dirname(HERE)
 OUT = os.path.join(PKG, "libgennbv_hip.so")
 SOURCES = ["voxel.hip", "gae.hip", "envstep.hip", "encoder.hip", "linear.hip", "head.hip", "chamfer.hip", "ppo.hip", "imitation.hip", "render.hip",
            "voxelize.hip", "collide.hip", "sweep.hip", "flight.hip", "flightmap.hip", "sweepmap.hip", "frontier.hip", "frontview.hip", "scan.hip", "viewgain.hip", "viewcover.hip", "covergreedy.hip",
-           "tour.hip"]
+           "tour.hip", "sensor.hip"]
 HEADERS = ["common.h", "conv_split.h", "conv_splitx.h", "backproject.h", "raytrace.h", "scene_cells.h", "voxel_frame.h", "voxel_plan.h", "encoder_plan.h", "map_bits.h", "seg_box.h", "ray_walk.h", "view_kernels.h",
            os.path.join("..", "..", "include", "gennbv_hip.h")]
 ARCH = "gfx950"

@@ -1286,6 +1286,68 @@ typedef struct GnbvTourRoute {
 } GnbvTourRoute;
 int gnbv_tour_route(const GnbvTourRoute *args /*[host]*/, void *stream);
 
+/* ------------------------------------------------------------------------- */
+/* Depth sensor model: what a real depth camera would have returned for a      */
+/* frame of gnbv_render_depth -- range limits, dropouts at depth edges and at  */
+/* random, range noise, disparity quantisation (a new entry point of ABI 5).   */
+/* ------------------------------------------------------------------------- */
+/* Input frame depth_in / seg_in: f32 [n, h, w] as gnbv_render_depth writes them, rows contiguous, env e at base + e in_env_stride
+ * (in floats, >= h w); output frame depth_out / seg_out the same with out_env_stride.  r is the raw value and t = -r.
+ * GNBV_DEPTH_NO_RETURN (below) is the raw depth of a pixel the sensor got no return for.
+ * Every fp32 operation is the correctly rounded one (fadd, fsub, fmul, fdiv = the _rn intrinsics), in the order given.
+ *
+ * Class of an input pixel, from the input alone:
+ *   MISS  r == -inf;
+ *   RET   t finite and min_range <= t <= max_range;
+ *   FAR   t finite and t > max_range;
+ *   VOID  everything else: NaN, +inf, t <= 0, t < min_range.
+ * MISS and FAR give (-inf, 0.0f); VOID gives (GNBV_DEPTH_NO_RETURN, 0.0f).  A RET pixel p = (e, v, u), in this order:
+ *   1. (w0, w1, w2, w3) = Philox4x32-10 of the counter (v w + u, e, frame[e], 0) under the key (seed & 0xffffffff, seed >> 32);
+ *      frame is int32 [n] on the device, read and never written.  All four words are drawn whichever effects are enabled.
+ *   2. edge test, skipped when edge_radius == 0: thr = fadd(edge_abs, fmul(edge_rel, t_p)); p is an EDGE pixel iff some q != p of
+ *      the (2 edge_radius + 1)^2 window around p, inside the image, is not RET, or is RET with fabsf(fsub(t_q, t_p)) > thr
+ *      (neighbours outside the image are ignored).  An edge pixel is dropped iff edge_drop == 0xFFFFFFFF, or edge_drop != 0 and
+ *      w0 < edge_drop.
+ *   3. random dropout: the pixel is dropped iff drop == 0xFFFFFFFF, or drop != 0 and w1 < drop.
+ *   4. range noise: z = gauss_lut[w2 >> 20] (the caller's table of 4096 floats on the device; 0 where it is NULL);
+ *      sigma = fadd(fadd(sigma0, fmul(sigma1, t)), fmul(sigma2, fmul(t, t)));  t1 = fadd(t, fmul(sigma, z)).
+ *   5. disparity quantisation: t2 = quant > 0 ? fdiv(quant, rintf(fdiv(quant, t1))) : t1 (rintf rounds ties to even).
+ *   6. a dropped pixel gives (GNBV_DEPTH_NO_RETURN, 0); else !(t2 >= min_range) gives (GNBV_DEPTH_NO_RETURN, 0); else
+ *      t2 > max_range (+inf from a zero divisor included) gives (-inf, 0); else (-t2, seg_in[p]) with the seg bits copied.
+ * The result is a pure function of (the inputs, seed, frame[e], e, v, u): it depends neither on n, nor on the launch shape, nor
+ * on what other envs hold.
+ *
+ * Why the no-return value is a tiny negative number and not NaN or 0: under the measured-frame rule of gnbv_view_gain above, NaN,
+ * +-0 and -inf are RANGE-ENDED, so a carve would free a dropped pixel's ray all the way to the sensor's range, straight through
+ * whatever the sensor failed to see.  -2^-100 is finite, non-zero and above the clamp: SURFACE-ENDED with length 2^-100, its
+ * target voxel the camera's own, so the ray marks and carves nothing; with seg 0 the pixel is not foreground, so the voxel
+ * update and the scan set ignore it.
+ *
+ * One launch on the caller's stream; no workspace, no allocation, no host synchronisation, no atomics.  Every output element of
+ * every env's h w block is written; bytes between the blocks are not touched.
+ * Returns hipErrorInvalidValue, before any launch, for: a NULL struct; n, h or w < 1; h w > 2^32 - 1; an env stride below h w; a
+ * NULL depth_in, seg_in, depth_out, seg_out or frame; gauss_lut NULL with a sigma above 0; any overlap of an output span
+ * [base, base + (n - 1) stride + h w) with an input span or of the two output spans (the stencil reads neighbours: in place is
+ * refused); and any parameter outside the ranges noted in the struct.  [host struct]; pointers are device. */
+#define GNBV_DEPTH_NO_RETURN (-0x1p-100f)
+typedef struct GnbvDepthSensor {
+    int n, h, w;
+    const float *depth_in, *seg_in;
+    int64_t in_env_stride;
+    float *depth_out, *seg_out;
+    int64_t out_env_stride;
+    const int32_t *frame;            /* [n] device */
+    uint64_t seed;
+    float min_range, max_range;      /* 0 < min_range <= max_range, finite */
+    int edge_radius;                 /* 0..2 */
+    float edge_abs, edge_rel;        /* >= 0, finite */
+    uint32_t edge_drop, drop;        /* thresholds on a 32-bit word: 0 never, 0xFFFFFFFF always */
+    float sigma0, sigma1, sigma2;    /* >= 0, finite */
+    const float *gauss_lut;          /* [4096] device; may be NULL iff all three sigmas are 0 */
+    float quant;                     /* >= 0, finite; 0 = off */
+} GnbvDepthSensor;
+int gnbv_depth_sensor(const GnbvDepthSensor *args /*[host]*/, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,6 +3,7 @@ pilot that knows only its own map.
 
     python tools/closed_loop_belief.py [--envs 16] [--grid 20] [--steps 20] [--k 32] [--seeds 1] [--stride 2] [--penalties 1,5,20] [--carve] [--carve-stride 2]
                                         [--out FILE.json]
+                                        [--sensor-sigma a,b,c] [--sensor-drop p] [--sensor-edge r,abs,rel,p] [--sensor-quant q] [--sensor-range lo,hi]
 
 The set-up of tools/closed_loop_flight.py (box scenes, 60 x 80 camera, CollisionBody(sweep=True), episodes of at most `steps`
 steps, each env's first episode).  Rows:
@@ -29,6 +30,12 @@ report, with or without --carve, `mean_routed_nodes`: the lattice nodes the fiel
 (1: the drone's own node and nothing else), and `path_collisions_on_a_route`: of the episodes ended by a path collision, the
 share whose last step flew a route of the field (the others flew the straight fallback of a decision without a reachable
 candidate).
+
+Any `--sensor-*` flag puts a DepthSensor (ops/depth_sensor.py) between the renderer and the env of every row: range noise of
+sigma = a + b t + c t^2 metres, random dropouts of probability p, dropouts of probability p at depth edges (window radius r, step
+above abs + rel t), disparity quantisation t = q / round(q / t), returns outside [lo, hi] metres lost (default 0.1 to 50 m, the
+updater's clamp).  Every row's sensor starts from the same seed and frame counters.  Without such a flag there is no sensor and
+the output is what it was.
 """
 from __future__ import annotations
 
@@ -50,6 +57,7 @@ from gennbv_amd.env.render_feed import RenderFeed  # noqa: E402
 from gennbv_amd.env.replay_feed import ReplayFeedEnv  # noqa: E402
 from gennbv_amd.eval.baselines import GreedyGainPolicy, MapGreedyPolicy  # noqa: E402
 from gennbv_amd.ops.carve import CarvedMap  # noqa: E402
+from gennbv_amd.ops.depth_sensor import DepthSensor  # noqa: E402
 from gennbv_amd.ops.flight_field import BeliefFlightField, FlightField  # noqa: E402
 
 DEV = "cuda:0"
@@ -132,6 +140,11 @@ def main():
     ap.add_argument("--carve", action="store_true", help="the belief rows fly and plan on a CarvedMap: free space along every camera ray")
     ap.add_argument("--carve-stride", type=int, default=2, help="the CarvedMap's pixel lattice")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--sensor-sigma", default=None, help="a,b,c: range noise of a + b t + c t^2 metres")
+    ap.add_argument("--sensor-drop", type=float, default=None, help="probability of a random dropout")
+    ap.add_argument("--sensor-edge", default=None, help="r,abs,rel,p: pixels with a step above abs + rel t within radius r drop with probability p")
+    ap.add_argument("--sensor-quant", type=float, default=None, help="disparity quantisation: t = q / round(q / t)")
+    ap.add_argument("--sensor-range", default=None, help="lo,hi: returns outside it are lost")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("closed_loop_belief needs a GPU")
@@ -144,6 +157,14 @@ def main():
     blocked = mesh.flight_blocked(lattice, body)  # once per scene set
     res = {"envs": n, "grid": g, "steps": args.steps, "k": args.k, "stride": args.stride, "carve": bool(args.carve),
            "carve_stride": args.carve_stride if args.carve else None, "rows": []}
+    sensor_kw = None
+    if any(v is not None for v in (args.sensor_sigma, args.sensor_drop, args.sensor_edge, args.sensor_quant, args.sensor_range)):
+        lo, hi = (float(x) for x in (args.sensor_range or "0.1,50").split(","))
+        r, e_abs, e_rel, e_p = (float(x) for x in (args.sensor_edge or "0,0,0,0").split(","))
+        sensor_kw = dict(min_range_m=lo, max_range_m=hi, edge_radius=int(r), edge_abs_m=e_abs, edge_rel=e_rel, edge_drop=e_p,
+                         drop=args.sensor_drop or 0.0, sigma=tuple(float(x) for x in (args.sensor_sigma or "0,0,0").split(",")),
+                         quant=args.sensor_quant or 0.0)
+        res["sensor"] = dict(sensor_kw)
     for seed in (int(s) for s in args.seeds.split(",")):
         names = ["greedy / privileged", "map-greedy / optimistic", "map-greedy / conservative"]
         names += [f"map-greedy / cautious {p} m" for p in args.penalties.split(",")]
@@ -159,7 +180,8 @@ def main():
             carve = None
             if args.carve and not name.startswith("greedy"):
                 carve = CarvedMap(n, cfg, scene.range_gt, scene.voxel_size, stride=args.carve_stride, device=DEV)
-            env = ReplayFeedEnv(cfg, scene, RenderFeed(mesh, cfg), DEV, max_episode_length=args.steps, collision=body, flight=flight,
+            sensor = DepthSensor(n, cfg.camera_height, cfg.camera_width, seed=seed, device=DEV, **sensor_kw) if sensor_kw else None
+            env = ReplayFeedEnv(cfg, scene, RenderFeed(mesh, cfg, sensor=sensor), DEV, max_episode_length=args.steps, collision=body, flight=flight,
                                 carve=carve)
             pol = (GreedyGainPolicy if name.startswith("greedy") else MapGreedyPolicy)(env, k=args.k, weights=(1, 4), seed=seed)
             row = {"seed": seed, "row": name}
